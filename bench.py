@@ -16,14 +16,21 @@ games = 3,981,312 parent positions (81 per game), and one step is
   positions chained, king-move refreshes from the block's king cache) + the
   Eval::evaluate epilogue with to_cp,
 ~127 M evaluated positions per GPU per step, i.e. >= 1e9 per step on 8 GPUs.
-The timed step's own outputs are verified: a device checksum of every parent and
+A plain run does only what `value` needs: it sets up, warms up, times the K steps and
+prints the line (`ms_per_step`: the milliseconds one timed step took; the roofline block is
+computed from the timed steps' own events).  `--dump-outputs DIR` also writes a fixed, seeded
+sample of the last timed step's outputs as DIR/<name>.npy (float64; dump_expand / dump_eval),
+so that two builds can be compared output for output: the inputs are the same from run to run.
+Everything else is behind `--full`:
+the timed step's own outputs are verified: a device checksum of every parent and
 child result against the same expansion run the plain way (one workgroup per
 parent, every parent refreshed, no king cache), and sampled parents with all
-their children against the CPU oracle.
-Secondary results (same JSON object, not `value`):
+their children against the CPU oracle; the CPU baseline; the result gather at N > 1;
+and the secondary results (same JSON object, not `value`):
   big16m  configs[2]: big-net full refresh of 16,777,216 positions per GPU;
   small1m configs[1]: small-net evaluation of 1,048,576 positions per GPU;
-each with an oracle check of 4,096 of the timed outputs.
+each with an oracle check of 4,096 of the timed outputs; then the depth-2 expansion, the
+C-ABI host path and the drop-in's call shape (grandchild, abi_games, dropin).
 
 All inputs are generated on the GPU by the same seeded playout code the host
 uses (`value` never includes host transfers), per-GPU work is fixed as N grows
@@ -214,7 +221,63 @@ class Ctx:
         self.nn.close()
 
 
-def run_eval(c: Ctx, wl: dict, n: int, steps: int, warmup: int, max_plies: int, check: int):
+DUMP_RUN = 64        # --dump-outputs, expand: consecutive parents per sampled run (chains, king cache)
+DUMP_RUNS = 256      # ... and sampled runs: 16,384 parents with all their children, about 35 MB
+DUMP_EVALS = 1 << 19  # --dump-outputs, eval workloads: sampled positions (29 MB)
+DUMP_LIMIT = 60 << 20  # bytes of all the arrays written together
+
+
+def _fields64(rec: np.ndarray) -> np.ndarray:
+    """gn_eval records as a float64 matrix, one column per field in record order (psqt, positional,
+    final_v, final_cp, score, flags, best_move): every field is an integer of <= 32 bits, exact."""
+    return np.stack([rec[f].astype(np.float64) for f in rec.dtype.names], axis=1)
+
+
+def _save(dump_dir: str, arrays: dict):
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+
+
+def dump_expand(c: Ctx, out: dict, n: int, children: int, dump_dir: str):
+    """--dump-outputs for the expansion: what a caller of the timed path receives (parent records,
+    child offsets, child moves, child records), for a fixed seeded sample of runs of consecutive
+    parents with all their children.  parent_index names the sampled parents, totals the whole
+    step's (parents, children)."""
+    G = c.G
+    run = min(DUMP_RUN, n)
+    slots = n // run
+    starts = np.sort(np.random.default_rng(SEED).choice(slots, size=min(DUMP_RUNS, slots), replace=False)) * run
+    offs = out["off"].download(np.uint32, n + 1).astype(np.int64)
+    idx, counts, pev, mv, cev, size = [], [], [], [], [], 0
+    for s in starts.tolist():
+        lo, hi = int(offs[s]), int(offs[s + run])
+        size += run * 72 + (hi - lo) * 64  # (float64: 9 per parent, 8 per child)
+        if size > DUMP_LIMIT:
+            break
+        idx.append(np.arange(s, s + run))
+        counts.append(np.diff(offs[s:s + run + 1]))
+        pev.append(out["po"].download(G.EVAL_DTYPE, run, offset=s))
+        mv.append(out["mv"].download(np.uint16, hi - lo, offset=lo))
+        cev.append(out["co"].download(G.EVAL_DTYPE, hi - lo, offset=lo))
+    _save(dump_dir, {"parent_index": np.concatenate(idx).astype(np.float64),
+                     "parent_evals": _fields64(np.concatenate(pev)),
+                     "child_counts": np.concatenate(counts).astype(np.float64),
+                     "child_moves": np.concatenate(mv).astype(np.float64),
+                     "child_evals": _fields64(np.concatenate(cev)),
+                     "totals": np.array([n, children], dtype=np.float64)})
+
+
+def dump_eval(out: np.ndarray, dump_dir: str):
+    """--dump-outputs for the eval workloads: a fixed seeded sample of the timed launch's records."""
+    n = len(out)
+    idx = np.sort(np.random.default_rng(SEED).choice(n, size=min(DUMP_EVALS, n), replace=False))
+    _save(dump_dir, {"index": idx.astype(np.float64), "evals": _fields64(out[idx])})
+
+
+def run_eval(c: Ctx, wl: dict, n: int, steps: int, warmup: int, max_plies: int, check: int,
+             dump_dir: str | None = None):
     """Full-refresh batch evaluation of n device-resident positions per GPU."""
     G, nn, mode = c.G, c.nn, wl["mode"]
     d_b, d_o = nn.alloc(n * 32), nn.alloc(n * G.EVAL_SIZE)
@@ -234,6 +297,8 @@ def run_eval(c: Ctx, wl: dict, n: int, steps: int, warmup: int, max_plies: int, 
     out, boards = d_o.download(G.EVAL_DTYPE, n), d_b.download(G.BOARD_DTYPE, n)
     checksum = nn.checksum_device(d_o, n * G.EVAL_SIZE)
     d_b.free(), d_o.free()
+    if dump_dir and c.rank == 0:
+        dump_eval(out, dump_dir)
     pieces = popcounts(boards["occ"])
     alg = rows * (2 * wl["l1"] + 4) + n * 40
     k = 1 if mode == 2 else 2
@@ -251,8 +316,11 @@ def run_eval(c: Ctx, wl: dict, n: int, steps: int, warmup: int, max_plies: int, 
     return r
 
 
-def run_expand(c: Ctx, wl: dict, games: int, steps: int, warmup: int, check: int, gather: bool | None = None):
-    """Games x 81 parents, every legal child, incremental evaluation; verifies the timed outputs."""
+def run_expand(c: Ctx, wl: dict, games: int, steps: int, warmup: int, check: int, gather: bool | None = None,
+               lean: bool = False, dump_dir: str | None = None):
+    """Games x 81 parents, every legal child, incremental evaluation; verifies the timed outputs
+    (check > 0).  lean: nothing beyond the timed steps (no download of the parents, no checksums,
+    no result gather); dump_dir: rank 0 writes dump_expand's sample of the last timed step there."""
     G, nn, mode = c.G, c.nn, wl["mode"]
     n = games * (PLIES + 1)
     d_p = nn.alloc(n * 32)
@@ -280,9 +348,14 @@ def run_expand(c: Ctx, wl: dict, games: int, steps: int, warmup: int, check: int
     # timed region): the roofline's dominant kernel is stream_eval_kernel alone
     plan_ms, stream_ms = nn.get_option(G.STAT_PLAN_NS) / 1e6, nn.get_option(G.STAT_STREAM_NS) / 1e6
     finish_ms = nn.get_option(G.STAT_FINISH_NS) / 1e6  # the sliced stream's slice_finish_kernel
-    parents = d_p.download(G.BOARD_DTYPE, n)
-    sums = (nn.checksum_device(out["po"], n * G.EVAL_SIZE), nn.checksum_device(out["co"], children * G.EVAL_SIZE),
-            nn.checksum_device(out["mv"], children * 2), nn.checksum_device(out["off"], (n + 1) * 4))
+    if dump_dir and c.rank == 0:  # (before the plain-path check below reuses the output buffers)
+        dump_expand(c, out, n, children, dump_dir)
+    extras = bool(check) or not lean
+    parents, sums = None, None
+    if extras:
+        parents = d_p.download(G.BOARD_DTYPE, n)
+        sums = (nn.checksum_device(out["po"], n * G.EVAL_SIZE), nn.checksum_device(out["co"], children * G.EVAL_SIZE),
+                nn.checksum_device(out["mv"], children * 2), nn.checksum_device(out["off"], (n + 1) * 4))
     planned = stream_ms > 0
     # the column-sliced stream (GN_OPT_STREAM_SLICES 3): three launches per step, each over a
     # third of every row's columns; the roofline is per launch (= rocprofv3's per-dispatch view)
@@ -291,7 +364,7 @@ def run_expand(c: Ctx, wl: dict, games: int, steps: int, warmup: int, check: int
              kern_ms=(stream_ms / sl) if planned else stage[5 if mode != 2 else 4], plan_ms=plan_ms,
              finish_ms=finish_ms,
              alg=rows * (2 * wl["l1"] // sl + 4), rows=rows, parents=parents, n=n, launches=sl,
-             children=children, gen_s=gen_s, checksum=sums[0] ^ sums[1], scratch_pads=scratch_pads,
+             children=children, gen_s=gen_s, checksum=sums[0] ^ sums[1] if sums else None, scratch_pads=scratch_pads,
              kernel=(f"stream_eval_kernel<{wl['l1']}, 3> (3 column-slice launches per step)" if sl == 3 else
                      f"stream_eval_kernel<{wl['l1']}>") if wl["l1"] != 128 else f"expand_eval<{wl['l1']}>")
     if check:
@@ -337,7 +410,7 @@ def run_expand(c: Ctx, wl: dict, games: int, steps: int, warmup: int, check: int
                                 "checksum_plain": f"{ref[0] ^ ref[1]:016x}",
                                 "plain_path": "GN_OPT_CHAIN=1, GN_OPT_KING_CACHE=0 (refresh-started parents)"}
         r["oracle_check"] = ver
-    if c.world > 1 if gather is None else gather:  # (gather=True: also at N = 1, tests)
+    if (c.world > 1 and not lean) if gather is None else gather:  # (gather=True: also at N = 1, tests)
         r["gather"] = gather_results(c, out, n, children, games, mode, check)
     for b in ("po", "off", "mv", "co"):
         out[b].free()
@@ -809,12 +882,18 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="expand")
     ap.add_argument("--positions", type=int, default=0, help="positions (or games for expand) per GPU")
     ap.add_argument("--max-plies", type=int, default=160)
+    ap.add_argument("--full", action="store_true",
+                    help="also what `value` does not need: the checks of the timed outputs (--check), the CPU "
+                         "baseline, the result gather at N > 1, the checksums and the secondary results")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of the last step's outputs (rank 0's) "
+                         "as DIR/<name>.npy, float64, at most 64 MB in all")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondary results")
     ap.add_argument("--check", type=int, default=256,
-                    help="expand: parents (with children) of the timed outputs re-checked against the oracle, plus "
-                         "the plain-path checksum; eval: positions (x16, >= 4096)")
+                    help="with --full; expand: parents (with children) of the timed outputs re-checked against the "
+                         "oracle, plus the plain-path checksum; eval: positions (x16, >= 4096)")
     ap.add_argument("--swizzle", type=int, default=-1, help="GN_OPT_XCD_SWIZZLE mask (-1: library default)")
     ap.add_argument("--king-sort", type=int, default=-1, help="GN_OPT_KING_SORT (-1: library default)")
     ap.add_argument("--chain", type=int, default=None, help="GN_OPT_CHAIN (None: library default; -k: exactly k)")
@@ -848,9 +927,10 @@ def main():
     wl = WORKLOADS[args.workload]
     mode = wl["mode"]
     n = args.positions or wl["n"]
-    eval_check = max(4096, 16 * args.check) if args.check else 0
+    check = args.check if args.full else 0
+    eval_check = max(4096, 16 * check) if check else 0
     if args.workload == "expand":
-        r = run_expand(c, wl, n, args.steps, args.warmup, args.check)
+        r = run_expand(c, wl, n, args.steps, args.warmup, check, lean=not args.full, dump_dir=args.dump_outputs)
         cfg = {"workload": wl["config"], "games_per_gpu": n, "parents_per_gpu": r["n"],
                "children_per_gpu": r["children"], "evals_per_step_per_gpu": r["n"] + r["children"],
                "evals_per_step_all_gpus": c.world * (r["n"] + r["children"]), "plies": PLIES,
@@ -858,7 +938,7 @@ def main():
         stage_names = G.EXPAND_STAGES
         data = f"synthetic: seeded random 80-ply games generated on the GPU; nets {c.net_label}"
     else:
-        r = run_eval(c, wl, n, args.steps, args.warmup, args.max_plies, eval_check)
+        r = run_eval(c, wl, n, args.steps, args.warmup, args.max_plies, eval_check, dump_dir=args.dump_outputs)
         cfg = {"workload": wl["config"], "positions_per_gpu": n, "global_batch": n * c.world,
                "mean_pieces": round(float(r["pieces"].mean()), 3), "max_plies": args.max_plies,
                "ft_rows_per_step_per_gpu": r["rows"]}
@@ -891,9 +971,10 @@ def main():
             bad += r["gather"].get("oracle_check", {}).get("mismatching_parents", 0)
         line["oracle_check"] = chk
         line["rank_check_failures"] = c.comm.gather_i64(int(bad))
-    line["rank_checksums"] = [f"{x:016x}" for x in c.comm.gather_i64(int(r["checksum"]) & 0x7FFFFFFFFFFFFFFF)]
+    if r["checksum"] is not None:
+        line["rank_checksums"] = [f"{x:016x}" for x in c.comm.gather_i64(int(r["checksum"]) & 0x7FFFFFFFFFFFFFFF)]
 
-    if c.rank == 0 and not args.no_cpu_baseline:
+    if c.rank == 0 and args.full and not args.no_cpu_baseline:
         if args.workload == "expand":
             cb = cpu_baseline_expand(c, r["parents"][:1_000_000], mode, args.cpu_seconds)
         else:
@@ -906,14 +987,14 @@ def main():
                                    f"logical CPUs (not measured; an upper bound with SMT)"}
         line["cpu_baseline"] = cb
 
-    if not args.no_secondary and args.workload == "expand":
+    if args.full and not args.no_secondary and args.workload == "expand":
         sec = {}
         for name in ("big16m", "small1m"):
             w = WORKLOADS[name]
             # (the small net's launch is < 1 ms: 20 steps after 3 warmups, so that its first launches
             # after the big-net line, with the small table not yet in L2, do not dominate)
             st, wu = (20, 3) if name == "small1m" else (3, 1)
-            s = run_eval(c, w, w["n"], st, wu, args.max_plies, 4096 if args.check else 0)
+            s = run_eval(c, w, w["n"], st, wu, args.max_plies, 4096 if check else 0)
             rf = roofline(s["alg"], s["kern_ms"], s["kernel"], load_pmc(name, w["n"]))
             sec[name] = {"workload": w["config"], "value": round(s["value"], 1), "unit": "evals/s",
                          "kernel": s["kernel"], "kernel_ms": round(s["kern_ms"], 4), "ft_rows": s["rows"],
@@ -922,18 +1003,18 @@ def main():
             if "oracle_check" in s:
                 sec[name]["oracle_check"] = s["oracle_check"]
                 sec[name]["rank_check_failures"] = c.comm.gather_i64(s["oracle_check"]["mismatches"])
-        g2 = run_expand2(c, 2048, 1, 2, 256 if args.check else 0)
+        g2 = run_expand2(c, 2048, 1, 2, 256 if check else 0)
         if "oracle_check" in g2:
             g2["rank_check_failures"] = c.comm.gather_i64(g2["oracle_check"]["mismatching_children"])
         sec["grandchild"] = g2
-        ag = run_abi_games(c, WORKLOADS["expand"]["n"], 1, 2, 256 if args.check else 0)
+        ag = run_abi_games(c, WORKLOADS["expand"]["n"], 1, 2, 256 if check else 0)
         ag["frac_of_device_resident"] = round(ag["value"] / line["value"], 4)
         if "oracle_check" in ag:
             ck = ag["oracle_check"]
             ag["rank_check_failures"] = c.comm.gather_i64(ck["oracle"]["mismatching_positions"] +
                                                           ck["vs_device_resident"]["mismatching_games"])
         sec["abi_games"] = ag
-        dr = run_dropin(c, 1024, 16, 64, 32 if args.check else 0)
+        dr = run_dropin(c, 1024, 16, 64, 32 if check else 0)
         if "oracle_check" in dr:
             dr["rank_check_failures"] = c.comm.gather_i64(dr["oracle_check"]["mismatches"])
         sec["dropin"] = dr

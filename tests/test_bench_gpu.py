@@ -92,6 +92,58 @@ def test_run_expand_and_gather_two_loopback_ranks():
     assert r0["checksum"] != r1["checksum"]
 
 
+def test_plain_run_dumps_the_timed_outputs(tmp_path):
+    """bench.py --dump-outputs on the plain (lean) path: the sample written after the timed steps
+    is float64, consistent in itself (child counts sum to the child records, totals = the step's
+    counts), the same from run to run, and equal to the library's host-buffer expansion of the
+    same sampled parents (parent records; every child's move and psqt / positional / final_cp)."""
+    import bench
+    from fishnet_amd import gpu_nnue as G
+    args = argparse.Namespace(swizzle=-1, king_sort=-1, chain=None, king_cache=None)
+    c = bench.Ctx(args, comm=LoopbackComm(LoopbackHub(1), 0))
+    wl, games = bench.WORKLOADS["expand"], 48
+    n = games * (bench.PLIES + 1)
+    try:
+        dumps = []
+        for d in ("a", "b"):
+            r = bench.run_expand(c, wl, games, 2, 1, 0, lean=True, dump_dir=str(tmp_path / d))
+            assert r["checksum"] is None and r["parents"] is None and "oracle_check" not in r and "gather" not in r
+            names = sorted(p.name for p in (tmp_path / d).iterdir())
+            assert names == ["child_counts.npy", "child_evals.npy", "child_moves.npy", "parent_evals.npy",
+                             "parent_index.npy", "totals.npy"]
+            dumps.append({p[:-4]: np.load(tmp_path / d / p) for p in names})
+        a, b = dumps
+        assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+        assert all(np.array_equal(a[k], b[k]) for k in a)
+        assert a["totals"].tolist() == [n, r["children"]]
+        idx = a["parent_index"].astype(np.int64)
+        assert len(idx) == (n // bench.DUMP_RUN) * bench.DUMP_RUN and len(np.unique(idx)) == len(idx) and idx.max() < n
+        assert a["parent_evals"].shape == (len(idx), 7) and a["child_counts"].shape == (len(idx),)
+        total = int(a["child_counts"].sum())
+        assert a["child_evals"].shape == (total, 7) and a["child_moves"].shape == (total,)
+        # the same parents through gn_expand_and_evaluate (host buffers, no chain across parents)
+        d_p = c.nn.alloc(n * 32)
+        c.nn.random_games_device(bench.SEED, 0, games, bench.PLIES, d_p)
+        c.nn.synchronize()
+        boards = d_p.download(G.BOARD_DTYPE, n)
+        d_p.free()
+        sel = idx[:256]
+        parents, offs, moves, kids = c.nn.expand_and_evaluate([G.board_to_fen(boards[i]) for i in sel], wl["mode"])
+        assert np.array_equal(a["parent_evals"][:256], bench._fields64(parents))
+        assert np.array_equal(np.diff(offs), a["child_counts"][:256])
+        k = int(offs[-1])
+        for j in range(256):  # (children of one parent: the same set, in either order)
+            lo, hi = int(offs[j]), int(offs[j + 1])
+            got = sorted(zip(a["child_moves"][lo:hi].tolist(), map(tuple, a["child_evals"][lo:hi, [0, 1, 3]].tolist())))
+            exp = sorted(zip(moves[lo:hi].tolist(),
+                             zip(kids["psqt"][lo:hi].tolist(), kids["positional"][lo:hi].tolist(),
+                                 kids["final_cp"][lo:hi].tolist())))
+            assert got == exp, j
+        assert k == int(a["child_counts"][:256].sum())
+    finally:
+        c.nn.close()
+
+
 def test_evaluate_device_blocks_until_written(gpu_ctx):
     """gn_evaluate_device is documented as blocking (gpu_nnue.h: the score rule reads
     the in-check count back, so the call synchronises the stream it is given).  On a caller's

@@ -1,10 +1,10 @@
 #!/bin/bash
-# GPU parity tests + default bench line.  Usage: bash tools/gpu_check.sh <tag>
+# GPU parity tests + the full bench line (bench.py --full).  Usage: bash tools/gpu_check.sh <tag>
 TAG=${1:-chk}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $OUT/pytest.log 2>&1 || { tail -30 $OUT/pytest.log; exit 1; }
 tail -3 $OUT/pytest.log
-timeout -k 10 400 python -u bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Default bench line + rocprofv3 kernel-trace stats of the same command + PMC
+# Full bench line (--full) + rocprofv3 kernel-trace stats of the plain run + PMC
 # passes (one counter group per pass, each its own process) for the expand and
 # big16m workloads.  Usage: bash tools/profile_round.sh <tag>; then, locally,
 # python tools/pmc_summary.py <tag>.
@@ -7,7 +7,7 @@ TAG=${1:-r01}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- \
     python bench.py --no-cpu-baseline --no-secondary --check 0 > $OUT/trace.log 2>&1 || { tail -20 $OUT/trace.log; exit 1; }
