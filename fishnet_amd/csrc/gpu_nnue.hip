@@ -241,24 +241,29 @@ struct FastBatch {
 };
 
 // The buffers one expansion's front half (child generation, classify, small net, plan) writes and
-// its back half (row stream, finalize, score rule) reads: the expansion pipeline (expand_pipeline
+// its back half (row stream, finalize, score rule) reads: the expansion pipeline (run_expansions
 // below) runs expansion k + 1's front on the device's second stream while expansion k's back
-// runs, in the other set (swap_sets: the Dev's own fields are always the current set).
+// runs, in the other set (Dev::cur / Dev::alt, swap_sets).
 struct ExpSet {
   DevBuf<uint64_t> counts, offsets;
-  DevBuf<uint32_t> owner;
-  DevBuf<Board> unpacked;
-  DevBuf<uint16_t> moves_tmp;
-  const uint16_t *child_moves = nullptr;
-  DevBuf<int2> pinfo, p_osm, p_obg;
-  DevBuf<uint8_t> p_nsm, p_nbg;
-  EvalBufs eb;
-  DevBuf<gn_board> children;
-  int chain_k = 1, slices = 1;
-  bool planned = false;
-  uint64_t etot = 0;
+  DevBuf<uint32_t> owner;                // parent of each child (write_children scratch)
+  DevBuf<Board> unpacked;                // the parents unpacked once (write_children scratch)
+  DevBuf<uint16_t> moves_tmp;            // when the caller keeps no moves
+  const uint16_t *child_moves = nullptr; // the last generate_children's moves (finalize reads them)
+  DevBuf<int2> pinfo;                    // sliced stream: each position's (PSQT value, bucket) for the finish
+  DevBuf<int2> p_osm, p_obg;             // parent-side net outputs during expansion
+  DevBuf<uint8_t> p_nsm, p_nbg;          // parent-side net selection during expansion
+  EvalBufs eb;                           // the children's net outputs; evaluate_on's outputs
+  DevBuf<gn_board> children;             // library-internal child boards
+  int chain_k = 1;      // block length of this expansion (1: no chaining)
+  int slices = 1;       // this expansion's stream: column slices (3) or whole rows (1)
+  bool planned = false; // this expansion runs the planned kernels (stream.hip; perr is meaningful)
+  uint64_t etot = 0;    // eoff[n] of this expansion
   void *scan_tmp = nullptr, *sort_tmp = nullptr; // (the two streams' scans / sorts run at once)
   size_t scan_bytes = 0, sort_bytes = 0;
+  // recorded on the device stream behind this set's last score rule: a front that does not wait
+  // for the row stream (GN_OPT_EXPAND_PIPELINE 2) waits for it before it overwrites the set
+  hipEvent_t scored = nullptr;
   DevBuf<uint32_t> perr;            // the planned expansion's error word ...
   DevBuf<unsigned long long> pstat; // ... and pad count (each expansion of the pipeline its own)
   // the plan's output the row stream reads (GN_OPT_EXPAND_PIPELINE 2: the next plan runs beside
@@ -275,6 +280,8 @@ struct ExpSet {
     if (scan_tmp) (void)hipFree(scan_tmp);
     if (sort_tmp) (void)hipFree(sort_tmp);
     scan_tmp = sort_tmp = nullptr, scan_bytes = sort_bytes = 0;
+    if (scored) (void)hipEventDestroy(scored);
+    scored = nullptr;
   }
 };
 
@@ -285,45 +292,28 @@ struct Dev {
   NetDevice net[2] = {};
   bool has[2] = {false, false};
   Tables *tables = nullptr;
-  EvalBufs eb; // evaluate_on's outputs
-  DevBuf<int2> &osm = eb.osm, &obg = eb.obg;
-  DevBuf<uint8_t> &nsm = eb.nsm, &nbg = eb.nbg;
-  DevBuf<gn_board> io_boards, frontier[2];
+  // The current expansion's buffers (generate_children, expand_evaluate, resolve_scores and
+  // evaluate_on work in cur) and the other set, in which the pipeline's next front runs.  What an
+  // expansion's back half reads belongs in ExpSet.  Here stay only: what the front half that wrote
+  // it alone reads (deltas, nslot, ebound, bkeys*, bidx: the fronts run one after another on one
+  // stream), and what the back halves share because they run one after another (pool; part, which
+  // a front may not reallocate while a pipeline runs: part_locked).
+  ExpSet cur, alt;
+  DevBuf<gn_board> io_boards, frontier; // frontier: gn_perft's current level
   DevBuf<gn_eval> io_out, io_out2;
-  DevBuf<uint64_t> counts, offsets;
   DevBuf<uint32_t> off32;
-  DevBuf<uint16_t> moves, moves_tmp; // moves_tmp: when the caller keeps no moves
-  DevBuf<uint32_t> owner;             // parent of each child (write_children scratch)
-  DevBuf<Board> unpacked;             // the parents unpacked once (write_children scratch)
-  const uint16_t *child_moves = nullptr; // the last generate_children's moves (finalize reads them)
+  DevBuf<uint16_t> moves;
   DevBuf<ChildDelta> deltas;
   DevBuf<uint64_t> kkeys, kkeys2; // king-sort keys
   DevBuf<uint32_t> kidx, kperm;   // king-sort permutation
-  void *sort_tmp = nullptr;
-  size_t sort_bytes = 0;
-  DevBuf<int2> p_osm, p_obg;     // parent-side net outputs during expansion
-  DevBuf<uint8_t> p_nsm, p_nbg;  // parent-side net selection during expansion
   DevBuf<unsigned long long> sum;
   DevBuf<uint8_t> nslot; // chained walk: child of parent i that is parent i + 1 (255: none)
   DevBuf<int32_t> part;  // column-sliced stream: fc_0 partial sums of the 3 slices (3 x positions x 16)
-  DevBuf<int2> pinfo;    // ... and each position's (PSQT value, bucket) for the finish
-  int chain_k = 1;          // block length of the current expansion (1: no chaining)
-  int slices = 1;           // the current expansion's stream: column slices (3) or whole rows (1)
   bool part_locked = false; // a pipeline runs: part is in use by a back half (no reallocation)
-  // planned expansion (stream.hip): per-parent entry bounds and their scan, the entry
-  // lists, tile descriptors, the scratch-slot pool and the error word
-  DevBuf<uint64_t> ebound, eoff;
-  DevBuf<uint64_t> ent;           // the planned expansion's row entries (stream.hip)
-  DevBuf<uint32_t> pool, perr;
-  DevBuf<unsigned long long> pstat; // no-op entries the last planned expansion's plan inserted (GN_SCR_GAP)
-  DevBuf<TileDesc> tiles;
-  DevBuf<uint32_t> btiles; // tiles per block of the planned expansion
+  DevBuf<uint64_t> ebound;  // planned expansion (stream.hip): per-parent entry bounds
+  DevBuf<uint32_t> pool;    // ... and the scratch-slot pool
   DevBuf<uint16_t> bkeys, bkeys2; // block_order scratch
-  DevBuf<uint32_t> bidx, border;  // block_order: identity, then the order
-  uint64_t etot = 0;        // eoff[n] of the current expansion
-  bool planned = false;     // the last expansion runs the planned kernels (perr is meaningful)
-  void *scan_tmp = nullptr;
-  size_t scan_bytes = 0;
+  DevBuf<uint32_t> bidx;          // block_order: identity
   // Cross-stream ordering of the library-owned scratch above: every launch sequence
   // waits for the previous one when it runs on another stream (gn_*_device take a
   // caller stream and return while their kernels are still queued).
@@ -345,7 +335,7 @@ struct Dev {
       boards.release(), children.release(), moves.release(), ce.release(), sv.release();
     }
   } lv[2];
-  // the host-buffer calls' pipeline (expand_chunks): per chunk slot the parent / child
+  // the host-buffer calls' pipeline (expand_pipelined): per chunk slot the parent / child
   // records and child moves a drain thread downloads on the copy stream while the next chunk
   // computes; the lichess replay's inputs and outputs (replay_games_kernel)
   hipStream_t copy = nullptr;
@@ -364,9 +354,8 @@ struct Dev {
   // so that a second call's launch queues on the stream behind a first one in flight
   std::unique_ptr<FastBatch> fast[6][3][2];
   std::condition_variable fast_cv; // an instance's launch completed (its busy flag cleared; d.mu)
-  // the expansion pipeline: the other buffer set, the front's stream and its two events (the
-  // back's row stream done: the front may overwrite the plan's lists; the plan done)
-  ExpSet alt;
+  // the expansion pipeline: the front's stream and its two events (the back's row stream done:
+  // the front may overwrite the plan's lists; the plan done)
   hipStream_t front = nullptr;
   hipEvent_t ev_streamed = nullptr, ev_planned = nullptr;
   std::mutex mu;
@@ -374,22 +363,7 @@ struct Dev {
 
 // The Dev's current expansion buffers <-> its other set (host-side pointers only: launches already
 // queued keep the buffers they were given).
-static void swap_sets(Dev &d) {
-  ExpSet &x = d.alt;
-  std::swap(d.counts, x.counts), std::swap(d.offsets, x.offsets), std::swap(d.owner, x.owner);
-  std::swap(d.unpacked, x.unpacked), std::swap(d.moves_tmp, x.moves_tmp), std::swap(d.child_moves, x.child_moves);
-  std::swap(d.pinfo, x.pinfo), std::swap(d.p_osm, x.p_osm), std::swap(d.p_obg, x.p_obg);
-  std::swap(d.p_nsm, x.p_nsm), std::swap(d.p_nbg, x.p_nbg);
-  std::swap(d.eb.osm, x.eb.osm), std::swap(d.eb.obg, x.eb.obg), std::swap(d.eb.nsm, x.eb.nsm), std::swap(d.eb.nbg, x.eb.nbg);
-  std::swap(d.frontier[1], x.children);
-  std::swap(d.chain_k, x.chain_k), std::swap(d.slices, x.slices), std::swap(d.planned, x.planned);
-  std::swap(d.etot, x.etot);
-  std::swap(d.scan_tmp, x.scan_tmp), std::swap(d.scan_bytes, x.scan_bytes);
-  std::swap(d.sort_tmp, x.sort_tmp), std::swap(d.sort_bytes, x.sort_bytes);
-  std::swap(d.perr, x.perr), std::swap(d.pstat, x.pstat);
-  std::swap(d.ent, x.ent), std::swap(d.eoff, x.eoff), std::swap(d.tiles, x.tiles), std::swap(d.btiles, x.btiles);
-  std::swap(d.border, x.border);
-}
+static void swap_sets(Dev &d) { std::swap(d.cur, d.alt); }
 
 // Called under d.mu before a launch sequence on stream s / after it.
 static hipError_t seq_begin(Dev &d, hipStream_t s) {
@@ -404,9 +378,9 @@ static hipError_t seq_end(Dev &d, hipStream_t s) {
 // After a synchronised planned expansion: its device error word (entry overflow or no
 // scratch slot; neither can happen by construction, but a wrong result must not pass).
 static int check_plan(Dev &d, hipStream_t s) {
-  if (!d.planned || !d.perr.p) return GN_OK;
+  if (!d.cur.planned || !d.cur.perr.p) return GN_OK;
   uint32_t e = 0;
-  HIP_TRY(hipMemcpyAsync(&e, d.perr.p, sizeof(e), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&e, d.cur.perr.p, sizeof(e), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (e) return fail(GN_E_HIP, "planned expansion failed on the device (error bits 0x%x)", e);
   return GN_OK;
@@ -569,23 +543,17 @@ static void destroy(gn_ctx *ctx) {
     for (void *m : d.net_mem)
       if (m) (void)hipFree(m);
     if (d.tables) (void)hipFree(d.tables);
-    d.osm.release(), d.obg.release(), d.nsm.release(), d.nbg.release();
-    d.io_boards.release(), d.frontier[0].release(), d.frontier[1].release();
-    d.io_out.release(), d.io_out2.release(), d.counts.release(), d.offsets.release();
+    d.cur.release(), d.alt.release();
+    d.io_boards.release(), d.frontier.release(), d.io_out.release(), d.io_out2.release();
     d.off32.release(), d.moves.release(), d.sum.release(), d.deltas.release();
-    d.moves_tmp.release(), d.owner.release(), d.unpacked.release();
-    d.p_osm.release(), d.p_obg.release(), d.p_nsm.release(), d.p_nbg.release();
-    d.part.release(), d.pinfo.release(), d.alt.release();
+    d.part.release();
     if (d.front) (void)hipStreamSynchronize(d.front), (void)hipStreamDestroy(d.front);
     if (d.ev_streamed) (void)hipEventDestroy(d.ev_streamed);
     if (d.ev_planned) (void)hipEventDestroy(d.ev_planned);
-    if (d.scan_tmp) (void)hipFree(d.scan_tmp);
-    if (d.sort_tmp) (void)hipFree(d.sort_tmp);
     d.kkeys.release(), d.kkeys2.release(), d.kidx.release(), d.kperm.release();
     d.nslot.release();
-    d.ebound.release(), d.eoff.release(), d.ent.release(), d.pool.release(), d.perr.release(), d.tiles.release(), d.btiles.release();
-    d.pstat.release();
-    d.bkeys.release(), d.bkeys2.release(), d.bidx.release(), d.border.release();
+    d.ebound.release(), d.pool.release();
+    d.bkeys.release(), d.bkeys2.release(), d.bidx.release();
     d.lv[0].release(), d.lv[1].release();
     for (auto &row : d.fast)
       for (auto &pair : row)
@@ -657,10 +625,11 @@ static int create(const uint8_t *big, size_t big_len, const uint8_t *small, size
     }
 #endif
     HIP_TRY(hipMalloc(&d.tables, sizeof(Tables)));
-    HIP_TRY(d.perr.ensure(1)); // the planned expansion's error word and pad count (both sets)
-    HIP_TRY(d.pstat.ensure(1));
-    HIP_TRY(d.alt.perr.ensure(1));
-    HIP_TRY(d.alt.pstat.ensure(1));
+    for (ExpSet *x : {&d.cur, &d.alt}) { // the planned expansion's error word and pad count
+      HIP_TRY(x->perr.ensure(1));
+      HIP_TRY(x->pstat.ensure(1));
+      HIP_TRY(hipEventCreateWithFlags(&x->scored, hipEventDisableTiming));
+    }
     HIP_TRY(hipMemset(d.alt.perr.p, 0, sizeof(uint32_t)));
     HIP_TRY(hipMemcpy(d.tables, &host_tables(), sizeof(Tables), hipMemcpyHostToDevice));
     for (int w = 0; w < 2; ++w)
@@ -695,7 +664,7 @@ struct KernelTimes {
 // the stages [classify(+)] [small net (+reeval)] [big net] [finalize].
 // score: the records are positions (the score rule's static part; resolve_scores does the
 // in-check ones) rather than child records; counts (optional): their legal-move counts.
-// eb (optional): the net outputs and selections in these buffers instead of the device's (the
+// eb (optional): the net outputs and selections in these buffers instead of the current set's (the
 // drop-in's captured small-batch graphs own theirs, FastBatch); sort false: no king sort.
 static int evaluate_on(gn_ctx *ctx, Dev &d, const gn_board *b, size_t n, int mode, gn_eval *out, hipStream_t s,
                        hipEvent_t *ev, unsigned long long *rows_out = nullptr, int score = 1,
@@ -704,7 +673,7 @@ static int evaluate_on(gn_ctx *ctx, Dev &d, const gn_board *b, size_t n, int mod
   if ((mode != GN_MODE_SMALL && !d.has[BIG]) || (mode != GN_MODE_BIG && !d.has[SMALL]))
     return fail(GN_E_NONET, "mode %d needs a network that is not loaded", mode);
   if (!n) return GN_OK;
-  EvalBufs &B = eb ? *eb : d.eb;
+  EvalBufs &B = eb ? *eb : d.cur.eb;
   DevBuf<int2> &osm = B.osm, &obg = B.obg;
   DevBuf<uint8_t> &nsm = B.nsm, &nbg = B.nbg;
   if (mode != GN_MODE_BIG) HIP_TRY(osm.ensure(n));
@@ -726,8 +695,8 @@ static int evaluate_on(gn_ctx *ctx, Dev &d, const gn_board *b, size_t n, int mod
     HIP_TRY(d.kkeys2.ensure(n));
     HIP_TRY(d.kidx.ensure(n));
     HIP_TRY(d.kperm.ensure(n));
-    HIP_TRY(king_sort(b, n, d.kkeys.p, d.kidx.p, d.kkeys2.p, d.kperm.p, mode != GN_MODE_SMALL, d.sort_tmp,
-                      d.sort_bytes, s));
+    HIP_TRY(king_sort(b, n, d.kkeys.p, d.kidx.p, d.kkeys2.p, d.kperm.p, mode != GN_MODE_SMALL, d.cur.sort_tmp,
+                      d.cur.sort_bytes, s));
     perm = d.kperm.p;
   }
   const int swz = (ctx->swizzle >> 1) & 1;
@@ -767,10 +736,6 @@ static void parallel_for(size_t n, size_t grain, F &&f) {
   for (auto &t : th) t.join();
 }
 
-// Child generation: counts -> exclusive scan (d.offsets, n + 1) -> children
-// boards (+ moves, + ChildDelta when deltas is non-null).  *total = children.
-// ev (optional) gets 3 events: after count+scan, after the host read of the
-// total, after write_children.
 // Block length of the chained walk for an n-parent expansion: GN_OPT_CHAIN, shortened
 // (to >= 2) when the blocks would not fill the resident workgroups; 1 = off.
 static int chain_len(const gn_ctx *ctx, Dev &d, size_t n) {
@@ -800,220 +765,252 @@ static int finalize_all(gn_ctx *ctx, Dev &d, const gn_board *parents, const gn_b
                         gn_eval *parent_out, gn_eval *child_out, size_t n, size_t total, hipStream_t s,
                         bool score_parents, bool sliced = false) {
   const gn_eval_params &P = ctx->P;
-  const SlicedOut sc = {&d.net[BIG], d.part.p, d.pinfo.p, (uint64_t)(n + total), (uint64_t)n},
-                  sp = {&d.net[BIG], d.part.p, d.pinfo.p, (uint64_t)(n + total), 0};
+  const ExpSet &x = d.cur;
+  const SlicedOut sc = {&d.net[BIG], d.part.p, x.pinfo.p, (uint64_t)(n + total), (uint64_t)n},
+                  sp = {&d.net[BIG], d.part.p, x.pinfo.p, (uint64_t)(n + total), 0};
   // children from their parents as write_children unpacked them
-  const bool fast = d.child_moves != nullptr;
-  HIP_TRY(launch_finalize(children, total, mode, d.osm.p, d.obg.p, d.nsm.p, d.nbg.p, P, d.tables, child_out, s, 0,
-                          nullptr, fast ? d.owner.p : nullptr, fast ? d.child_moves : nullptr,
-                          fast ? d.unpacked.p : nullptr, sliced ? &sc : nullptr));
+  const bool fast = x.child_moves != nullptr;
+  HIP_TRY(launch_finalize(children, total, mode, x.eb.osm.p, x.eb.obg.p, x.eb.nsm.p, x.eb.nbg.p, P, d.tables, child_out,
+                          s, 0, nullptr, fast ? x.owner.p : nullptr, fast ? x.child_moves : nullptr,
+                          fast ? x.unpacked.p : nullptr, sliced ? &sc : nullptr));
   if (parent_out) // the parents' legal-move counts are generate_children's
-    HIP_TRY(launch_finalize(parents, n, mode, d.p_osm.p, d.p_obg.p, d.p_nsm.p, d.p_nbg.p, P, d.tables, parent_out, s,
-                            score_parents ? 1 : 0, d.counts.p, nullptr, nullptr, nullptr, sliced ? &sp : nullptr));
+    HIP_TRY(launch_finalize(parents, n, mode, x.p_osm.p, x.p_obg.p, x.p_nsm.p, x.p_nbg.p, P, d.tables, parent_out, s,
+                            score_parents ? 1 : 0, x.counts.p, nullptr, nullptr, nullptr, sliced ? &sp : nullptr));
   return GN_OK;
 }
 
 // Legal-child count of n boards (a capacity query), synchronously.
 static hipError_t count_children(Dev &d, const gn_board *parents, size_t n, hipStream_t s, size_t *total) {
+  ExpSet &x = d.cur;
   hipError_t e;
-  if ((e = d.counts.ensure(n + 1)) != hipSuccess || (e = d.offsets.ensure(n + 1)) != hipSuccess) return e;
-  if ((e = hipMemsetAsync(d.counts.p + n, 0, sizeof(uint64_t), s)) != hipSuccess) return e;
-  if ((e = launch_count_children(parents, n, d.tables, d.counts.p, s)) != hipSuccess) return e;
-  if ((e = exclusive_scan_u64(d.counts.p, d.offsets.p, n + 1, d.scan_tmp, d.scan_bytes, s)) != hipSuccess) return e;
+  if ((e = x.counts.ensure(n + 1)) != hipSuccess || (e = x.offsets.ensure(n + 1)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(x.counts.p + n, 0, sizeof(uint64_t), s)) != hipSuccess) return e;
+  if ((e = launch_count_children(parents, n, d.tables, x.counts.p, s)) != hipSuccess) return e;
+  if ((e = exclusive_scan_u64(x.counts.p, x.offsets.p, n + 1, x.scan_tmp, x.scan_bytes, s)) != hipSuccess) return e;
   uint64_t t = 0;
-  if ((e = hipMemcpyAsync(&t, d.offsets.p + n, sizeof(t), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(&t, x.offsets.p + n, sizeof(t), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
   *total = (size_t)t;
   return hipSuccess;
 }
 
-// skip_internal: the planned big-net path reads no child board after this (finalize makes each
-// child from its unpacked parent and move), so library-internal child boards are not written.
-static int generate_children(Dev &d, const gn_board *parents, size_t n, gn_board *children_or_null, size_t cap,
-                             uint16_t *moves, bool want_deltas, size_t *total, hipStream_t s, hipEvent_t *ev,
-                             unsigned long long *rows = nullptr, int chain_k = 1, bool plan = false,
-                             bool skip_internal = false) {
-  d.chain_k = want_deltas ? chain_k : 1;
-  d.planned = want_deltas && plan;
-  if (d.planned) { // a stale error bit of an earlier expansion must not fail this one
-    HIP_TRY(hipMemsetAsync(d.perr.p, 0, sizeof(uint32_t), s));
-    HIP_TRY(hipMemsetAsync(d.pstat.p, 0, sizeof(unsigned long long), s));
+// generate_children's optional arguments.
+struct GenOpts {
+  hipEvent_t *ev = nullptr; // 3 events: after count + scan, after the host read of the total, after write_children
+  unsigned long long *rows = nullptr; // += FT rows by write_children's formula
+  bool deltas = false;                // + each child's ChildDelta (the incremental evaluation's input)
+  int chain_k = 1;                    // with deltas: block length of the chained walk (chain_len)
+  bool plan = false;                  // with deltas: the big net runs planned (plan_path)
+  // the planned big-net path reads no child board after this (finalize makes each child from its
+  // unpacked parent and move), so library-internal child boards are not written
+  bool skip_internal = false;
+  size_t limit = SIZE_MAX; // more children than this fail the call (GN_E_CAPACITY) before anything is written
+};
+// Child generation into d.cur: counts -> exclusive scan (offsets, n + 1) -> children boards
+// (children_or_null, else the set's own) + moves (moves, else the set's own).  *total = children.
+static int generate_children(Dev &d, const gn_board *parents, size_t n, gn_board *children_or_null, uint16_t *moves,
+                             size_t *total, hipStream_t s, const GenOpts &o = {}) {
+  ExpSet &x = d.cur;
+  x.chain_k = o.deltas ? o.chain_k : 1;
+  x.planned = o.deltas && o.plan;
+  if (x.planned) { // a stale error bit of an earlier expansion must not fail this one
+    HIP_TRY(hipMemsetAsync(x.perr.p, 0, sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(x.pstat.p, 0, sizeof(unsigned long long), s));
   }
-  if (d.chain_k > 1) HIP_TRY(d.nslot.ensure(n));
-  HIP_TRY(d.counts.ensure(n + 1));
-  HIP_TRY(d.offsets.ensure(n + 1));
-  HIP_TRY(hipMemsetAsync(d.counts.p + n, 0, sizeof(uint64_t), s));
-  if (d.planned) {
+  if (x.chain_k > 1) HIP_TRY(d.nslot.ensure(n));
+  HIP_TRY(x.counts.ensure(n + 1));
+  HIP_TRY(x.offsets.ensure(n + 1));
+  HIP_TRY(hipMemsetAsync(x.counts.p + n, 0, sizeof(uint64_t), s));
+  if (x.planned) {
     HIP_TRY(d.ebound.ensure(n + 1));
-    HIP_TRY(d.eoff.ensure(n + 1));
+    HIP_TRY(x.eoff.ensure(n + 1));
     HIP_TRY(hipMemsetAsync(d.ebound.p + n, 0, sizeof(uint64_t), s));
   }
-  HIP_TRY(launch_count_children(parents, n, d.tables, d.counts.p, s, d.planned ? d.ebound.p : nullptr));
-  HIP_TRY(exclusive_scan_u64(d.counts.p, d.offsets.p, n + 1, d.scan_tmp, d.scan_bytes, s));
-  if (d.planned) HIP_TRY(exclusive_scan_u64(d.ebound.p, d.eoff.p, n + 1, d.scan_tmp, d.scan_bytes, s));
-  if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+  HIP_TRY(launch_count_children(parents, n, d.tables, x.counts.p, s, x.planned ? d.ebound.p : nullptr));
+  HIP_TRY(exclusive_scan_u64(x.counts.p, x.offsets.p, n + 1, x.scan_tmp, x.scan_bytes, s));
+  if (x.planned) HIP_TRY(exclusive_scan_u64(d.ebound.p, x.eoff.p, n + 1, x.scan_tmp, x.scan_bytes, s));
+  if (o.ev) HIP_TRY(hipEventRecord(o.ev[0], s));
   uint64_t t = 0;
-  HIP_TRY(hipMemcpyAsync(&t, d.offsets.p + n, sizeof(t), hipMemcpyDeviceToHost, s));
-  if (d.planned) HIP_TRY(hipMemcpyAsync(&d.etot, d.eoff.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&t, x.offsets.p + n, sizeof(t), hipMemcpyDeviceToHost, s));
+  if (x.planned) HIP_TRY(hipMemcpyAsync(&x.etot, x.eoff.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   *total = (size_t)t;
-  if (ev) HIP_TRY(hipEventRecord(ev[1], s));
-  if ((children_or_null || moves) && t > cap) // caller-owned child buffers hold cap entries
-    return fail(GN_E_CAPACITY, "%zu children exceed capacity %zu", (size_t)t, cap);
+  if (t > o.limit) return fail(GN_E_CAPACITY, "%zu children exceed capacity %zu", (size_t)t, o.limit);
+  if (o.ev) HIP_TRY(hipEventRecord(o.ev[1], s));
   gn_board *children = children_or_null;
-  const bool skip_boards = !children_or_null && d.planned && skip_internal;
+  const bool skip_boards = !children_or_null && x.planned && o.skip_internal;
   if (!children && !skip_boards) {
-    HIP_TRY(d.frontier[1].ensure(std::max<size_t>(t, 1)));
-    children = d.frontier[1].p;
+    HIP_TRY(x.children.ensure(std::max<size_t>(t, 1)));
+    children = x.children.p;
   }
-  if (want_deltas) HIP_TRY(d.deltas.ensure(std::max<size_t>(t, 1)));
-  HIP_TRY(d.owner.ensure(std::max<size_t>(t, 1)));
-  HIP_TRY(d.unpacked.ensure(std::max<size_t>(n, 1)));
+  if (o.deltas) HIP_TRY(d.deltas.ensure(std::max<size_t>(t, 1)));
+  HIP_TRY(x.owner.ensure(std::max<size_t>(t, 1)));
+  HIP_TRY(x.unpacked.ensure(std::max<size_t>(n, 1)));
   if (!moves) {
-    HIP_TRY(d.moves_tmp.ensure(std::max<size_t>(t, 1)));
-    moves = d.moves_tmp.p;
+    HIP_TRY(x.moves_tmp.ensure(std::max<size_t>(t, 1)));
+    moves = x.moves_tmp.p;
   }
-  d.child_moves = moves;
+  x.child_moves = moves;
   if (t) {
-    HIP_TRY(launch_write_children(parents, n, d.tables, d.offsets.p, 0, t, children, moves, d.owner.p,
-                                  want_deltas ? d.deltas.p : nullptr, d.chain_k > 1 ? d.nslot.p : nullptr, d.chain_k,
-                                  rows, s, d.unpacked.p));
+    HIP_TRY(launch_write_children(parents, n, d.tables, x.offsets.p, 0, t, children, moves, x.owner.p,
+                                  o.deltas ? d.deltas.p : nullptr, x.chain_k > 1 ? d.nslot.p : nullptr, x.chain_k,
+                                  o.rows, s, x.unpacked.p));
   }
-  if (ev) HIP_TRY(hipEventRecord(ev[2], s));
+  if (o.ev) HIP_TRY(hipEventRecord(o.ev[2], s));
   return GN_OK;
 }
 
-// Evaluate parents + children after generate_children.  Incremental: the
+// An expansion of n parents in mode whose children may number at most limit.
+static GenOpts gen_opts(const gn_ctx *ctx, Dev &d, size_t n, int mode, size_t limit) {
+  GenOpts g;
+  g.deltas = ctx->incremental, g.chain_k = chain_len(ctx, d, n), g.plan = plan_path(ctx, d, mode);
+  g.skip_internal = mode == GN_MODE_BIG, g.limit = limit;
+  return g;
+}
+
+// expand_evaluate's optional arguments.
+constexpr int EXP_FRONT = 1, EXP_BACK = 2;
+struct EvalOpts {
+  // [0] after classify, [1] after the small net (+ reeval), [2] after the big net, [3] after
+  // finalize, [4] the plan -> stream boundary, [6] after the stream launches, [7] (EXP_BACK alone)
+  // the stream's start
+  hipEvent_t *ev = nullptr;
+  unsigned long long *rows = nullptr; // += FT rows the row stream gathers
+  // the parents are positions (the score rule's static part; callers run resolve_scores on them)
+  // rather than child records (depth 2's level 2)
+  bool score_parents = true;
+  // EXP_FRONT (classify, the small net, the big net's plan) and / or EXP_BACK (the big net's row
+  // stream, finalize); the expansion pipeline runs the two on different streams
+  int phases = EXP_FRONT | EXP_BACK;
+  hipEvent_t streamed = nullptr; // recorded after the stream launches (the pipeline's next front waits for it)
+};
+// Evaluate parents + children after generate_children (in d.cur).  Incremental: the
 // expand_eval kernels (one workgroup per parent, children from the parent
 // accumulators); otherwise every child is a full refresh (evaluate_on).
-// ev (optional) gets 5 events: after classify, after the small net (+reeval),
-// after the big net, after finalize, and (planned path) between its plan and stream kernels.
-// score_parents: the parents are positions (the score rule's static part; callers run
-// resolve_scores on them) rather than child records (depth 2's level 2).
-// phases: EXP_FRONT (classify, the small net, the big net's plan) and / or EXP_BACK (the big net's
-// row stream, finalize); the expansion pipeline runs the two on different streams.  ev (optional):
-// [0] after classify, [1] after the small net, [2] after the big net, [3] after finalize, [4] the
-// plan -> stream boundary, [6] after the stream launches, [7] (EXP_BACK alone) the stream's start.
-// streamed (without ev): recorded after the stream launches (the pipeline's next front waits for it).
-constexpr int EXP_FRONT = 1, EXP_BACK = 2;
 static int expand_evaluate(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t n, const gn_board *children,
                            size_t total, int mode, gn_eval *parent_out, gn_eval *child_out, hipStream_t s,
-                           hipEvent_t *ev, unsigned long long *rows_out = nullptr, bool score_parents = true,
-                           int phases = EXP_FRONT | EXP_BACK, hipEvent_t streamed = nullptr) {
+                           const EvalOpts &o = {}) {
   if (mode < GN_MODE_FULL || mode > GN_MODE_SMALL) return fail(GN_E_INVALID, "bad mode %d", mode);
   if ((mode != GN_MODE_SMALL && !d.has[BIG]) || (mode != GN_MODE_BIG && !d.has[SMALL]))
     return fail(GN_E_NONET, "mode %d needs a network that is not loaded", mode);
+  ExpSet &x = d.cur;
+  hipEvent_t *const ev = o.ev;
+  const int phases = o.phases;
   if (!ctx->incremental) {
     if (!(phases & EXP_BACK)) return GN_OK; // (no front half: every child is a full refresh)
     if (total) {
       int rc = evaluate_on(ctx, d, children, total, mode, child_out, s, nullptr, nullptr, 0);
       if (rc) return rc;
     }
-    return parent_out ? evaluate_on(ctx, d, parents, n, mode, parent_out, s, nullptr, nullptr, score_parents ? 1 : 0,
-                                    d.counts.p)
+    return parent_out ? evaluate_on(ctx, d, parents, n, mode, parent_out, s, nullptr, nullptr, o.score_parents ? 1 : 0,
+                                    x.counts.p)
                       : GN_OK;
   }
   auto mark = [&](int k) -> hipError_t { return ev ? hipEventRecord(ev[k], s) : hipSuccess; };
   const gn_eval_params &P = ctx->P;
-  const uint64_t *off = d.offsets.p;
+  const uint64_t *off = x.offsets.p;
   const ChildDelta *dl = d.deltas.p;
   const bool f = mode == GN_MODE_FULL;
-  const size_t K = (size_t)std::max(1, d.chain_k), nblk = (n + K - 1) / K;
+  const size_t K = (size_t)std::max(1, x.chain_k), nblk = (n + K - 1) / K;
+  const bool ordered = ctx->king_sort && nblk > 1; // XCD-local block order
+  // the planned big net: the plan's launch and the row stream's take the same arguments
+  auto plan_args = [&] {
+    PlanStreamArgs a;
+    a.parents = parents, a.n = n, a.offsets = off, a.deltas = dl;
+    a.need_parent = f ? x.p_nbg.p : nullptr, a.need_child = f ? x.eb.nbg.p : nullptr;
+    a.out_parent = x.p_obg.p, a.out_child = x.eb.obg.p;
+    a.next_slot = x.chain_k > 1 ? d.nslot.p : nullptr, a.chain_k = x.chain_k, a.kc = ctx->king_cache ? 1 : 0;
+    a.eoff = x.eoff.p, a.ent = x.ent.p, a.tiles = x.tiles.p, a.btiles = x.btiles.p;
+    a.pool = d.pool.p, a.err = x.perr.p, a.rows_out = o.rows, a.pads_out = x.pstat.p;
+    a.slices = x.slices, a.npos = n + total;
+    if (x.slices > 1) a.part = d.part.p, a.pinfo = x.pinfo.p;
+    return a;
+  };
   // ---- the front half: selections, the small net, the plan (the stream's lists and tiles)
   if (phases & EXP_FRONT) {
     const size_t nt = std::max<size_t>(total, 1);
     if (mode != GN_MODE_BIG) {
-      HIP_TRY(d.osm.ensure(nt));
-      HIP_TRY(d.p_osm.ensure(n));
+      HIP_TRY(x.eb.osm.ensure(nt));
+      HIP_TRY(x.p_osm.ensure(n));
     }
     if (mode != GN_MODE_SMALL) {
-      HIP_TRY(d.obg.ensure(nt));
-      HIP_TRY(d.p_obg.ensure(n));
+      HIP_TRY(x.eb.obg.ensure(nt));
+      HIP_TRY(x.p_obg.ensure(n));
     }
     if (f) {
-      HIP_TRY(d.nsm.ensure(nt));
-      HIP_TRY(d.nbg.ensure(nt));
-      HIP_TRY(d.p_nsm.ensure(n));
-      HIP_TRY(d.p_nbg.ensure(n));
-      HIP_TRY(launch_classify(parents, n, P, d.p_nsm.p, d.p_nbg.p, s));
-      HIP_TRY(launch_classify(children, total, P, d.nsm.p, d.nbg.p, s));
+      HIP_TRY(x.eb.nsm.ensure(nt));
+      HIP_TRY(x.eb.nbg.ensure(nt));
+      HIP_TRY(x.p_nsm.ensure(n));
+      HIP_TRY(x.p_nbg.ensure(n));
+      HIP_TRY(launch_classify(parents, n, P, x.p_nsm.p, x.p_nbg.p, s));
+      HIP_TRY(launch_classify(children, total, P, x.eb.nsm.p, x.eb.nbg.p, s));
     }
     HIP_TRY(mark(0));
     if (mode != GN_MODE_BIG) {
-      HIP_TRY(launch_expand_net(d.net[SMALL], parents, n, off, children, dl, f ? d.p_nsm.p : nullptr,
-                                f ? d.nsm.p : nullptr, d.p_osm.p, d.osm.p, ctx->swizzle & 1, s));
+      HIP_TRY(launch_expand_net(d.net[SMALL], parents, n, off, children, dl, f ? x.p_nsm.p : nullptr,
+                                f ? x.eb.nsm.p : nullptr, x.p_osm.p, x.eb.osm.p, ctx->swizzle & 1, s));
       if (f) {
-        HIP_TRY(launch_reeval(d.p_osm.p, d.p_nsm.p, n, P, d.p_nbg.p, s));
-        HIP_TRY(launch_reeval(d.osm.p, d.nsm.p, total, P, d.nbg.p, s));
+        HIP_TRY(launch_reeval(x.p_osm.p, x.p_nsm.p, n, P, x.p_nbg.p, s));
+        HIP_TRY(launch_reeval(x.eb.osm.p, x.eb.nsm.p, total, P, x.eb.nbg.p, s));
       }
     }
     HIP_TRY(mark(1));
-    d.slices = 1;
-    if (mode != GN_MODE_SMALL && d.planned) {
-      HIP_TRY(d.ent.ensure(d.etot + (size_t)ENT_SPARE * (nblk + 1)));
-      HIP_TRY(d.tiles.ensure((n + total) / 16 + (K + 2) * nblk + 2));
-      HIP_TRY(d.btiles.ensure(nblk + 1));
+    x.slices = 1;
+    if (mode != GN_MODE_SMALL && x.planned) {
+      HIP_TRY(x.ent.ensure(x.etot + (size_t)ENT_SPARE * (nblk + 1)));
+      HIP_TRY(x.tiles.ensure((n + total) / 16 + (K + 2) * nblk + 2));
+      HIP_TRY(x.btiles.ensure(nblk + 1));
       HIP_TRY(d.pool.ensure(88)); // 8 XCDs x 8 words of scratch-slot bits, then 8 block claim counters
-      int slices = d.net[BIG].L1 == 3072 && ctx->stream_slices == 3 ? 3 : 1;
       // the sliced stream's partial sums cost 200 B per position (include/gpu_nnue.h,
       // GN_OPT_STREAM_SLICES); when they do not fit, the whole-row stream gives the same results
       // (part_locked: a pipelined front, beside the back half of the previous expansion that reads
       // part -- it may not reallocate it; when it is too small this expansion streams whole rows)
-      if (slices > 1) {
+      if (d.net[BIG].L1 == 3072 && ctx->stream_slices == 3) {
         const size_t need = (size_t)GN_PART_SLICES * 16 * (n + total);
         bool ok = d.part_locked ? d.part.cap >= need : d.part.ensure(need) == hipSuccess;
-        ok = ok && d.pinfo.ensure(n + total) == hipSuccess;
-        if (!ok) {
+        ok = ok && x.pinfo.ensure(n + total) == hipSuccess;
+        if (ok) x.slices = 3;
+        else {
           (void)hipGetLastError(); // (the failed allocation's error is not the call's)
           if (!d.part_locked) d.part.release();
-          d.pinfo.release();
-          slices = 1;
+          x.pinfo.release();
         }
       }
-      d.slices = slices;
-      // XCD-local block order
-      if (ctx->king_sort && nblk > 1) {
+      if (ordered) {
         HIP_TRY(d.bkeys.ensure(nblk));
         HIP_TRY(d.bkeys2.ensure(nblk));
         HIP_TRY(d.bidx.ensure(nblk));
-        HIP_TRY(d.border.ensure(nblk));
-        HIP_TRY(block_order(parents, n, (uint32_t)K, (uint32_t)nblk, d.bkeys.p, d.bidx.p, d.bkeys2.p, d.border.p,
-                            d.sort_tmp, d.sort_bytes, s));
+        HIP_TRY(x.border.ensure(nblk));
+        HIP_TRY(block_order(parents, n, (uint32_t)K, (uint32_t)nblk, d.bkeys.p, d.bidx.p, d.bkeys2.p, x.border.p,
+                            x.sort_tmp, x.sort_bytes, s));
       }
-      HIP_TRY(launch_plan_stream(d.net[BIG], parents, n, off, dl, f ? d.p_nbg.p : nullptr, f ? d.nbg.p : nullptr,
-                                 d.p_obg.p, d.obg.p, 0, d.chain_k > 1 ? d.nslot.p : nullptr, d.chain_k,
-                                 ctx->king_cache ? 1 : 0, d.eoff.p, d.ent.p, d.tiles.p, d.btiles.p, d.pool.p, d.perr.p,
-                                 rows_out, d.pstat.p, 0, nblk, nullptr, ev ? ev[4] : nullptr, s, slices,
-                                 slices > 1 ? d.part.p : nullptr, n + total, slices > 1 ? d.pinfo.p : nullptr,
-                                 nullptr, false, PLAN_PHASE));
+      PlanStreamArgs a = plan_args();
+      a.mid = ev ? ev[4] : nullptr;
+      HIP_TRY(launch_plan_stream(d.net[BIG], a, PLAN_PHASE, s));
     }
   }
   if (!(phases & EXP_BACK)) return GN_OK;
   // ---- the back half: the big net's row stream, finalize
   bool fused = false; // the sliced stream's finish runs inside finalize
   if (mode != GN_MODE_SMALL) {
-    if (d.planned) {
-      const int slices = d.slices;
-      const uint32_t *order = ctx->king_sort && nblk > 1 ? d.border.p : nullptr;
+    if (x.planned) {
       HIP_TRY(hipMemsetAsync(d.pool.p, 0, 88 * sizeof(uint32_t), s)); // per stream launch (<= 3)
 #ifndef GN_AB_FINISH_SEPARATE // A/B (round 4): slice_finish_kernel, then finalize
-      fused = slices > 1;
+      fused = x.slices > 1;
 #endif
       if (ev && (phases & EXP_FRONT) == 0) HIP_TRY(hipEventRecord(ev[7], s)); // (the pipeline: the stream's start)
-      HIP_TRY(launch_plan_stream(d.net[BIG], parents, n, off, dl, f ? d.p_nbg.p : nullptr, f ? d.nbg.p : nullptr,
-                                 d.p_obg.p, d.obg.p, (ctx->swizzle >> 2) & 1 ? 1 : (ctx->swizzle >> 3) & 1 ? 2 : 0,
-                                 d.chain_k > 1 ? d.nslot.p : nullptr, d.chain_k,
-                                 ctx->king_cache ? 1 : 0, d.eoff.p, d.ent.p, d.tiles.p, d.btiles.p, d.pool.p, d.perr.p,
-                                 rows_out, d.pstat.p, 0, nblk, order, nullptr, s, slices,
-                                 slices > 1 ? d.part.p : nullptr, n + total, slices > 1 ? d.pinfo.p : nullptr,
-                                 ev ? ev[6] : streamed, !fused, STREAM_PHASE));
+      PlanStreamArgs a = plan_args();
+      a.swz = (ctx->swizzle >> 2) & 1 ? 1 : (ctx->swizzle >> 3) & 1 ? 2 : 0;
+      a.order = ordered ? x.border.p : nullptr;
+      a.fin = ev ? ev[6] : nullptr, a.streamed = o.streamed, a.finish = !fused;
+      HIP_TRY(launch_plan_stream(d.net[BIG], a, STREAM_PHASE, s));
     } else { // a 128-wide net loaded as the big net
-      HIP_TRY(launch_expand_net(d.net[BIG], parents, n, off, children, dl, f ? d.p_nbg.p : nullptr,
-                                f ? d.nbg.p : nullptr, d.p_obg.p, d.obg.p, ctx->swizzle & 1, s));
+      HIP_TRY(launch_expand_net(d.net[BIG], parents, n, off, children, dl, f ? x.p_nbg.p : nullptr,
+                                f ? x.eb.nbg.p : nullptr, x.p_obg.p, x.eb.obg.p, ctx->swizzle & 1, s));
     }
   }
   HIP_TRY(mark(2));
-  int rc = finalize_all(ctx, d, parents, children, mode, parent_out, child_out, n, total, s, score_parents, fused);
+  int rc = finalize_all(ctx, d, parents, children, mode, parent_out, child_out, n, total, s, o.score_parents, fused);
   if (rc) return rc;
   HIP_TRY(mark(3));
   return GN_OK;
@@ -1031,8 +1028,8 @@ static int expand_evaluate(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t 
 // always prints a score from its search; fishnet requires one for every analysed
 // position (/root/reference/src/stockfish.rs:366-368, src/ipc.rs:56).
 // replies (optional, an expansion's parents): every position's legal replies are already
-// evaluated (child records / moves at d.offsets, the parents unpacked in d.unpacked); they are
-// reused instead of generated and evaluated again.
+// evaluated (child records / moves at d.cur.offsets, the parents unpacked in d.cur.unpacked); they
+// are reused instead of generated and evaluated again.
 struct Replies {
   const gn_eval *rec;
   const uint16_t *moves;
@@ -1044,7 +1041,7 @@ static int resolve_scores(gn_ctx *ctx, Dev &d, const gn_board *boards, size_t n,
   HIP_TRY(L.sel.ensure(n + 1));
   HIP_TRY(L.pos.ensure(n + 1));
   HIP_TRY(launch_score_select(out, n, L.sel.p, s));
-  HIP_TRY(exclusive_scan_u64(L.sel.p, L.pos.p, n + 1, d.scan_tmp, d.scan_bytes, s));
+  HIP_TRY(exclusive_scan_u64(L.sel.p, L.pos.p, n + 1, d.cur.scan_tmp, d.cur.scan_bytes, s));
   uint64_t m = 0;
   HIP_TRY(hipMemcpyAsync(&m, L.pos.p + n, sizeof(m), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1056,13 +1053,14 @@ static int resolve_scores(gn_ctx *ctx, Dev &d, const gn_board *boards, size_t n,
   HIP_TRY(launch_score_gather(boards, L.sel.p, L.pos.p, n, L.idx.p, L.boards.p, s));
   if (replies) {
     uint64_t t = 0;
-    HIP_TRY(launch_score_replies(L.idx.p, m, d.offsets.p, L.counts.p, L.offsets.p, d.scan_tmp, d.scan_bytes, &t, s));
+    HIP_TRY(launch_score_replies(L.idx.p, m, d.cur.offsets.p, L.counts.p, L.offsets.p, d.cur.scan_tmp,
+                                 d.cur.scan_bytes, &t, s));
     HIP_TRY(L.moves.ensure(std::max<uint64_t>(t, 1)));
     HIP_TRY(L.children.ensure(std::max<uint64_t>(t, 1)));
     HIP_TRY(L.ce.ensure(std::max<uint64_t>(t, 1)));
     HIP_TRY(L.sv.ensure(std::max<uint64_t>(t, 1)));
-    HIP_TRY(launch_score_replies_fill(L.idx.p, m, d.offsets.p, L.offsets.p, replies->rec, replies->moves, d.unpacked.p,
-                                      d.tables, L.ce.p, L.children.p, L.moves.p, s));
+    HIP_TRY(launch_score_replies_fill(L.idx.p, m, d.cur.offsets.p, L.offsets.p, replies->rec, replies->moves,
+                                      d.cur.unpacked.p, d.tables, L.ce.p, L.children.p, L.moves.p, s));
     int rc = resolve_scores(ctx, d, L.children.p, t, mode, L.ce.p, L.sv.p, s, depth - 1);
     if (rc) return rc;
     HIP_TRY(launch_score_reduce(L.boards.p, m, L.idx.p, L.offsets.p, L.moves.p, L.ce.p, L.sv.p, ctx->P, out, sv_out,
@@ -1071,7 +1069,7 @@ static int resolve_scores(gn_ctx *ctx, Dev &d, const gn_board *boards, size_t n,
   }
   HIP_TRY(hipMemsetAsync(L.counts.p + m, 0, sizeof(uint64_t), s));
   HIP_TRY(launch_count_children(L.boards.p, m, d.tables, L.counts.p, s));
-  HIP_TRY(exclusive_scan_u64(L.counts.p, L.offsets.p, m + 1, d.scan_tmp, d.scan_bytes, s));
+  HIP_TRY(exclusive_scan_u64(L.counts.p, L.offsets.p, m + 1, d.cur.scan_tmp, d.cur.scan_bytes, s));
   uint64_t t = 0;
   HIP_TRY(hipMemcpyAsync(&t, L.offsets.p + m, sizeof(t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1483,8 +1481,122 @@ static int count_shard(Dev &d, const gn_board *d_par, size_t m, std::vector<uint
   size_t total = 0;
   HIP_TRY(count_children(d, d_par, m, d.stream, &total));
   off.resize(m + 1);
-  HIP_TRY(hipMemcpy(off.data(), d.offsets.p, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(off.data(), d.cur.offsets.p, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return GN_OK;
+}
+
+// ---- a sequence of expansions (the host-buffer calls' chunks, gn_time_expand_device's iterations)
+// One expansion of the sequence, as its caller describes it.
+struct ExpStep {
+  const gn_board *parents = nullptr;
+  size_t n = 0;
+  gn_eval *parent_out = nullptr, *child_out = nullptr; // (NULL: the device's io_out / io_out2)
+  uint16_t *moves = nullptr; // the children's moves (NULL: the buffer set's own)
+  size_t cap = SIZE_MAX;     // more children than this fail the call (GN_E_CAPACITY)
+  // 12 stage events (optional): [0] the start, [1..3] generate_children's, [4..11] expand_evaluate's
+  hipEvent_t *ev = nullptr;
+  // 2 row counters (optional): [0] += rows by write_children's formula, when no planned row stream
+  // counts them (a per-wave atomic over every child would sit in a timed region), [1] += rows the
+  // row stream gathered
+  unsigned long long *rows = nullptr;
+};
+// GN_OPT_EXPAND_PIPELINE: expansion i + 1's front half (children, classify, small net, plan) runs
+// on the device's second stream, in the other buffer set, while expansion i's back half runs.
+static bool pipelined(const gn_ctx *ctx, const Dev &d, int mode, size_t count) {
+  return ctx->pipeline && plan_path(ctx, d, mode) && ctx->incremental && count > 1;
+}
+// Expansions 0 .. count - 1 on d (d.mu held, inside a sequence on d.stream), serial or pipelined.
+// step(i, ExpStep &) describes expansion i just before its front half is queued; done(i, total)
+// runs after its score rule is queued on d.stream, d.cur being expansion i's set (it stays the
+// last expansion's on return; pipelined, d.alt is then the one before's).  largest (optional):
+// parents + children of the largest step, for which the sliced stream's partial sums are sized
+// before any front runs (otherwise step 0's front sizes them): a later front runs beside a back
+// half that reads them and may not reallocate them (part_locked).
+template <class Step, class Done>
+static int run_expansions(gn_ctx *ctx, Dev &d, int mode, size_t count, size_t largest, Step &&step, Done &&done) {
+  if (!count) return GN_OK;
+  const hipStream_t s = d.stream;
+  const bool pipe = pipelined(ctx, d, mode, count);
+  const hipStream_t F = pipe ? d.front : s; // the front halves' stream
+  struct Guard { // on every way out: nothing of a failed call's front may still run
+    Dev &d;
+    bool pipe, ok = false;
+    ~Guard() {
+      d.part_locked = false;
+      if (pipe && !ok) (void)hipStreamSynchronize(d.front);
+    }
+  } guard{d, pipe};
+  struct Queued { // expansion i, from its front to its done, in q[i & 1]
+    ExpStep st;
+    size_t total = 0;
+    gn_eval *po = nullptr, *co = nullptr;
+  } q[2];
+  auto front = [&](size_t i) -> int { // into d.cur
+    Queued &x = q[i & 1];
+    x = Queued();
+    int rc = step(i, x.st);
+    if (rc) return rc;
+    const ExpStep &st = x.st;
+    if (st.ev) HIP_TRY(hipEventRecord(st.ev[0], F));
+    GenOpts g = gen_opts(ctx, d, st.n, mode, st.cap);
+    g.ev = st.ev ? st.ev + 1 : nullptr, g.rows = g.plan ? nullptr : st.rows;
+    if ((rc = generate_children(d, st.parents, st.n, nullptr, st.moves, &x.total, F, g)) != GN_OK) return rc;
+    if (!st.parent_out) HIP_TRY(d.io_out.ensure(st.n));
+    if (!st.child_out) HIP_TRY(d.io_out2.ensure(std::max<size_t>(x.total, 1)));
+    x.po = st.parent_out ? st.parent_out : d.io_out.p, x.co = st.child_out ? st.child_out : d.io_out2.p;
+    if (!pipe) return GN_OK; // (serial: the back half evaluates both phases)
+    EvalOpts e;
+    e.ev = st.ev ? st.ev + 4 : nullptr, e.rows = st.rows ? st.rows + 1 : nullptr, e.phases = EXP_FRONT;
+    rc = expand_evaluate(ctx, d, st.parents, st.n, d.cur.children.p, x.total, mode, nullptr, nullptr, F, e);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(d.ev_planned, F));
+    return GN_OK;
+  };
+  // the next front overwrites the other set: after this row stream, which reads the plan's lists
+  // there (GN_OPT_EXPAND_PIPELINE 1), or beside it (2: the lists are per set), after the score
+  // rule of the expansion that last used that set
+  auto next_front = [&](size_t i) -> int {
+    swap_sets(d);
+    int rc = GN_OK;
+    if (hipStreamWaitEvent(F, ctx->pipeline == 2 ? d.cur.scored : d.ev_streamed, 0) != hipSuccess)
+      rc = fail(GN_E_HIP, "hipStreamWaitEvent failed");
+    if (!rc) rc = front(i);
+    swap_sets(d);
+    return rc;
+  };
+  if (pipe) {
+    HIP_TRY(hipEventRecord(d.ev_streamed, s)); // the front starts after what the device stream holds
+    HIP_TRY(hipStreamWaitEvent(F, d.ev_streamed, 0));
+    if (largest) {
+      if (d.has[BIG] && d.net[BIG].L1 == 3072 && ctx->stream_slices == 3 &&
+          d.part.ensure((size_t)GN_PART_SLICES * 16 * largest) != hipSuccess)
+        (void)hipGetLastError(); // (then the steps that do not fit stream whole rows)
+      d.part_locked = true;
+    }
+  }
+  int rc = front(0);
+  d.part_locked = pipe;
+  for (size_t i = 0; i < count && rc == GN_OK; ++i) {
+    const Queued &x = q[i & 1];
+    const bool more = i + 1 < count;
+    EvalOpts e; // d.cur's row stream and finalize
+    e.ev = x.st.ev ? x.st.ev + 4 : nullptr, e.rows = x.st.rows ? x.st.rows + 1 : nullptr;
+    if (pipe) {
+      HIP_TRY(hipStreamWaitEvent(s, d.ev_planned, 0));
+      e.phases = EXP_BACK, e.streamed = d.ev_streamed;
+    }
+    rc = expand_evaluate(ctx, d, x.st.parents, x.st.n, d.cur.children.p, x.total, mode, x.po, x.co, s, e);
+    if (rc || (pipe && more && (rc = next_front(i + 1)) != GN_OK)) return rc;
+    const Replies rp{x.co, d.cur.child_moves}; // the replies this expansion evaluated
+    if ((rc = resolve_scores(ctx, d, x.st.parents, x.st.n, mode, x.po, nullptr, s, 2, &rp)) != GN_OK) return rc;
+    if (pipe) HIP_TRY(hipEventRecord(d.cur.scored, s));
+    rc = done(i, x.total);
+    if (rc || !more) break;
+    if (pipe) swap_sets(d);
+    else rc = front(i + 1);
+  }
+  guard.ok = rc == GN_OK;
+  return rc;
 }
 
 // Pass 2 of a shard (see above).  off: the shard's child offsets from pass 1; results to
@@ -1524,7 +1636,6 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
     g_err = derr[k];
     return r;
   };
-  int rc = GN_OK;
   auto drain_chunk = [&](int k, size_t pa, size_t mp, size_t t, uint64_t cb) {
     drain[k] = std::thread([&, k, pa, mp, t, cb] {
       const auto t1 = Clock::now();
@@ -1541,102 +1652,34 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
       dms[k] = ms_since(t1);
     });
   };
-  // GN_OPT_EXPAND_PIPELINE: chunk c + 1's child generation and plan run on the second stream (in
-  // the other buffer set) while chunk c's finalize and score rule run
-  const bool pipe = ctx->pipeline && plan_path(ctx, d, mode) && ctx->incremental && chunks.size() > 2;
-  if (pipe) {
-    hipStream_t B = d.front;
-    auto front = [&](size_t c) -> int {
-      const int k = (int)(c & 1);
-      const size_t pa = chunks[c], mp = chunks[c + 1] - pa;
-      const uint64_t tc = off[chunks[c + 1]] - off[pa];
-      size_t t = 0;
-      int r = generate_children(d, d_par + pa, mp, nullptr, d.mv2[k].cap, d.mv2[k].p, true, &t, B, nullptr, nullptr,
-                                chain_len(ctx, d, mp), true, mode == GN_MODE_BIG);
-      if (!r && t != tc) r = fail(GN_E_HIP, "child count changed between passes (%zu != %zu)", t, (size_t)tc);
-      if (!r)
-        r = expand_evaluate(ctx, d, d_par + pa, mp, d.frontier[1].p, t, mode, nullptr, nullptr, B, nullptr, nullptr,
-                            true, EXP_FRONT);
-      if (!r && hipEventRecord(d.ev_planned, B) != hipSuccess) r = fail(GN_E_HIP, "hipEventRecord failed");
-      return r;
-    };
-    // the front starts after what the device stream holds (the parents' upload / replay)
-    if (hipEventRecord(d.ev_streamed, s) != hipSuccess || hipStreamWaitEvent(B, d.ev_streamed, 0) != hipSuccess)
-      return fail(GN_E_HIP, "hipStreamWaitEvent failed");
-    // the partial sums sized for the largest chunk now: a later front runs beside a back half that
-    // reads them and may not reallocate them (part_locked)
-    if (d.has[BIG] && d.net[BIG].L1 == 3072 && ctx->stream_slices == 3 &&
-        d.part.ensure((size_t)GN_PART_SLICES * 16 * (maxp + maxc)) != hipSuccess)
-      (void)hipGetLastError(); // (then the chunks that do not fit stream whole rows)
-    d.part_locked = true;
-    struct Unlock {
-      Dev &d;
-      ~Unlock() { d.part_locked = false; }
-    } unlock{d};
-    rc = front(0);
-    for (size_t c = 0; c + 1 < chunks.size() && rc == GN_OK; ++c) {
-      const int k = (int)(c & 1);
-      const size_t pa = chunks[c], mp = chunks[c + 1] - pa;
-      const uint64_t cb = off[pa], t = off[chunks[c + 1]] - cb;
-      const auto t0 = Clock::now();
-      if (hipStreamWaitEvent(s, d.ev_planned, 0) != hipSuccess) {
-        rc = fail(GN_E_HIP, "hipStreamWaitEvent failed");
-        break;
-      }
-      rc = expand_evaluate(ctx, d, d_par + pa, mp, d.frontier[1].p, t, mode, d.po2[k].p, d.co2[k].p, s, nullptr,
-                           nullptr, true, EXP_BACK, d.ev_streamed);
-      if (rc) break;
-      const bool more = c + 2 < chunks.size();
-      if (more) { // the next chunk's front (slot k ^ 1: its previous chunk downloaded first)
-        if ((rc = join(k ^ 1)) != GN_OK) break;
-        swap_sets(d);
-        if (ctx->pipeline != 2 && hipStreamWaitEvent(B, d.ev_streamed, 0) != hipSuccess)
-          rc = fail(GN_E_HIP, "hipStreamWaitEvent failed");
-        if (!rc) rc = front(c + 1);
-        swap_sets(d);
-        if (rc) break;
-      }
-      const Replies rp{d.co2[k].p, d.mv2[k].p};
-      rc = resolve_scores(ctx, d, d_par + pa, mp, mode, d.po2[k].p, nullptr, s, 2, &rp);
-      if (!rc && launch_pack_children(d.co2[k].p, t, d.cc2[k].p, s) != hipSuccess)
-        rc = fail(GN_E_HIP, "child record packing failed");
-      if (!rc) rc = check_plan(d, s); // synchronises the stream: chunk c is computed
-      if (rc) break;
-      d.t_compute += ms_since(t0);
-      if (hipEventRecord(d.cev[k], s) != hipSuccess) {
-        rc = fail(GN_E_HIP, "hipEventRecord failed");
-        break;
-      }
-      drain_chunk(k, pa, mp, t, cb);
-      if (more) swap_sets(d);
-    }
-    if (rc) (void)hipStreamSynchronize(B); // (nothing of a failed call's front may still run)
-  }
-  for (size_t c = 0; !pipe && c + 1 < chunks.size() && rc == GN_OK; ++c) {
-    const int k = (int)(c & 1);
-    if ((rc = join(k)) != GN_OK) break; // the slot's previous chunk is downloaded
-    const size_t pa = chunks[c], mp = chunks[c + 1] - pa;
-    const uint64_t cb = off[pa], tc = off[chunks[c + 1]] - cb;
-    const auto t0 = Clock::now();
-    size_t t = 0;
-    rc = generate_children(d, d_par + pa, mp, nullptr, d.mv2[k].cap, d.mv2[k].p, ctx->incremental, &t, s, nullptr,
-                           nullptr, chain_len(ctx, d, mp), plan_path(ctx, d, mode), mode == GN_MODE_BIG);
-    if (!rc && t != tc) rc = fail(GN_E_HIP, "child count changed between passes (%zu != %zu)", t, (size_t)tc);
-    if (!rc)
-      rc = expand_evaluate(ctx, d, d_par + pa, mp, d.frontier[1].p, t, mode, d.po2[k].p, d.co2[k].p, s, nullptr);
-    const Replies rp{d.co2[k].p, d.mv2[k].p};
-    if (!rc) rc = resolve_scores(ctx, d, d_par + pa, mp, mode, d.po2[k].p, nullptr, s, 2, &rp);
-    if (!rc && launch_pack_children(d.co2[k].p, t, d.cc2[k].p, s) != hipSuccess)
-      rc = fail(GN_E_HIP, "child record packing failed");
-    if (!rc) rc = check_plan(d, s); // synchronises the stream: chunk c is computed
-    if (rc) break;
-    d.t_compute += ms_since(t0);
-    if (hipEventRecord(d.cev[k], s) != hipSuccess) {
-      rc = fail(GN_E_HIP, "hipEventRecord failed");
-      break;
-    }
-    drain_chunk(k, pa, mp, t, cb);
-  }
+  // chunk c computes into slot c & 1, which a drain thread then downloads on the copy stream while
+  // the next chunk computes (t_compute: from one chunk's completion to the next's, less the waits
+  // for a slot's download)
+  auto t0 = Clock::now();
+  int rc = run_expansions(
+      ctx, d, mode, chunks.size() - 1, maxp + maxc,
+      [&](size_t c, ExpStep &st) -> int {
+        const int k = (int)(c & 1);
+        const auto tj = Clock::now();
+        const int r = join(k); // the slot's previous chunk is downloaded
+        t0 += Clock::now() - tj;
+        st.parents = d_par + chunks[c], st.n = chunks[c + 1] - chunks[c];
+        st.parent_out = d.po2[k].p, st.child_out = d.co2[k].p, st.moves = d.mv2[k].p, st.cap = d.mv2[k].cap;
+        return r;
+      },
+      [&](size_t c, size_t t) -> int {
+        const int k = (int)(c & 1);
+        const size_t pa = chunks[c], mp = chunks[c + 1] - pa;
+        const uint64_t cb = off[pa], tc = off[chunks[c + 1]] - cb;
+        if (t != tc) return fail(GN_E_HIP, "child count changed between passes (%zu != %zu)", t, (size_t)tc);
+        HIP_TRY(launch_pack_children(d.co2[k].p, t, d.cc2[k].p, s));
+        int r = check_plan(d, s); // synchronises the stream: chunk c is computed
+        if (r) return r;
+        d.t_compute += ms_since(t0), t0 = Clock::now();
+        HIP_TRY(hipEventRecord(d.cev[k], s));
+        drain_chunk(k, pa, mp, t, cb);
+        return GN_OK;
+      });
   const auto tt = Clock::now();
   for (int k = 0; k < 2; ++k) {
     const int r = join(k);
@@ -2486,16 +2529,15 @@ int gn_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, si
   if (!n) return GN_OK;
   if (!d_children || !d_moves || !d_child_out) return fail(GN_E_INVALID, "NULL child buffer");
   size_t t = 0;
-  int rc = generate_children(*d, d_parents, n, d_children, cap, d_moves, ctx->incremental, &t, s, nullptr, nullptr,
-                             chain_len(ctx, *d, n), plan_path(ctx, *d, mode), mode == GN_MODE_BIG);
+  int rc = generate_children(*d, d_parents, n, d_children, d_moves, &t, s, gen_opts(ctx, *d, n, mode, cap));
   *total = t;
   if (t > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "%zu children exceed 32-bit offsets", t);
-  HIP_TRY(launch_offsets_u32(d->offsets.p, n + 1, d_offsets, s));
+  HIP_TRY(launch_offsets_u32(d->cur.offsets.p, n + 1, d_offsets, s));
   if (rc) {
     HIP_TRY(hipStreamSynchronize(s));
     return rc;
   }
-  rc = expand_evaluate(ctx, *d, d_parents, n, d_children, t, mode, d_parent_out, d_child_out, s, nullptr);
+  rc = expand_evaluate(ctx, *d, d_parents, n, d_children, t, mode, d_parent_out, d_child_out, s);
   const Replies rp{d_child_out, d_moves}; // the replies this expansion evaluated
   if (!rc) rc = resolve_scores(ctx, *d, d_parents, n, mode, d_parent_out, nullptr, s, 2, &rp);
   if (rc) return rc;
@@ -2532,16 +2574,15 @@ int gn_expand2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, s
     return t ? fail(GN_E_CAPACITY, "%zu children exceed capacity %zu", t, cap) : GN_OK;
   }
   // level 1
-  int rc = generate_children(*d, d_parents, n, d_children, cap, d_moves, ctx->incremental, &t, s, nullptr, nullptr,
-                             chain_len(ctx, *d, n), plan_path(ctx, *d, mode), mode == GN_MODE_BIG);
+  int rc = generate_children(*d, d_parents, n, d_children, d_moves, &t, s, gen_opts(ctx, *d, n, mode, cap));
   *total = t;
   if (t > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "%zu children exceed 32-bit offsets", t);
-  HIP_TRY(launch_offsets_u32(d->offsets.p, n + 1, d_offsets, s));
+  HIP_TRY(launch_offsets_u32(d->cur.offsets.p, n + 1, d_offsets, s));
   if (rc) {
     HIP_TRY(hipStreamSynchronize(s));
     return rc;
   }
-  rc = expand_evaluate(ctx, *d, d_parents, n, d_children, t, mode, d_parent_out, d_child_out, s, nullptr);
+  rc = expand_evaluate(ctx, *d, d_parents, n, d_children, t, mode, d_parent_out, d_child_out, s);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(s));
   if ((rc = check_plan(*d, s)) != GN_OK) return rc;
@@ -2559,19 +2600,19 @@ int gn_expand2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, s
     *gtotal = g;
     return g ? fail(GN_E_CAPACITY, "%zu grandchildren exceed capacity %zu", g, gcap) : GN_OK;
   }
-  rc = generate_children(*d, d_children, t, nullptr, gcap, d_gmoves, ctx->incremental, &g, s, nullptr, nullptr,
-                         chain_len(ctx, *d, t), plan_path(ctx, *d, mode), mode == GN_MODE_BIG);
+  rc = generate_children(*d, d_children, t, nullptr, d_gmoves, &g, s, gen_opts(ctx, *d, t, mode, gcap));
   *gtotal = g;
   if (g > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "%zu grandchildren exceed 32-bit offsets", g);
-  HIP_TRY(launch_offsets_u32(d->offsets.p, t + 1, d_goffsets, s));
+  HIP_TRY(launch_offsets_u32(d->cur.offsets.p, t + 1, d_goffsets, s));
   if (rc) {
     HIP_TRY(hipStreamSynchronize(s));
     return rc;
   }
   HIP_TRY(d->io_out.ensure(t));
   // (the children as parents are child records here too: compared with level 1's below)
-  rc = expand_evaluate(ctx, *d, d_children, t, d->frontier[1].p, g, mode, d->io_out.p, d_grand_out, s, nullptr,
-                       nullptr, false);
+  EvalOpts as_children;
+  as_children.score_parents = false;
+  rc = expand_evaluate(ctx, *d, d_children, t, d->cur.children.p, g, mode, d->io_out.p, d_grand_out, s, as_children);
   if (rc) return rc;
   // the children evaluated twice (level 1 as children, level 2 as parents) must agree
   HIP_TRY(d->sum.ensure(2));
@@ -2600,151 +2641,82 @@ int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parent
   // planned big net's plan -> stream boundary, [score rule] (ends at e[9]), and the stream ->
   // finish boundary (e[10])
   const int NE = 12;
-  std::vector<hipEvent_t> ev((size_t)iters * NE + 2, nullptr);
-  auto cleanup = [&] {
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e);
-  };
-  for (auto &e : ev)
-    if (hipEventCreate(&e) != hipSuccess) {
-      cleanup();
-      return fail(GN_E_HIP, "hipEventCreate failed");
+  struct Events { // destroyed on every way out
+    std::vector<hipEvent_t> v;
+    ~Events() {
+      for (auto &e : v)
+        if (e) (void)hipEventDestroy(e);
     }
-  int rc = GN_OK;
-  size_t t = 0;
+  } events{std::vector<hipEvent_t>((size_t)iters * NE + 2, nullptr)};
+  std::vector<hipEvent_t> &ev = events.v;
+  for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
   HIP_TRY(d->sum.ensure(2)); // [0] rows by write_children's formula, [1] rows the row stream gathered
   HIP_TRY(hipMemsetAsync(d->sum.p, 0, 2 * sizeof(unsigned long long), s));
-  hipError_t he = hipEventRecord(ev[0], s);
-  // the expansion pipeline (GN_OPT_EXPAND_PIPELINE): expansion it + 1's front half (children,
-  // plan) on the device's second stream, into the other buffer set, while expansion it's finalize
-  // and score rule run; its row stream waits for that plan
-  const bool pipe = ctx->pipeline && plan_path(ctx, *d, mode) && ctx->incremental && iters > 1;
-  if (pipe && he == hipSuccess) {
-    hipStream_t B = d->front;
-    size_t tn = 0; // the children of the expansion whose front ran last
-    auto front = [&](int it) -> int {
-      hipEvent_t *e = &ev[2 + (size_t)NE * it];
-      HIP_TRY(hipEventRecord(e[0], B));
-      // (moves into the set's own buffer: the caller's is written once, after the last expansion)
-      int r = generate_children(*d, d_parents, n, nullptr, cap, nullptr, true, &tn, B, e + 1, nullptr,
-                                chain_len(ctx, *d, n), true, mode == GN_MODE_BIG);
-      if (r) return r;
-      if (d_child_out && tn > cap) return fail(GN_E_CAPACITY, "%zu children exceed capacity %zu", tn, cap);
-      r = expand_evaluate(ctx, *d, d_parents, n, d->frontier[1].p, tn, mode, nullptr, nullptr, B, e + 4,
-                          it == 0 ? d->sum.p + 1 : nullptr, true, EXP_FRONT);
-      if (r) return r;
-      HIP_TRY(hipEventRecord(d->ev_planned, B));
-      return GN_OK;
-    };
-    // the front starts after what the stream holds so far (the sequence guard's wait, the reset)
-    he = hipEventRecord(d->ev_streamed, s);
-    if (he == hipSuccess) he = hipStreamWaitEvent(B, d->ev_streamed, 0);
-    if (he == hipSuccess) rc = front(0);
-    t = tn;
-    d->part_locked = true; // (front(0) sized the partial sums; later fronts run beside a back half)
-    struct Unlock {
-      Dev &d;
-      ~Unlock() { d.part_locked = false; }
-    } unlock{*d};
-    HIP_TRY(d->io_out.ensure(n));
-    HIP_TRY(d->io_out2.ensure(std::max<size_t>(t, 1)));
-    gn_eval *po = d_parent_out ? d_parent_out : d->io_out.p, *co = d_child_out ? d_child_out : d->io_out2.p;
-    for (int it = 0; it < iters && rc == GN_OK && he == hipSuccess; ++it) {
-      hipEvent_t *e = &ev[2 + (size_t)NE * it];
-      if ((he = hipStreamWaitEvent(s, d->ev_planned, 0)) != hipSuccess) break;
-      rc = expand_evaluate(ctx, *d, d_parents, n, d->frontier[1].p, t, mode, po, co, s, e + 4, nullptr, true,
-                           EXP_BACK);
-      if (rc) break;
-      const bool more = it + 1 < iters;
-      if (more) { // the next front, after this row stream (it overwrites the plan's lists)
-        swap_sets(*d);
-        he = ctx->pipeline == 2 ? hipSuccess : hipStreamWaitEvent(B, e[10], 0);
-        if (he == hipSuccess) rc = front(it + 1);
-        swap_sets(*d);
-        if (rc || he != hipSuccess) break;
-      }
-      const Replies rp{co, d->child_moves};
-      rc = resolve_scores(ctx, *d, d_parents, n, mode, po, nullptr, s, 2, &rp);
-      if (rc == GN_OK) he = hipEventRecord(e[9], s);
-      if (more) swap_sets(*d), t = tn;
-    }
-    if (rc == GN_OK && he == hipSuccess && d_moves && t)
-      he = hipMemcpyAsync(d_moves, d->child_moves, t * sizeof(uint16_t), hipMemcpyDeviceToDevice, s);
-  }
-  for (int it = 0; !pipe && it < iters && rc == GN_OK && he == hipSuccess; ++it) {
-    hipEvent_t *e = &ev[2 + (size_t)NE * it];
-    he = hipEventRecord(e[0], s);
-    if (he != hipSuccess) break;
-    // rows by write_children's formula only when no planned row stream counts them (a
-    // per-wave atomic over every child would sit in the timed region)
-    const bool planned = plan_path(ctx, *d, mode);
-    rc = generate_children(*d, d_parents, n, nullptr, cap, d_moves, ctx->incremental, &t, s, e + 1,
-                           it == 0 && !planned ? d->sum.p : nullptr, chain_len(ctx, *d, n), planned,
-                           mode == GN_MODE_BIG);
-    if (rc) break;
-    if (d_child_out && t > cap) {
-      rc = fail(GN_E_CAPACITY, "%zu children exceed capacity %zu", t, cap);
-      break;
-    }
-    HIP_TRY(d->io_out.ensure(n));
-    HIP_TRY(d->io_out2.ensure(std::max<size_t>(t, 1)));
-    gn_eval *po = d_parent_out ? d_parent_out : d->io_out.p;
-    rc = expand_evaluate(ctx, *d, d_parents, n, d->frontier[1].p, t, mode, po,
-                         d_child_out ? d_child_out : d->io_out2.p, s, e + 4, it == 0 ? d->sum.p + 1 : nullptr);
-    const Replies rp{d_child_out ? d_child_out : d->io_out2.p, d->child_moves}; // this expansion's replies
-    if (rc == GN_OK) rc = resolve_scores(ctx, *d, d_parents, n, mode, po, nullptr, s, 2, &rp);
-    if (rc == GN_OK) he = hipEventRecord(e[9], s);
-  }
-  if (rc == GN_OK && he == hipSuccess && d_offsets) he = launch_offsets_u32(d->offsets.p, n + 1, d_offsets, s);
-  if (rc == GN_OK && he == hipSuccess) he = hipEventRecord(ev[1], s);
-  if (rc == GN_OK && he == hipSuccess) he = hipEventSynchronize(ev[1]);
-  if (rc == GN_OK && he == hipSuccess) he = hipEventElapsedTime(ms_total, ev[0], ev[1]);
-  // stage k from event k to k + 1 (score: 7 -> 9).  Pipelined, the front's stages are on the second
-  // stream and the big net is the plan (5 -> 8) plus the stream (11 -> 10, after its wait)
-  if (rc == GN_OK && he == hipSuccess && stage_ms) {
-    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int it = 0; it < iters && he == hipSuccess; ++it)
-      for (int k = 0; k < 8 && he == hipSuccess; ++k) {
-        float ms = 0, ms2 = 0;
-        const size_t o = 2 + (size_t)NE * it;
-        if (pipe && k == 5) {
-          he = hipEventElapsedTime(&ms, ev[o + 5], ev[o + 8]);
-          if (he == hipSuccess) he = hipEventElapsedTime(&ms2, ev[o + 11], ev[o + 6]);
-        } else {
-          he = hipEventElapsedTime(&ms, ev[o + k], ev[o + (k < 7 ? k + 1 : 9)]);
-        }
-        acc[k] += ms + ms2;
-      }
-    for (int k = 0; k < 8; ++k) stage_ms[k] = acc[k] / (float)iters;
-  }
-  if (rc == GN_OK && he == hipSuccess && d->planned) { // the big net's two kernels apart
-    float pl = 0, st = 0, fi = 0;
-    for (int it = 0; it < iters && he == hipSuccess; ++it) {
-      float a = 0, b = 0, c = 0;
-      const size_t o = 2 + (size_t)NE * it;
-      he = hipEventElapsedTime(&a, ev[o + 5], ev[o + 8]);
-      if (he == hipSuccess) he = hipEventElapsedTime(&b, ev[o + (pipe ? 11 : 8)], ev[o + 10]); // the stream launches
-      if (he == hipSuccess) he = hipEventElapsedTime(&c, ev[o + 10], ev[o + 6]);  // the sliced stream's finish
-      pl += a, st += b, fi += c;
-    }
-    d->plan_ms = pl / (float)iters, d->stream_ms = st / (float)iters, d->finish_ms = fi / (float)iters;
-  }
-  cleanup();
+  HIP_TRY(hipEventRecord(ev[0], s));
+  const bool pipe = pipelined(ctx, *d, mode, (size_t)iters);
+  size_t t = 0;
+  int rc = run_expansions(
+      ctx, *d, mode, (size_t)iters, 0,
+      [&](size_t it, ExpStep &st) -> int {
+        st.parents = d_parents, st.n = n, st.parent_out = d_parent_out, st.child_out = d_child_out;
+        // (pipelined, the moves go into the set's own buffer: the caller's is written once, after
+        // the last expansion)
+        st.moves = pipe ? nullptr : d_moves;
+        if (d_moves || d_child_out) st.cap = cap;
+        st.ev = &ev[2 + (size_t)NE * it];
+        st.rows = it == 0 ? d->sum.p : nullptr;
+        return GN_OK;
+      },
+      [&](size_t it, size_t children) -> int {
+        t = children;
+        HIP_TRY(hipEventRecord(ev[2 + (size_t)NE * it + 9], s));
+        return GN_OK;
+      });
   *total = t;
   if (rc) return rc;
-  if (he == hipSuccess && (rc = check_plan(*d, s)) != GN_OK) return rc;
-  if (he == hipSuccess && pipe) { // (the other set's expansion too)
+  if (pipe && d_moves && t)
+    HIP_TRY(hipMemcpyAsync(d_moves, d->cur.child_moves, t * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
+  if (d_offsets) HIP_TRY(launch_offsets_u32(d->cur.offsets.p, n + 1, d_offsets, s));
+  HIP_TRY(hipEventRecord(ev[1], s));
+  HIP_TRY(hipEventSynchronize(ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms_total, ev[0], ev[1]));
+  auto add_ms = [&](float &acc, size_t from, size_t to) -> hipError_t {
+    float ms = 0;
+    const hipError_t e = hipEventElapsedTime(&ms, ev[from], ev[to]);
+    acc += ms / (float)iters;
+    return e;
+  };
+  // stage k from event k to k + 1 (score: 7 -> 9).  Pipelined, the front's stages are on the second
+  // stream and the big net is the plan (5 -> 8) plus the stream (11 -> 10, after its wait)
+  float stage[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pl = 0, st = 0, fi = 0;
+  for (int it = 0; it < iters; ++it) {
+    const size_t o = 2 + (size_t)NE * it;
+    for (int k = 0; k < 8 && stage_ms; ++k)
+      if (pipe && k == 5) {
+        HIP_TRY(add_ms(stage[k], o + 5, o + 8));
+        HIP_TRY(add_ms(stage[k], o + 11, o + 6));
+      } else {
+        HIP_TRY(add_ms(stage[k], o + k, o + (k < 7 ? k + 1 : 9)));
+      }
+    if (!d->cur.planned) continue; // the big net's two kernels apart
+    HIP_TRY(add_ms(pl, o + 5, o + 8));
+    HIP_TRY(add_ms(st, o + (pipe ? 11 : 8), o + 10)); // the stream launches
+    HIP_TRY(add_ms(fi, o + 10, o + 6));               // the sliced stream's finish
+  }
+  if (stage_ms) std::copy(stage, stage + 8, stage_ms);
+  if (d->cur.planned) d->plan_ms = pl, d->stream_ms = st, d->finish_ms = fi;
+  if ((rc = check_plan(*d, s)) != GN_OK) return rc;
+  if (pipe) { // (the other set's expansion too)
     swap_sets(*d);
     rc = check_plan(*d, s);
     swap_sets(*d);
     if (rc) return rc;
   }
-  if (ft_rows && he == hipSuccess) {
+  if (ft_rows) {
     unsigned long long r[2] = {0, 0};
-    he = hipMemcpy(r, d->sum.p, sizeof(r), hipMemcpyDeviceToHost);
+    HIP_TRY(hipMemcpy(r, d->sum.p, sizeof(r), hipMemcpyDeviceToHost));
     *ft_rows = ctx->incremental ? (r[1] ? r[1] : r[0]) : 0; // the row stream's own count when it ran
   }
-  if (he != hipSuccess) return fail(GN_E_HIP, "timing failed: %s", hipGetErrorString(he));
   return GN_OK;
 }
 
@@ -2906,11 +2878,11 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
     for (auto &dp : ctx->devs) {
       Dev &d = *dp;
       std::lock_guard<std::mutex> lk(d.mu);
-      if (!d.pstat.p) continue;
+      if (!d.cur.pstat.p) continue;
       HIP_TRY(hipSetDevice(d.id));
       if (d.done_on) HIP_TRY(hipEventSynchronize(d.done));
       unsigned long long v = 0;
-      HIP_TRY(hipMemcpy(&v, d.pstat.p, sizeof(v), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&v, d.cur.pstat.p, sizeof(v), hipMemcpyDeviceToHost));
       sum += (int64_t)v;
     }
     *value = sum;
@@ -2962,14 +2934,14 @@ int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {
   HIP_TRY(sg.e);
   gn_board root;
   pack(B, root);
-  HIP_TRY(d->frontier[0].ensure(1));
-  HIP_TRY(hipMemcpyAsync(d->frontier[0].p, &root, sizeof(root), hipMemcpyHostToDevice, s));
+  HIP_TRY(d->frontier.ensure(1));
+  HIP_TRY(hipMemcpyAsync(d->frontier.p, &root, sizeof(root), hipMemcpyHostToDevice, s));
   size_t n = 1;
   for (int level = 1; level < depth; ++level) {
     size_t total = 0;
-    int rc = generate_children(*d, d->frontier[0].p, n, nullptr, 0, nullptr, false, &total, s, nullptr);
+    int rc = generate_children(*d, d->frontier.p, n, nullptr, nullptr, &total, s);
     if (rc) return rc;
-    std::swap(d->frontier[0], d->frontier[1]);
+    std::swap(d->frontier, d->cur.children);
     n = total;
     if (!n) break;
   }
@@ -2977,7 +2949,7 @@ int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {
   if (n) {
     HIP_TRY(d->sum.ensure(1));
     HIP_TRY(hipMemsetAsync(d->sum.p, 0, sizeof(unsigned long long), s));
-    HIP_TRY(launch_count_sum(d->frontier[0].p, n, d->tables, d->sum.p, s));
+    HIP_TRY(launch_count_sum(d->frontier.p, n, d->tables, d->sum.p, s));
     HIP_TRY(hipMemcpyAsync(&sum, d->sum.p, sizeof(sum), hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(hipStreamSynchronize(s));

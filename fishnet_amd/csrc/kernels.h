@@ -108,36 +108,53 @@ struct TileDesc {
 };
 static_assert(sizeof(TileDesc) == 192, "TileDesc is 192 bytes");
 // Tiles of a block start at tiles + (pbeg + offsets[pbeg]) / 16 + (K + 2) * block (btiles[block]
-// of them), entries at ent + eoff[pbeg] + 16 * block (list 0 upward, list 1 downward from
+// of them), entries at ent + eoff[pbeg] + ENT_SPARE * block (list 0 upward, list 1 downward from
 // the region's end, eoff = exclusive scan of write_children's per-parent entry bounds).
-// One call plans and evaluates blocks [b0, b1) of the n parents (every index absolute, so
-// block ranges can run as a pipeline on different streams).  pool: 88 words (scratch-slot
-// bits, then 8 block claim counters per stream launch), zeroed by the caller before each call; err: bit 0 entry overflow, bit 1 no scratch slot, bit 2 a
-// king-cache load closer than GN_SCR_GAP entries to its list's last store to scratch.
-// rows_out: += FT rows the stream gathers (bias, carry and king-cache rows included);
-// pads_out (optional): += no-op entries the plan inserted to keep GN_SCR_GAP.
-// order: block order of the stream (block_order) or NULL; mid: recorded between the kernels.
-// slices == 3 (L1 3072; part, pinfo non-null): the stream runs as three launches over 1,024
-// columns each (stream_eval_kernel<3072, 3>) and slice_finish_kernel; part = GN_PART_SLICES x npos
-// x 16 int32 fc_0 partial sums, pinfo = npos (PSQT value, bucket) pairs (written by the plan),
-// npos = n + the children;
-// otherwise one launch over whole rows.  fin (optional): recorded after the stream launches
-// (before the finish).  finish false (sliced stream): no slice_finish_kernel, out_parent /
-// out_child stay unwritten: the caller's launch_finalize takes the big net's outputs from part
-// and pinfo itself.
+// One call plans and / or evaluates every block of the n parents.
 // phases: PLAN_PHASE (the pinfo reset and plan_kernel) and / or STREAM_PHASE (the stream launches
 // and the finish), so that an expansion's plan can run on another stream than its row stream (the
-// expansion pipeline, gpu_nnue.hip): the two calls take the same arguments.
+// expansion pipeline, gpu_nnue.hip): the two calls take the same PlanStreamArgs, and differ in
+// phases, swz and the events.
 constexpr int PLAN_PHASE = 1, STREAM_PHASE = 2;
-hipError_t launch_plan_stream(const NetDevice &net, const gn_board *parents, size_t n, const uint64_t *offsets,
-                              const ChildDelta *deltas, const uint8_t *need_parent, const uint8_t *need_child,
-                              int2 *out_parent, int2 *out_child, int swz, const uint8_t *next_slot, int chain_k,
-                              int kc, const uint64_t *eoff, uint64_t *ent, TileDesc *tiles, uint32_t *btiles,
-                              uint32_t *pool, uint32_t *err, unsigned long long *rows_out,
-                              unsigned long long *pads_out, size_t b0, size_t b1, const uint32_t *order,
-                              hipEvent_t mid, hipStream_t s, int slices = 1, int32_t *part = nullptr,
-                              size_t npos = 0, int2 *pinfo = nullptr, hipEvent_t fin = nullptr, bool finish = true,
-                              int phases = PLAN_PHASE | STREAM_PHASE);
+struct PlanStreamArgs {
+  const gn_board *parents = nullptr;
+  size_t n = 0;
+  const uint64_t *offsets = nullptr; // the parents' child offsets (n + 1)
+  const ChildDelta *deltas = nullptr;
+  const uint8_t *need_parent = nullptr, *need_child = nullptr; // what this net evaluates (nullptr: all)
+  int2 *out_parent = nullptr, *out_child = nullptr;
+  const uint8_t *next_slot = nullptr; // the chained walk's links (chain_k > 1) ...
+  int chain_k = 1;                    // ... and its block length
+  int kc = 0;                         // king cache on
+  const uint64_t *eoff = nullptr;
+  uint64_t *ent = nullptr;
+  TileDesc *tiles = nullptr;
+  uint32_t *btiles = nullptr;
+  // 88 words (scratch-slot bits, then 8 block claim counters per stream launch), zeroed by the
+  // caller before each STREAM_PHASE call
+  uint32_t *pool = nullptr;
+  // bit 0 entry overflow, bit 1 no scratch slot, bit 2 a king-cache load closer than GN_SCR_GAP
+  // entries to its list's last store to scratch
+  uint32_t *err = nullptr;
+  unsigned long long *rows_out = nullptr; // += FT rows the stream gathers (bias, carry and king-cache rows included)
+  unsigned long long *pads_out = nullptr; // (optional) += no-op entries the plan inserted to keep GN_SCR_GAP
+  const uint32_t *order = nullptr;        // block order of the stream (block_order) or NULL
+  // slices == 3 (L1 3072; part, pinfo non-null): the stream runs as three launches over 1,024
+  // columns each (stream_eval_kernel<3072, 3>) and slice_finish_kernel; part = GN_PART_SLICES x npos
+  // x 16 int32 fc_0 partial sums, pinfo = npos (PSQT value, bucket) pairs (written by the plan),
+  // npos = n + the children; otherwise one launch over whole rows
+  int slices = 1;
+  int32_t *part = nullptr;
+  size_t npos = 0;
+  int2 *pinfo = nullptr;
+  // finish false (sliced stream): no slice_finish_kernel, out_parent / out_child stay unwritten:
+  // the caller's launch_finalize takes the big net's outputs from part and pinfo itself
+  bool finish = true;
+  int swz = 0;
+  hipEvent_t mid = nullptr;                     // (optional) recorded between the kernels
+  hipEvent_t fin = nullptr, streamed = nullptr; // (optional) recorded after the stream launches (before the finish)
+};
+hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int phases, hipStream_t s);
 // GN_MODE_FULL preparation: need_small = valid && |simple_eval| > threshold,
 // need_big = valid && !need_small.
 hipError_t launch_classify(const gn_board *boards, size_t n, const gn_eval_params &P, uint8_t *need_small,

@@ -1543,64 +1543,63 @@ __global__ void __launch_bounds__(256) slice_finish_kernel(NetDevice net, const 
   else out_child[q - np] = val;
 }
 
-hipError_t launch_plan_stream(const NetDevice &net, const gn_board *parents, size_t n, const uint64_t *offsets,
-                              const ChildDelta *deltas, const uint8_t *need_parent, const uint8_t *need_child,
-                              int2 *out_parent, int2 *out_child, int swz, const uint8_t *next_slot, int chain_k,
-                              int kc, const uint64_t *eoff, uint64_t *ent, TileDesc *tiles, uint32_t *btiles,
-                              uint32_t *pool, uint32_t *err, unsigned long long *rows_out,
-                              unsigned long long *pads_out, size_t b0, size_t b1, const uint32_t *order,
-                              hipEvent_t mid, hipStream_t s, int slices, int32_t *part, size_t npos,
-                              int2 *pinfo, hipEvent_t fin, bool finish, int phases) {
-  if (!n || b1 <= b0) return hipSuccess;
+hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int phases, hipStream_t s) {
+  const size_t n = a.n;
+  if (!n) return hipSuccess;
   const bool do_plan = phases & PLAN_PHASE, do_stream = phases & STREAM_PHASE;
   if (n >= 0x80000000ull) return hipErrorInvalidValue; // 32-bit parent indices in the kernels
-  const uint32_t K = chain_k > 1 && next_slot ? (uint32_t)chain_k : 1u;
-  const int scr = K > 1 && kc; // the king cache's rows (the chained walk itself needs no scratch)
-  if (b1 > (n + K - 1) / K) return hipErrorInvalidValue;
-  const uint32_t nb = (uint32_t)(b1 - b0), B0 = (uint32_t)b0, B1 = (uint32_t)b1;
-  const unsigned pg = (nb + PLAN_WAVES - 1) / PLAN_WAVES, g = swz == 1 ? 8 * ((nb + 7) / 8) : nb + nb / 16 + 8; // (stream_eval_kernel: claims)
+  const uint32_t K = a.chain_k > 1 && a.next_slot ? (uint32_t)a.chain_k : 1u;
+  const uint8_t *next_slot = K > 1 ? a.next_slot : nullptr;
+  const int kc = K > 1 ? a.kc : 0;
+  const int scr = K > 1 && a.kc; // the king cache's rows (the chained walk itself needs no scratch)
+  const uint32_t nb = (uint32_t)((n + K - 1) / K), B0 = 0, B1 = nb; // every block of the n parents
+  const unsigned pg = (nb + PLAN_WAVES - 1) / PLAN_WAVES, g = a.swz == 1 ? 8 * ((nb + 7) / 8) : nb + nb / 16 + 8; // (stream_eval_kernel: claims)
+  auto stream_done = [&] {
+    if (a.fin) (void)hipEventRecord(a.fin, s);
+    if (a.streamed) (void)hipEventRecord(a.streamed, s);
+  };
   if (net.L1 == 3072) {
-    const bool sliced = slices == 3 && part && pinfo;
+    const bool sliced = a.slices == 3 && a.part && a.pinfo;
     if (do_plan) {
       if (sliced) { // (positions the big net does not evaluate keep pinfo.y < 0; the plan writes the rest)
-        hipError_t e = hipMemsetAsync(pinfo, 0xFF, npos * sizeof(int2), s);
+        hipError_t e = hipMemsetAsync(a.pinfo, 0xFF, a.npos * sizeof(int2), s);
         if (e != hipSuccess) return e;
       }
-      hipLaunchKernelGGL((plan_kernel<3072>), dim3(pg), dim3(GN_FRONT_WG), 0, s, net, parents, offsets, deltas, need_parent,
-                         need_child, K > 1 ? next_slot : nullptr, (uint32_t)n, K, B0, B1, K > 1 ? kc : 0, eoff, ent,
-                         tiles, btiles, rows_out, pads_out, err, sliced ? pinfo : nullptr,
+      hipLaunchKernelGGL((plan_kernel<3072>), dim3(pg), dim3(GN_FRONT_WG), 0, s, net, a.parents, a.offsets, a.deltas,
+                         a.need_parent, a.need_child, next_slot, (uint32_t)n, K, B0, B1, kc, a.eoff, a.ent, a.tiles,
+                         a.btiles, a.rows_out, a.pads_out, a.err, sliced ? a.pinfo : nullptr,
                          sliced ? ps::field_xu(3072, 3) : ps::field_xu(3072, 1), sliced ? ps::field_hu(3072, 3) : ps::field_hu(3072, 1));
-      if (mid) (void)hipEventRecord(mid, s);
+      if (a.mid) (void)hipEventRecord(a.mid, s);
     }
     if (!do_stream) {
     } else if (sliced) { // three launches over 1,024 columns each (claim counters pool[64 + 8 slice ..]),
       // then the finish
       for (int sl = 0; sl < 3; ++sl)
-        hipLaunchKernelGGL((stream_eval_kernel<3072, 3>), dim3(g), dim3(128), 0, s, net, offsets, (uint32_t)n, K, B0,
-                           B1, swz, eoff, ent, tiles, btiles, order, out_parent, out_child, pool, scr, err,
-                           pool + 64 + 8 * sl, sl, part, (uint64_t)npos, pinfo);
-      if (fin) (void)hipEventRecord(fin, s);
-      if (finish) // (otherwise the caller's finalize takes the outputs from part itself)
-        hipLaunchKernelGGL((slice_finish_kernel<3>), dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, s, net, part,
-                           pinfo, (uint64_t)npos, (uint32_t)n, out_parent, out_child);
+        hipLaunchKernelGGL((stream_eval_kernel<3072, 3>), dim3(g), dim3(128), 0, s, net, a.offsets, (uint32_t)n, K, B0,
+                           B1, a.swz, a.eoff, a.ent, a.tiles, a.btiles, a.order, a.out_parent, a.out_child, a.pool, scr,
+                           a.err, a.pool + 64 + 8 * sl, sl, a.part, (uint64_t)a.npos, a.pinfo);
+      stream_done();
+      if (a.finish) // (otherwise the caller's finalize takes the outputs from part itself)
+        hipLaunchKernelGGL((slice_finish_kernel<3>), dim3((unsigned)((a.npos + 255) / 256)), dim3(256), 0, s, net,
+                           a.part, a.pinfo, (uint64_t)a.npos, (uint32_t)n, a.out_parent, a.out_child);
     } else {
-      hipLaunchKernelGGL((stream_eval_kernel<3072>), dim3(g), dim3(384), 0, s, net, offsets, (uint32_t)n, K, B0, B1,
-                         swz, eoff, ent, tiles, btiles, order, out_parent, out_child, pool, scr, err, pool + 64, 0,
-                         nullptr, (uint64_t)0, nullptr);
-      if (fin) (void)hipEventRecord(fin, s);
+      hipLaunchKernelGGL((stream_eval_kernel<3072>), dim3(g), dim3(384), 0, s, net, a.offsets, (uint32_t)n, K, B0, B1,
+                         a.swz, a.eoff, a.ent, a.tiles, a.btiles, a.order, a.out_parent, a.out_child, a.pool, scr, a.err,
+                         a.pool + 64, 0, nullptr, (uint64_t)0, nullptr);
+      stream_done();
     }
   } else if (net.L1 == 1024) {
     if (do_plan) {
-      hipLaunchKernelGGL((plan_kernel<1024>), dim3(pg), dim3(GN_FRONT_WG), 0, s, net, parents, offsets, deltas, need_parent,
-                         need_child, K > 1 ? next_slot : nullptr, (uint32_t)n, K, B0, B1, K > 1 ? kc : 0, eoff, ent,
-                         tiles, btiles, rows_out, pads_out, err, nullptr, ps::field_xu(1024, 1), ps::field_hu(1024, 1));
-      if (mid) (void)hipEventRecord(mid, s);
+      hipLaunchKernelGGL((plan_kernel<1024>), dim3(pg), dim3(GN_FRONT_WG), 0, s, net, a.parents, a.offsets, a.deltas,
+                         a.need_parent, a.need_child, next_slot, (uint32_t)n, K, B0, B1, kc, a.eoff, a.ent, a.tiles,
+                         a.btiles, a.rows_out, a.pads_out, a.err, nullptr, ps::field_xu(1024, 1), ps::field_hu(1024, 1));
+      if (a.mid) (void)hipEventRecord(a.mid, s);
     }
     if (do_stream) {
-      hipLaunchKernelGGL((stream_eval_kernel<1024>), dim3(g), dim3(128), 0, s, net, offsets, (uint32_t)n, K, B0, B1,
-                         swz, eoff, ent, tiles, btiles, order, out_parent, out_child, pool, scr, err, pool + 64, 0,
-                         nullptr, (uint64_t)0, nullptr);
-      if (fin) (void)hipEventRecord(fin, s);
+      hipLaunchKernelGGL((stream_eval_kernel<1024>), dim3(g), dim3(128), 0, s, net, a.offsets, (uint32_t)n, K, B0, B1,
+                         a.swz, a.eoff, a.ent, a.tiles, a.btiles, a.order, a.out_parent, a.out_child, a.pool, scr, a.err,
+                         a.pool + 64, 0, nullptr, (uint64_t)0, nullptr);
+      stream_done();
     }
   } else {
     return hipErrorInvalidValue;

@@ -1137,3 +1137,38 @@ def test_expand_pipeline_equals_serial(gpu_ctx, oracle_nets, oracle_lib):
         p_exp, m_exp, k_exp = oracle_lib.expand_eval(big, small, G.board_to_fen(parents[i]), 1, incremental=True)
         assert tuple(pev[i]) == p_exp
         assert dict(zip(mv.tolist(), map(tuple, ev.tolist()))) == dict(zip(m_exp, map(tuple, k_exp.tolist())))
+
+
+def test_expand_capacity_error_then_retry_equals_serial(gpu_ctx):
+    """gn_time_expand_device with child buffers one entry too small fails with GN_E_CAPACITY before
+    anything is written, pipelined (GN_OPT_EXPAND_PIPELINE 2 and 1) as well, and leaves nothing of
+    its front half queued: the same call with enough room, at once after it, gives every output of
+    one serial expansion -- parents, offsets, moves, children (24 games of 40 plies, mode BIG)."""
+    from fishnet_amd import gpu_nnue as G
+    games, plies = 24, 40
+    n = games * (plies + 1)
+    d_b = gpu_ctx.alloc(n * 32)
+    gpu_ctx.random_games_device(0x5EED0CA9, 0, games, plies, d_b)
+    gpu_ctx.synchronize()
+    _, total, _, _ = gpu_ctx.time_expand_device(d_b, n, G.MODE_BIG, 1)
+    out = {"po": gpu_ctx.alloc(n * G.EVAL_SIZE), "off": gpu_ctx.alloc((n + 1) * 4), "mv": gpu_ctx.alloc(total * 2),
+           "co": gpu_ctx.alloc(total * G.EVAL_SIZE)}
+
+    def run(iters, pipe, cap):
+        gpu_ctx.set_option(G.OPT_EXPAND_PIPELINE, pipe)
+        for b in ("po", "off", "mv", "co"):
+            out[b].upload(np.zeros(out[b].nbytes, np.uint8))
+        _, t, _, _ = gpu_ctx.time_expand_device(d_b, n, G.MODE_BIG, iters, outputs=dict(out, cap=cap))
+        assert t == total
+        return tuple(gpu_ctx.checksum_device(out[b], nb) for b, nb in
+                     (("po", n * G.EVAL_SIZE), ("off", (n + 1) * 4), ("mv", t * 2), ("co", t * G.EVAL_SIZE)))
+
+    try:
+        serial = run(1, 0, total)
+        for pipe in (2, 1):
+            with pytest.raises(G.GnError) as e:
+                run(3, pipe, total - 1)
+            assert e.value.code == G.E_CAPACITY, pipe
+            assert run(3, pipe, total) == serial, pipe
+    finally:
+        gpu_ctx.set_option(G.OPT_EXPAND_PIPELINE, 2)
