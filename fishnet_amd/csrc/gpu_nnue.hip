@@ -701,7 +701,13 @@ static int evaluate_on(gn_ctx *ctx, Dev &d, const gn_board *b, size_t n, int mod
   }
   const int swz = (ctx->swizzle >> 1) & 1;
   HIP_TRY(mark(1));
-  if (mode != GN_MODE_BIG)
+  if (mode == GN_MODE_FULL && d.net[SMALL].L1 != 128) {
+    // only the 128-wide kernel selects inside its launch: a wider net in the small slot gets the
+    // selection, the selected positions and the re-evaluation marks as launches of their own
+    HIP_TRY(launch_classify(b, n, P, nsm.p, nbg.p, s));
+    HIP_TRY(launch_eval_net(d.net[SMALL], b, nsm.p, n, osm.p, perm, swz, s, nullptr));
+    HIP_TRY(launch_reeval(osm.p, nsm.p, n, P, nbg.p, s));
+  } else if (mode != GN_MODE_BIG)
     HIP_TRY(launch_eval_net(d.net[SMALL], b, nullptr, n, osm.p, perm, swz, s, mode == GN_MODE_SMALL ? rows_out : nullptr,
                             mode == GN_MODE_FULL ? &P : nullptr, nsm.p, nbg.p));
   HIP_TRY(mark(2));
@@ -1254,7 +1260,11 @@ static int fast_run(gn_ctx *ctx, Dev &d, std::unique_lock<std::mutex> &lk, const
 // Host boards -> device(s) -> gn_eval: contiguous shards, one host thread per device.
 static int evaluate_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int mode, gn_eval *out) {
   if (!n) return GN_OK;
-  if (ctx->fast_batch && n <= FAST_MAX && ctx->devs.size() == 1 && mode >= GN_MODE_FULL && mode <= GN_MODE_SMALL) {
+  // (the graphs are built for the 128-wide small net's in-launch selection: a context with a wider net
+  // in the small slot takes the general path)
+  const bool small_ok = !ctx->devs.empty() && (!ctx->devs[0]->has[SMALL] || ctx->devs[0]->net[SMALL].L1 == 128);
+  if (ctx->fast_batch && n <= FAST_MAX && ctx->devs.size() == 1 && small_ok && mode >= GN_MODE_FULL &&
+      mode <= GN_MODE_SMALL) {
     Dev &d = *ctx->devs[0];
     std::unique_lock<std::mutex> lk(d.mu);
     bool done = false;

@@ -121,15 +121,16 @@ def _normal(seed: int, stream: int, n: int, sigma: float, mean: int = 0) -> np.n
     return out
 
 
-def synth_net_arrays(l1: int, seed: int, stress: bool = False) -> dict:
+def synth_net_arrays(l1: int, seed: int, stress: bool = False, with_ft: bool = True) -> dict:
     """The integer parameter arrays of a synthetic net, exactly as stored in
-    the file (feature-transformer values NOT doubled)."""
+    the file (feature-transformer values NOT doubled).  with_ft=False leaves
+    the (large) feature-transformer weight table out: "ft_w" is None."""
     assert l1 % 32 == 0 and 32 <= l1 <= 4096
     ft_sigma = 6000.0 if stress else 18.0
     a = {
         "ft_bias": np.clip(_normal(seed, 1, l1, 60.0, 40), -16383, 16383).astype(np.int16),
         "ft_w": np.clip(_normal(seed, 2, FT_INPUTS * l1, ft_sigma), -16383, 16383).astype(np.int16)
-        .reshape(FT_INPUTS, l1),
+        .reshape(FT_INPUTS, l1) if with_ft else None,
         "psqt": _normal(seed, 3, FT_INPUTS * PSQT_BUCKETS, 1000.0).astype(np.int32).reshape(FT_INPUTS, 8),
         "b0": [], "w0": [], "b1": [], "w1": [], "b2": [], "w2": [],
     }
@@ -148,21 +149,33 @@ def synth_net_arrays(l1: int, seed: int, stress: bool = False) -> dict:
     return a
 
 
+def tail_bytes(a: dict, l1: int) -> bytes:
+    """The part of the image after the feature-transformer weights: the LEB128 PSQT
+    block and the eight fixed-size layer stacks."""
+    arch_hash = hashes(l1)[2]
+    parts = [leb128_encode(a["psqt"])]
+    for b in range(LAYER_STACKS):
+        parts += [struct.pack("<I", arch_hash)] + [a[k][b].astype("<i4" if k[0] == "b" else np.int8).tobytes()
+                                                   for k in ("b0", "w0", "b1", "w1", "b2", "w2")]
+    return b"".join(parts)
+
+
+def net_bytes(a: dict, l1: int, description: str) -> bytes:
+    """A complete .nnue image of the parameter arrays `a` (as synth_net_arrays returns them)."""
+    net_hash, ft_hash, _ = hashes(l1)
+    desc = description.encode()
+    return b"".join([struct.pack("<III", VERSION, net_hash, len(desc)), desc, struct.pack("<I", ft_hash),
+                     leb128_encode(a["ft_bias"]), leb128_encode(a["ft_w"]), tail_bytes(a, l1)])
+
+
 def synth_net_bytes(l1: int, seed: int, stress: bool = False,
                     description: str | None = None) -> bytes:
     """A complete .nnue image for an L1-wide HalfKAv2_hm network.
 
     stress=True uses feature-transformer weights large enough that the int16
     accumulators wrap often (exercises the wrapping semantics)."""
-    a = synth_net_arrays(l1, seed, stress)
-    net_hash, ft_hash, arch_hash = hashes(l1)
-    desc = (description or f"fishnet_amd synthetic net L1={l1} seed={seed} stress={int(stress)}").encode()
-    parts = [struct.pack("<III", VERSION, net_hash, len(desc)), desc, struct.pack("<I", ft_hash),
-             leb128_encode(a["ft_bias"]), leb128_encode(a["ft_w"]), leb128_encode(a["psqt"])]
-    for b in range(LAYER_STACKS):
-        parts += [struct.pack("<I", arch_hash)] + [a[k][b].astype("<i4" if k[0] == "b" else np.int8).tobytes()
-                                                   for k in ("b0", "w0", "b1", "w1", "b2", "w2")]
-    return b"".join(parts)
+    return net_bytes(synth_net_arrays(l1, seed, stress), l1,
+                     description or f"fishnet_amd synthetic net L1={l1} seed={seed} stress={int(stress)}")
 
 
 def write_synth_net(path: str, l1: int, seed: int, stress: bool = False) -> str:

@@ -291,7 +291,10 @@ typedef struct gn_ctx gn_ctx;
 /* ---- lifecycle ---------------------------------------------------------- */
 /* Load nets and upload them to each listed device (devices = NULL: device 0).
  * small_path may be NULL (then only GN_MODE_BIG works); big_path may be NULL
- * (then only GN_MODE_SMALL works). */
+ * (then only GN_MODE_SMALL works).  A net wider than 128 in the small slot is
+ * evaluated (gn_evaluate_*; mode FULL's selection then runs as launches of its
+ * own and the small-batch graphs are not used); the expansion calls support it
+ * in GN_MODE_BIG only. */
 GN_API int gn_load_net(const char *big_path, const char *small_path, const int *devices, int n_devices,
                 gn_ctx **out);
 /* A file named like Stockfish's nets, "nn-" + 12 lowercase hex digits + ".nnue"

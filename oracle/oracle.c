@@ -675,8 +675,10 @@ static void update(const or_net *net, const pos_t *p, const accs_t *pa, const po
   }
 }
 
-/* Network::evaluate from accumulators: {psqt / 16, positional / 16} (side-to-move POV) */
-static void net_output_acc(const or_net *net, const pos_t *p, const accs_t *a, int32_t *psqt_out, int32_t *pos_out) {
+/* Network::evaluate from accumulators: {psqt / 16, positional / 16} (side-to-move POV);
+ * tr (optional) receives the layer stack's intermediate values. */
+static void net_output_traced(const or_net *net, const pos_t *p, const accs_t *a, int32_t *psqt_out, int32_t *pos_out,
+                              or_trace *tr) {
   int L1 = net->L1, H = L1 / 2;
   uint8_t x[4096];
   const int16_t(*acc)[4096] = a->acc;
@@ -691,7 +693,7 @@ static void net_output_acc(const or_net *net, const pos_t *p, const accs_t *a, i
   for (int sq = 0; sq < 64; ++sq) count += p->b[sq] != 0;
   int bucket = (count - 1) / 4;
   int32_t psqt = (int32_t)((uint32_t)ps[p->stm][bucket] - (uint32_t)ps[!p->stm][bucket]) / 2;
-  int32_t fc0[16], fc1[32], in1[32];
+  int32_t fc0[16], fc1[32], in1[32], sum1[32];
   for (int o = 0; o < 16; ++o) {
     int32_t s = net->b0[bucket][o];
     const int8_t *w = net->w0[bucket] + (size_t)o * L1;
@@ -707,6 +709,7 @@ static void net_output_acc(const or_net *net, const pos_t *p, const accs_t *a, i
   for (int o = 0; o < 32; ++o) {
     int32_t s = net->b1[bucket][o];
     for (int j = 0; j < 32; ++j) s = wadd(s, (int32_t)net->w1[bucket][o * 32 + j] * in1[j]);
+    sum1[o] = s;
     fc1[o] = clampi(s >> 6, 0, 127);
   }
   int32_t fc2 = net->b2[bucket];
@@ -715,6 +718,18 @@ static void net_output_acc(const or_net *net, const pos_t *p, const accs_t *a, i
   int32_t positional = wadd(fc2, fwd);
   *psqt_out = psqt / 16;
   *pos_out = positional / 16;
+  if (tr) {
+    tr->bucket = bucket;
+    memcpy(tr->fc0, fc0, sizeof fc0);
+    memcpy(tr->in1, in1, sizeof in1);
+    memcpy(tr->sum1, sum1, sizeof sum1);
+    memcpy(tr->fc1, fc1, sizeof fc1);
+    tr->fc2 = fc2, tr->fwd = fwd;
+  }
+}
+
+static void net_output_acc(const or_net *net, const pos_t *p, const accs_t *a, int32_t *psqt_out, int32_t *pos_out) {
+  net_output_traced(net, p, a, psqt_out, pos_out, NULL);
 }
 
 /* Network::evaluate: returns {psqt / 16, positional / 16} (side-to-move POV) */
@@ -950,6 +965,16 @@ int or_net_output(const or_net *net, const char *fen, int32_t *psqt, int32_t *po
   pos_t p;
   if (parse_fen(fen, &p)) return -1;
   net_output(net, &p, psqt, positional);
+  return 0;
+}
+
+int or_trace_fen(const or_net *net, const char *fen, or_trace *out) {
+  static __thread accs_t a;
+  pos_t p;
+  int32_t psqt, positional;
+  if (parse_fen(fen, &p)) return -1;
+  refresh(net, &p, &a);
+  net_output_traced(net, &p, &a, &psqt, &positional, out);
   return 0;
 }
 

@@ -81,6 +81,20 @@ int or_features(const char *fen, int perspective, uint32_t *idx, int cap);
 int or_accumulate(const or_net *net, const char *fen, int perspective, int16_t *acc, int32_t *psqt8);
 int or_net_output(const or_net *net, const char *fen, int32_t *psqt, int32_t *positional);
 
+/* The layer stack's intermediate values for one position (the same code as or_net_output):
+ * the piece-count bucket, fc_0's 16 sums, fc_1's 32 inputs (15 squared, 15 clipped, 2 zero),
+ * fc_1's sums before and after `>> 6` + clip, fc_2's sum and the skip term of fc0[15]. */
+typedef struct {
+  int32_t bucket;
+  int32_t fc0[16];
+  int32_t in1[32];
+  int32_t sum1[32];
+  int32_t fc1[32];
+  int32_t fc2;
+  int32_t fwd;
+} or_trace;
+int or_trace_fen(const or_net *net, const char *fen, or_trace *out);
+
 /* move generation.  Moves use Stockfish's 16-bit encoding:
  * to | from << 6 | (promo_type - KNIGHT) << 12 | type << 14, type 1 = promotion,
  * 2 = en passant, 3 = castling (to = rook square). */

@@ -33,6 +33,16 @@ EVAL_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("final_v", "<i4"
 assert EVAL_DTYPE.itemsize == C.sizeof(OrEval) == 24
 
 
+class OrTrace(C.Structure):
+    _fields_ = [("bucket", C.c_int32), ("fc0", C.c_int32 * 16), ("in1", C.c_int32 * 32), ("sum1", C.c_int32 * 32),
+                ("fc1", C.c_int32 * 32), ("fc2", C.c_int32), ("fwd", C.c_int32)]
+
+
+TRACE_DTYPE = np.dtype([("bucket", "<i4"), ("fc0", "<i4", 16), ("in1", "<i4", 32), ("sum1", "<i4", 32),
+                        ("fc1", "<i4", 32), ("fc2", "<i4"), ("fwd", "<i4")])
+assert TRACE_DTYPE.itemsize == C.sizeof(OrTrace)
+
+
 def _tup(e):
     return (e.psqt, e.positional, e.final_v, e.final_cp, e.score, e.flags, e.best_move)
 
@@ -71,6 +81,7 @@ def lib():
         L.or_features.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_uint32), C.c_int]
         L.or_accumulate.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p]
         L.or_net_output.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.or_trace_fen.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
         L.or_legal_moves.argtypes = [C.c_char_p, C.POINTER(C.c_uint16), C.c_int]
         L.or_child_fen.argtypes = [C.c_char_p, C.c_uint16, C.c_char_p, C.c_int]
         L.or_normalize_fen.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
@@ -159,6 +170,19 @@ def net_output(net, fen):
     if lib().or_net_output(net.h, fen.encode(), C.byref(a), C.byref(b)):
         raise ValueError("bad fen")
     return a.value, b.value
+
+
+def trace_fens(net, fens):
+    """The layer stack's intermediate values of every FEN: a TRACE_DTYPE array."""
+    out = np.zeros(len(fens), dtype=TRACE_DTYPE)
+    for i, f in enumerate(fens):
+        if lib().or_trace_fen(net.h, f.encode(), out[i:i + 1].ctypes.data):
+            raise ValueError(f"bad fen: {f}")
+    return out
+
+
+def trace_fen(net, fen):
+    return trace_fens(net, [fen])[0]
 
 
 def legal_moves(fen):

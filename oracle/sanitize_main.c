@@ -6,7 +6,8 @@
  *
  * usage: oracle_sanitize <big.nnue> <small.nnue> <fens.txt>
  * For every FEN line: or_eval_fen in the three modes, or_expand_eval and
- * or_expand_eval_inc (BIG mode; their results must agree), and perft(2).  Prints one
+ * or_expand_eval_inc (BIG mode; their results must agree), or_trace_fen on both nets,
+ * and perft(2).  Prints one
  * line per FEN: "<final_v FULL> <final_cp FULL> <n children> <sum of child final_v> <perft2>",
  * or "bad" for a rejected FEN.
  */
@@ -48,6 +49,11 @@ int main(int argc, char **argv) {
     if (n != n2 || n < 0 || memcmp(&par, &par2, sizeof par) || memcmp(mv, mv2, (size_t)(n > 0 ? n : 0) * 2) ||
         memcmp(ch, ch2, (size_t)(n > 0 ? n : 0) * sizeof(or_eval))) {
       fprintf(stderr, "refresh and incremental expansion differ: %s\n", line);
+      rc = 1;
+    }
+    or_trace tb, ts;
+    if (or_trace_fen(big, line, &tb) || or_trace_fen(small, line, &ts) || tb.bucket != ts.bucket) {
+      fprintf(stderr, "trace failed: %s\n", line);
       rc = 1;
     }
     long long sum = 0;

@@ -368,7 +368,12 @@ def test_common_row_base_tiles(gpu_ctx, oracle_nets, oracle_lib, ksort):
     most pieces and alternate the side to move; runs of one repeated position make the
     whole placement common (zero per-position rows); invalid boards and a tile whose
     first position is invalid must not constrain the base.  Bit-exact vs the oracle,
-    with the batch king/placement-sorted and in input order."""
+    with the batch king/placement-sorted and in input order.
+
+    Tile size: 789 positions, so launch_eval_net gives the big net one position per workgroup
+    (batches of <= 1,024) and the common-row base does nothing there; the small net runs 16 per
+    tile.  The big net at 2, 4, 8 and 16 positions per workgroup is compared with the oracle in
+    test_gpu_edge_nets.py::test_eval_net_3072_every_tile_size."""
     from fishnet_amd import gpu_nnue as G
     games, plies = 12, 60
     n = games * (plies + 1)
@@ -530,7 +535,11 @@ def test_caller_stream_and_context_stream_do_not_race(gpu_ctx):
 def test_common_row_base_under_int16_wrap_and_shared_kings(oracle_lib):
     """the common-row base with the int16-wrapping stress net, and tiles whose
     positions share their kings (and so the common rows) but differ in the side to move and
-    the PSQT bucket: the per-position PSQT of the common rows at each position's own bucket."""
+    the PSQT bucket: the per-position PSQT of the common rows at each position's own bucket.
+
+    Tile size: 383 positions, one per big-net workgroup (launch_eval_net, batches of <= 1,024), so
+    the tiles described above are not formed here; the stress net at 2 to 16 positions per
+    workgroup runs in test_gpu_edge_nets.py::test_eval_net_3072_stress_every_tile_size."""
     from fishnet_amd import gpu_nnue as G, synthnet
     p = synthnet.cached_synth_net(3072, 11, stress=True)
     ctx = G.GpuNnue(p, None)
