@@ -740,32 +740,50 @@ static void net_output(const or_net *net, const pos_t *p, int32_t *psqt_out, int
 }
 
 /* ------------------------------------------------------------ evaluate -- */
-static const int PIECE_VALUE[7] = {0, 208, 781, 825, 1276, 2538, 0};
+/* The Eval::evaluate / UCIEngine::to_cp constants (or_eval_params, oracle.h).  Process-wide;
+ * written only by or_set_eval_params between calls, read by every evaluation. */
+#define OR_DEFAULT_PARAMS                                                                          \
+  {962,   125,   131,   236, 18000, 18000, 535, 535, 77777, 212, 31506, {208, 781, 825, 1276, 2538}, \
+   {-37.45051876, 121.19101539, -132.78783573, 420.70576692}, 17, 78, 58, {1, 3, 3, 5, 9}}
+static or_eval_params EP = OR_DEFAULT_PARAMS;
 
+int or_set_eval_params(const or_eval_params *p) {
+  static const or_eval_params defaults = OR_DEFAULT_PARAMS;
+  if (!p) p = &defaults;
+  if (p->material_base == 0 || p->rule50_div == 0 || p->complexity_div_small == 0 || p->complexity_div_big == 0 ||
+      p->wdl_material_anchor == 0)
+    return -1; /* a zero divisor (gn_set_eval_params refuses the same) */
+  EP = *p;
+  return 0;
+}
+
+void or_get_eval_params(or_eval_params *out) { *out = EP; }
+
+/* pawn counts and non-pawn material (piece_value[1..4]) per colour */
 static void material(const pos_t *p, int *pawns, int npm[2]) {
   int np[2] = {0, 0};
   npm[0] = npm[1] = 0;
   for (int sq = 0; sq < 64; ++sq) {
     int pc = p->b[sq];
-    if (!pc) continue;
+    if (!pc || TYPE_OF(pc) == KING) continue;
     if (TYPE_OF(pc) == PAWN) np[COLOR_OF(pc)]++;
-    else npm[COLOR_OF(pc)] += PIECE_VALUE[TYPE_OF(pc)];
+    else npm[COLOR_OF(pc)] += EP.piece_value[TYPE_OF(pc) - 1];
   }
   pawns[0] = np[0], pawns[1] = np[1];
 }
 
-/* UCIEngine::to_cp (uci.cpp, Stockfish 17 era; recalled, parity unpinned):
- *   material = P + 3N + 3B + 5R + 9Q over both colours,
- *   m = clamp(material, 17, 78) / 58.0,
- *   a = ((as[0] m + as[1]) m + as[2]) m + as[3],
- *   cp = round(100 * v / a). */
+/* UCIEngine::to_cp (uci.cpp, Stockfish 17 era; recalled, parity unpinned), defaults:
+ *   material = P + 3N + 3B + 5R + 9Q over both colours (wdl_piece_weight),
+ *   m = clamp(material, 17, 78) / 58.0 (wdl_material_min / _max / _anchor),
+ *   a = ((as[0] m + as[1]) m + as[2]) m + as[3] (wdl_a),
+ *   cp = round(100 * v / a), half away from zero. */
 static int32_t to_cp(const pos_t *p, int32_t v) {
-  static const int W[7] = {0, 1, 3, 3, 5, 9, 0};
-  static const double as[4] = {-37.45051876, 121.19101539, -132.78783573, 420.70576692};
+  const double *as = EP.wdl_a;
   int material = 0;
   for (int sq = 0; sq < 64; ++sq)
-    if (p->b[sq]) material += W[TYPE_OF(p->b[sq])];
-  double m = (double)(material < 17 ? 17 : material > 78 ? 78 : material) / 58.0;
+    if (p->b[sq] && TYPE_OF(p->b[sq]) != KING) material += EP.wdl_piece_weight[TYPE_OF(p->b[sq]) - 1];
+  const int lo = EP.wdl_material_min, hi = EP.wdl_material_max;
+  double m = (double)(material < lo ? lo : material > hi ? hi : material) / (double)EP.wdl_material_anchor;
   double a = (((as[0] * m + as[1]) * m + as[2]) * m) + as[3];
   return (int32_t)round((double)(100 * (long long)v) / a);
 }
@@ -794,25 +812,26 @@ static void evaluate_src(const or_net *big, const or_net *small, const pos_t *p,
                          acc_src_t *src) {
   int pawns[2], npm[2], us = p->stm;
   material(p, pawns, npm);
-  int simple = 208 * (pawns[us] - pawns[!us]) + (npm[us] - npm[!us]);
-  int small_net = mode == OR_MODE_SMALL ? 1 : mode == OR_MODE_BIG ? 0 : (abs(simple) > 962);
+  int simple = EP.piece_value[0] * (pawns[us] - pawns[!us]) + (npm[us] - npm[!us]);
+  int small_net = mode == OR_MODE_SMALL ? 1 : mode == OR_MODE_BIG ? 0 : (abs(simple) > EP.small_net_threshold);
   uint32_t flags = 0;
   int32_t psqt, positional, nnue;
   if (small_net) output_of(small, 1, p, src, &psqt, &positional);
   else output_of(big, 0, p, src, &psqt, &positional);
-  nnue = wadd(wmul(125, psqt), wmul(131, positional)) / 128;
-  if (mode == OR_MODE_FULL && small_net && abs(nnue) < 236) {
+  nnue = wadd(wmul(EP.psqt_weight, psqt), wmul(EP.positional_weight, positional)) / 128;
+  if (mode == OR_MODE_FULL && small_net && abs(nnue) < EP.reeval_threshold) {
     output_of(big, 0, p, src, &psqt, &positional);
-    nnue = wadd(wmul(125, psqt), wmul(131, positional)) / 128;
+    nnue = wadd(wmul(EP.psqt_weight, psqt), wmul(EP.positional_weight, positional)) / 128;
     small_net = 0;
     flags |= OR_FLAG_REEVAL;
   }
+  /* the variants follow the net that produced the final output: big after a re-evaluation */
   int32_t complexity = abs(psqt - positional);
-  nnue = wadd(nnue, -(wmul(nnue, complexity) / 18000));
-  int32_t mat = 535 * (pawns[0] + pawns[1]) + npm[0] + npm[1];
-  int32_t v = wmul(nnue, 77777 + mat) / 77777;
-  v = wadd(v, -(wmul(v, p->rule50) / 212));
-  v = clampi(v, -31506, 31506);
+  nnue = wadd(nnue, -(wmul(nnue, complexity) / (small_net ? EP.complexity_div_small : EP.complexity_div_big)));
+  int32_t mat = (small_net ? EP.material_pawn_small : EP.material_pawn_big) * (pawns[0] + pawns[1]) + npm[0] + npm[1];
+  int32_t v = wmul(nnue, EP.material_base + mat) / EP.material_base;
+  v = wadd(v, -(wmul(v, p->rule50) / EP.rule50_div));
+  v = clampi(v, -EP.value_clamp, EP.value_clamp);
   if (small_net) flags |= OR_FLAG_SMALLNET;
   if (in_check(p)) flags |= OR_FLAG_IN_CHECK;
   out->psqt = psqt, out->positional = positional, out->final_v = v, out->flags = (uint16_t)flags;

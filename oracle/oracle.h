@@ -57,6 +57,38 @@ typedef struct {
   uint16_t best_move; /* the in-check rule's reply (Stockfish encoding)     */
 } or_eval;
 
+/* Field-for-field mirror of gn_eval_params (include/gpu_nnue.h, which states what each
+ * field does): the constants of the selection rules, the Eval::evaluate epilogue and
+ * UCIEngine::to_cp.  The defaults are the values this oracle always used (Stockfish 17.1,
+ * recalled, parity unpinned). */
+typedef struct {
+  int32_t small_net_threshold;  /* 962 */
+  int32_t psqt_weight;          /* 125 */
+  int32_t positional_weight;    /* 131 */
+  int32_t reeval_threshold;     /* 236 */
+  int32_t complexity_div_small; /* 18000 */
+  int32_t complexity_div_big;   /* 18000 */
+  int32_t material_pawn_small;  /* 535 */
+  int32_t material_pawn_big;    /* 535 */
+  int32_t material_base;        /* 77777 */
+  int32_t rule50_div;           /* 212 */
+  int32_t value_clamp;          /* 31506 */
+  int32_t piece_value[5];       /* 208 781 825 1276 2538 (P N B R Q) */
+  double wdl_a[4];              /* -37.45051876 121.19101539 -132.78783573 420.70576692 */
+  int32_t wdl_material_min;     /* 17 */
+  int32_t wdl_material_max;     /* 78 */
+  int32_t wdl_material_anchor;  /* 58 */
+  int32_t wdl_piece_weight[5];  /* 1 3 3 5 9 */
+} or_eval_params;
+
+/* Replace the constants every evaluation below reads (NULL: back to the defaults).  Returns 0,
+ * or -1 (nothing changed) for a zero divisor.  The setting is PROCESS-WIDE and unsynchronised:
+ * call it only between evaluation calls, never while or_eval_fens / or_expand_eval_batch
+ * threads (or any other thread's evaluation) run.  Values that make C division undefined
+ * (a divisor of -1 under a wrapped INT_MIN numerator) are the caller's to avoid. */
+int or_set_eval_params(const or_eval_params *params);
+void or_get_eval_params(or_eval_params *out);
+
 typedef struct or_net or_net;
 
 /* Load a .nnue file (Stockfish format).  Returns 0 on success, negative on error

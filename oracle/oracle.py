@@ -7,6 +7,7 @@ status (perft pinned by public known answers; NNUE "parity unpinned").
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -41,6 +42,16 @@ class OrTrace(C.Structure):
 TRACE_DTYPE = np.dtype([("bucket", "<i4"), ("fc0", "<i4", 16), ("in1", "<i4", 32), ("sum1", "<i4", 32),
                         ("fc1", "<i4", 32), ("fc2", "<i4"), ("fwd", "<i4")])
 assert TRACE_DTYPE.itemsize == C.sizeof(OrTrace)
+
+
+class OrEvalParams(C.Structure):
+    """or_eval_params (oracle.h): the mirror of gn_eval_params / fishnet_amd.gpu_nnue.EvalParams."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "small_net_threshold", "psqt_weight", "positional_weight", "reeval_threshold",
+        "complexity_div_small", "complexity_div_big", "material_pawn_small", "material_pawn_big",
+        "material_base", "rule50_div", "value_clamp")] + [
+        ("piece_value", C.c_int32 * 5), ("wdl_a", C.c_double * 4), ("wdl_material_min", C.c_int32),
+        ("wdl_material_max", C.c_int32), ("wdl_material_anchor", C.c_int32), ("wdl_piece_weight", C.c_int32 * 5)]
 
 
 def _tup(e):
@@ -92,8 +103,39 @@ def lib():
         L.or_expand_eval_inc.argtypes = L.or_expand_eval.argtypes
         L.or_expand_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_size_t, C.c_int,
                                            C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.or_set_eval_params.argtypes = [C.POINTER(OrEvalParams)]
+        L.or_get_eval_params.argtypes = [C.POINTER(OrEvalParams)]
+        L.or_get_eval_params.restype = None
         _lib = L
     return _lib
+
+
+def eval_params() -> OrEvalParams:
+    """The constants the oracle evaluates with now."""
+    p = OrEvalParams()
+    lib().or_get_eval_params(C.byref(p))
+    return p
+
+
+def set_eval_params(p):
+    """Process-wide, between evaluation calls only (oracle.h); None restores the defaults.  `p` may be
+    an OrEvalParams or any ctypes structure of the same layout (gpu_nnue.EvalParams)."""
+    if p is not None:
+        if C.sizeof(p) != C.sizeof(OrEvalParams):
+            raise ValueError("not an eval params structure")
+        p = OrEvalParams.from_buffer_copy(bytes(p))
+    if lib().or_set_eval_params(None if p is None else C.byref(p)) != 0:
+        raise ValueError("zero divisor in eval params")
+
+
+@contextlib.contextmanager
+def eval_params_set(p):
+    """with eval_params_set(p): ... -- evaluate under p; the defaults are restored on exit."""
+    set_eval_params(p)
+    try:
+        yield
+    finally:
+        set_eval_params(None)
 
 
 class Net:

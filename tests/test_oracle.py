@@ -213,7 +213,8 @@ def test_incremental_oracle_equals_refresh(oracle_lib, stress):
 def test_oracle_under_sanitizers(oracle_lib, tmp_path):
     """The oracle built with AddressSanitizer + UBSan (oracle/Makefile `sanitize`, a driver
     executable) over the hand-picked edge FENs plus a bad one: no sanitizer report, refresh
-    and incremental expansion equal, and the same numbers as the regular build."""
+    and incremental expansion equal, and the same numbers as the regular build, also under one
+    non-default set of eval params."""
     import shutil
     import subprocess
     from fishnet_amd import synthnet
@@ -248,6 +249,14 @@ def test_oracle_under_sanitizers(oracle_lib, tmp_path):
         assert (n, s) == (len(kids), int(kids["final_v"].astype(np.int64).sum())), fen
         assert p2 == oracle_lib.perft(fen, 2), fen
     assert lines[len(fens) - 1] == "bad"
+    # the same build under non-default eval params (sanitize_main.c PARAMS): the regular build's numbers
+    import eval_param_sets as S
+    extra = [ln.split() for ln in lines[len(fens):] if ln]
+    assert len(extra) == 6 and all(x[0] == "params" for x in extra)
+    with oracle_lib.eval_params_set(S.make(oracle_lib, S.SANITIZE_SET)):
+        for x in extra:
+            e = [oracle_lib.eval_fen(big, small, fens[int(x[1])], m) for m in (0, 1, 2)]
+            assert [int(v) for v in x[2:]] == [v for r in e for v in (r[2], r[3], r[5])], fens[int(x[1])]
 
 
 # ---- the score rule (include/gpu_nnue.h at gn_eval; tests/golden/score_fens.json) -------
