@@ -342,6 +342,8 @@ struct Dev {
   hipEvent_t cev[2] = {nullptr, nullptr};
   DevBuf<gn_eval> po2[2], co2[2];
   DevBuf<gn_child> cc2[2]; // co2 packed as the host's 12-B child records (ABI v4)
+  DevBuf<gn_line> ln2[2];  // or ranked: the chunk's lines (gn_evaluate_games_lines)
+  hipEvent_t rev[2] = {nullptr, nullptr}; // around a chunk's rank_children_kernel (GN_STAT_RANK_NS)
   DevBuf<uint16_t> mv2[2];
   DevBuf<gn_board> roots, rboards, par;
   DevBuf<uint64_t> moff;
@@ -349,7 +351,7 @@ struct Dev {
   DevBuf<int32_t> rstatus;
   DevBuf<uint32_t> gidx;
   // stage times of the last host-buffer call on this device (GN_STAT_HOST_*), ms
-  double t_upload = 0, t_replay = 0, t_compute = 0, t_download = 0, t_tail = 0;
+  double t_upload = 0, t_replay = 0, t_compute = 0, t_download = 0, t_tail = 0, t_rank = 0;
   // the drop-in's small-batch graphs (FastBatch): two per size class (128 << k positions) and mode,
   // so that a second call's launch queues on the stream behind a first one in flight
   std::unique_ptr<FastBatch> fast[6][3][2];
@@ -559,7 +561,8 @@ static void destroy(gn_ctx *ctx) {
       for (auto &pair : row)
         for (auto &f : pair) f.reset();
     for (int i = 0; i < 2; ++i) {
-      d.po2[i].release(), d.co2[i].release(), d.cc2[i].release(), d.mv2[i].release();
+      d.po2[i].release(), d.co2[i].release(), d.cc2[i].release(), d.mv2[i].release(), d.ln2[i].release();
+      if (d.rev[i]) (void)hipEventDestroy(d.rev[i]);
       if (d.cev[i]) (void)hipEventDestroy(d.cev[i]);
     }
     d.roots.release(), d.rboards.release(), d.par.release(), d.moff.release(), d.codes.release();
@@ -618,6 +621,7 @@ static int create(const uint8_t *big, size_t big_len, const uint8_t *small, size
     HIP_TRY(hipEventCreateWithFlags(&d.ev_streamed, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&d.ev_planned, hipEventDisableTiming));
     for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&d.cev[i], hipEventDisableTiming));
+    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&d.rev[i]));
 #ifdef GN_AB_AUX_STREAMS // A/B only: two extra streams, as the removed range pipeline had
     {
       hipStream_t x[2];
@@ -1437,7 +1441,7 @@ static int run_shards(gn_ctx *ctx, const std::vector<size_t> &b, F &&f) {
 }
 
 static void reset_host_stats(gn_ctx *ctx) {
-  for (auto &dp : ctx->devs) dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = 0;
+  for (auto &dp : ctx->devs) dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = 0;
 }
 
 // Chunk bounds of a shard's m parents: cut only where `starts` allows (the first parent of each
@@ -1611,10 +1615,11 @@ static int run_expansions(gn_ctx *ctx, Dev &d, int mode, size_t count, size_t la
 
 // Pass 2 of a shard (see above).  off: the shard's child offsets from pass 1; results to
 // parent_out[0, m) (optional), child_moves / child_out[0, off[m]) (the caller's arrays at this
-// shard's base).
+// shard's base).  n_lines > 0 (gn_evaluate_games_lines): no child reaches the host; each chunk's
+// children are ranked on the device and lines[0, m * n_lines) receives n_lines lines per parent.
 static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m, int mode,
                             const std::vector<uint64_t> &off, const std::vector<size_t> &chunks, gn_eval *parent_out,
-                            uint16_t *child_moves, gn_child *child_out) {
+                            uint16_t *child_moves, gn_child *child_out, int n_lines = 0, gn_line *lines = nullptr) {
   hipStream_t s = d.stream;
   size_t maxp = 1, maxc = 1;
   for (size_t c = 0; c + 1 < chunks.size(); ++c)
@@ -1623,7 +1628,8 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
   for (int k = 0; k < 2; ++k) {
     HIP_TRY(d.po2[k].ensure(maxp));
     HIP_TRY(d.co2[k].ensure(maxc));
-    HIP_TRY(d.cc2[k].ensure(maxc));
+    if (n_lines) HIP_TRY(d.ln2[k].ensure(maxp * (size_t)n_lines));
+    else HIP_TRY(d.cc2[k].ensure(maxc));
     HIP_TRY(d.mv2[k].ensure(maxc));
   }
   int drc[2] = {GN_OK, GN_OK};
@@ -1651,9 +1657,12 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
       const auto t1 = Clock::now();
       hipError_t e = hipSetDevice(d.id);
       if (e == hipSuccess) e = hipStreamWaitEvent(d.copy, d.cev[k], 0);
-      if (e == hipSuccess && t)
+      if (e == hipSuccess && n_lines)
+        e = hipMemcpyAsync(lines + pa * (size_t)n_lines, d.ln2[k].p, mp * (size_t)n_lines * sizeof(gn_line),
+                           hipMemcpyDeviceToHost, d.copy);
+      if (e == hipSuccess && t && !n_lines)
         e = hipMemcpyAsync(child_out + cb, d.cc2[k].p, t * sizeof(gn_child), hipMemcpyDeviceToHost, d.copy);
-      if (e == hipSuccess && t)
+      if (e == hipSuccess && t && !n_lines)
         e = hipMemcpyAsync(child_moves + cb, d.mv2[k].p, t * sizeof(uint16_t), hipMemcpyDeviceToHost, d.copy);
       if (e == hipSuccess && parent_out)
         e = hipMemcpyAsync(parent_out + pa, d.po2[k].p, mp * sizeof(gn_eval), hipMemcpyDeviceToHost, d.copy);
@@ -1682,9 +1691,24 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
         const size_t pa = chunks[c], mp = chunks[c + 1] - pa;
         const uint64_t cb = off[pa], tc = off[chunks[c + 1]] - cb;
         if (t != tc) return fail(GN_E_HIP, "child count changed between passes (%zu != %zu)", t, (size_t)tc);
-        HIP_TRY(launch_pack_children(d.co2[k].p, t, d.cc2[k].p, s));
+        if (n_lines) {
+          // (d.cur's offsets and unpacked parents are this chunk's: the front that overwrites the
+          // set is queued after the synchronisation below)
+          HIP_TRY(hipEventRecord(d.rev[0], s));
+          HIP_TRY(launch_rank_children(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P, d.tables,
+                                       n_lines, d.ln2[k].p, s));
+          HIP_TRY(hipEventRecord(d.rev[1], s));
+        } else {
+          HIP_TRY(launch_pack_children(d.co2[k].p, t, d.cc2[k].p, s));
+        }
         int r = check_plan(d, s); // synchronises the stream: chunk c is computed
         if (r) return r;
+        if (n_lines) {
+          HIP_TRY(hipStreamSynchronize(s)); // (check_plan returns at once when nothing ran planned)
+          float ms = 0;
+          HIP_TRY(hipEventElapsedTime(&ms, d.rev[0], d.rev[1]));
+          d.t_rank += ms;
+        }
         d.t_compute += ms_since(t0), t0 = Clock::now();
         HIP_TRY(hipEventRecord(d.cev[k], s));
         drain_chunk(k, pa, mp, t, cb);
@@ -1872,12 +1896,15 @@ int gn_replay_game(const gn_game *game, gn_board *positions, uint8_t *skipped, u
   }
 }
 
-int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int with_children,
-                      uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out, size_t position_cap,
-                      uint32_t *child_offsets, uint16_t *child_moves, gn_child *child_out, size_t child_cap) {
+// gn_evaluate_games, and (n_lines > 0) gn_evaluate_games_lines: the expansion with children,
+// whose chunks are ranked on the device instead of downloaded (no child array, no child capacity).
+static int evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int with_children,
+                          uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out, size_t position_cap,
+                          uint32_t *child_offsets, uint16_t *child_moves, gn_child *child_out, size_t child_cap,
+                          int n_lines, gn_line *lines) {
   if (!slot(ctx, 0)) return fail(GN_E_INVALID, "bad context");
   if (n_games && (!games || !position_offsets || !game_status)) return fail(GN_E_INVALID, "NULL argument");
-  if (with_children && !child_offsets) return fail(GN_E_INVALID, "child_offsets is NULL");
+  if (with_children && !n_lines && !child_offsets) return fail(GN_E_INVALID, "child_offsets is NULL");
   if (mode < GN_MODE_FULL || mode > GN_MODE_SMALL) return fail(GN_E_INVALID, "bad mode %d", mode);
   try {
     const auto T0 = Clock::now();
@@ -1964,6 +1991,7 @@ int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mod
     position_offsets[n_games] = (uint32_t)total;
     if (total > position_cap) return fail(GN_E_CAPACITY, "%zu positions exceed capacity %zu", (size_t)total, position_cap);
     if (total && !position_out) return fail(GN_E_INVALID, "position_out is NULL");
+    if (total && n_lines && !lines) return fail(GN_E_INVALID, "lines is NULL");
     // The evaluated positions of each device.  Fast path (the common case): every game of the
     // device replayed and none has a skipped position, so its positions are the replay's boards
     // as they lie (rboards: game j's position p at moff[j] + j + p) and one contiguous run of
@@ -2012,6 +2040,8 @@ int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mod
     // phase B: (slow path) the evaluated positions gathered into contiguous parents; evaluated
     // (no children) or counted (pass 1 of the expansion)
     std::vector<std::vector<gn_eval>> res(nd);
+    std::vector<std::vector<gn_line>> lres(nd); // (slow path) the evaluated positions' lines
+    const size_t K = (size_t)n_lines;
     std::vector<std::vector<uint64_t>> off(nd);
     std::vector<size_t> db(nd + 1);
     for (size_t k = 0; k <= nd; ++k) db[k] = k; // one "item" per device: run_shards' shard k = device k
@@ -2034,6 +2064,7 @@ int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mod
         HIP_TRY(hipStreamSynchronize(s));
         d.t_upload += ms_since(t0);
         res[k].resize(m);
+        lres[k].resize(m * K);
       }
       if (with_children) return count_shard(d, parents_of(k), m, off[k]);
       const auto t1 = Clock::now();
@@ -2053,29 +2084,31 @@ int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mod
       std::vector<uint64_t> cb(nd + 1, 0);
       for (size_t k = 0; k < nd; ++k) cb[k + 1] = cb[k] + (has(k) ? off[k].back() : 0);
       const uint64_t ctot = cb[nd];
-      if (ctot > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "children exceed 32-bit offsets");
-      // child offsets over all positions (skipped ones: no children, the next position's offset)
-      const bool all_fast = std::all_of(fast.begin(), fast.end(), [](uint8_t f) { return f != 0; });
-      if (!all_fast)
-        for (size_t g = 0; g < n_games; ++g)
-          for (uint32_t p = 0; p < npos[g]; ++p) child_offsets[position_offsets[g] + p] = 0xFFFFFFFFu;
-      for (size_t k = 0; k < nd; ++k) {
-        if (!has(k)) continue;
-        if (fast[k])
-          for (size_t e = 0; e < mcount[k]; ++e) child_offsets[p0[k] + e] = (uint32_t)(cb[k] + off[k][e]);
-        else
-          for (size_t e = 0; e < where[k].size(); ++e) child_offsets[where[k][e]] = (uint32_t)(cb[k] + off[k][e]);
-      }
-      if (!all_fast) {
-        uint32_t next = (uint32_t)ctot;
-        for (size_t at = total; at-- > 0;) {
-          if (child_offsets[at] == 0xFFFFFFFFu) child_offsets[at] = next;
-          else next = child_offsets[at];
+      if (!n_lines) { // (the lines call returns no children: no child offsets, no child capacity)
+        if (ctot > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "children exceed 32-bit offsets");
+        // child offsets over all positions (skipped ones: no children, the next position's offset)
+        const bool all_fast = std::all_of(fast.begin(), fast.end(), [](uint8_t f) { return f != 0; });
+        if (!all_fast)
+          for (size_t g = 0; g < n_games; ++g)
+            for (uint32_t p = 0; p < npos[g]; ++p) child_offsets[position_offsets[g] + p] = 0xFFFFFFFFu;
+        for (size_t k = 0; k < nd; ++k) {
+          if (!has(k)) continue;
+          if (fast[k])
+            for (size_t e = 0; e < mcount[k]; ++e) child_offsets[p0[k] + e] = (uint32_t)(cb[k] + off[k][e]);
+          else
+            for (size_t e = 0; e < where[k].size(); ++e) child_offsets[where[k][e]] = (uint32_t)(cb[k] + off[k][e]);
         }
+        if (!all_fast) {
+          uint32_t next = (uint32_t)ctot;
+          for (size_t at = total; at-- > 0;) {
+            if (child_offsets[at] == 0xFFFFFFFFu) child_offsets[at] = next;
+            else next = child_offsets[at];
+          }
+        }
+        child_offsets[total] = (uint32_t)ctot;
+        if (ctot > child_cap) return fail(GN_E_CAPACITY, "%zu children exceed capacity %zu", (size_t)ctot, child_cap);
+        if (ctot && (!child_moves || !child_out)) return fail(GN_E_INVALID, "NULL child buffer");
       }
-      child_offsets[total] = (uint32_t)ctot;
-      if (ctot > child_cap) return fail(GN_E_CAPACITY, "%zu children exceed capacity %zu", (size_t)ctot, child_cap);
-      if (ctot && (!child_moves || !child_out)) return fail(GN_E_INVALID, "NULL child buffer");
       // phase C: the expansion pipeline, chunks cut at game starts
       rc = run_shards(ctx, db, [&](size_t k, Dev &d, size_t, size_t) -> int {
         if (!has(k)) return GN_OK;
@@ -2083,6 +2116,10 @@ int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mod
         SeqGuard sg(d, d.stream);
         HIP_TRY(sg.e);
         const size_t m = mcount[k];
+        if (n_lines)
+          return expand_pipelined(ctx, d, parents_of(k), m, mode, off[k], chunk_plan(m, starts[k], ctx->chunk_parents),
+                                  records_of(k), nullptr, nullptr, n_lines,
+                                  fast[k] ? lines + p0[k] * K : lres[k].data());
         return expand_pipelined(ctx, d, parents_of(k), m, mode, off[k], chunk_plan(m, starts[k], ctx->chunk_parents),
                                 records_of(k), child_moves + cb[k], child_out + cb[k]);
       });
@@ -2090,6 +2127,17 @@ int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mod
     }
     for (size_t k = 0; k < nd; ++k)
       for (size_t e = 0; e < where[k].size(); ++e) position_out[where[k][e]] = res[k][e];
+    if (n_lines) { // (slow path) skipped positions: empty lines; the evaluated ones' from lres
+      const bool all_fast = std::all_of(fast.begin(), fast.end(), [](uint8_t f) { return f != 0; });
+      if (!all_fast)
+        for (size_t g = 0; g < n_games; ++g)
+          for (size_t at = position_offsets[g]; at < position_offsets[g + 1]; ++at)
+            if (position_out[at].flags & GN_FLAG_SKIPPED)
+              for (size_t j = 0; j < K; ++j) lines[at * K + j] = gn_line{0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE};
+      for (size_t k = 0; k < nd; ++k)
+        for (size_t e = 0; e < where[k].size(); ++e)
+          std::copy(lres[k].begin() + e * K, lres[k].begin() + (e + 1) * K, lines + (size_t)where[k][e] * K);
+    }
     ctx->t_total = ms_since(T0);
     if (!last_err.empty()) g_err = last_err;
     return GN_OK;
@@ -2098,6 +2146,21 @@ int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mod
   } catch (...) {
     return fail(GN_E_INVALID, "unexpected exception");
   }
+}
+
+int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int with_children,
+                      uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out, size_t position_cap,
+                      uint32_t *child_offsets, uint16_t *child_moves, gn_child *child_out, size_t child_cap) {
+  return evaluate_games(ctx, games, n_games, mode, with_children, position_offsets, game_status, position_out,
+                        position_cap, child_offsets, child_moves, child_out, child_cap, 0, nullptr);
+}
+
+int gn_evaluate_games_lines(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                            uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
+                            size_t position_cap, gn_line *lines) {
+  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  return evaluate_games(ctx, games, n_games, mode, 1, position_offsets, game_status, position_out, position_cap,
+                        nullptr, nullptr, nullptr, 0, n_lines, lines);
 }
 
 int gn_partition(const uint32_t *weights, size_t n_items, int n_shards, size_t *bounds) {
@@ -2562,6 +2625,22 @@ int gn_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, si
 // every grandchild is incremental from its parent's accumulator.  The children are
 // evaluated again at level 2 (as parents); those results must equal level 1's and are
 // compared on the device (GN_E_HIP if not: an internal consistency check).
+int gn_rank_children_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                            const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out, int n_lines,
+                            gn_line *d_lines, void *stream) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
+  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  // (d_moves / d_child_out may be NULL when no parent has a child: they are then never read)
+  if (n && (!d_parents || !d_offsets || !d_lines)) return fail(GN_E_INVALID, "NULL buffer");
+  std::lock_guard<std::mutex> lk(d->mu);
+  HIP_TRY(hipSetDevice(d->id));
+  SeqGuard sg(*d, stream ? (hipStream_t)stream : d->stream);
+  HIP_TRY(sg.e);
+  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables, n_lines, d_lines, sg.s));
+  return GN_OK;
+}
+
 int gn_expand2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, int mode,
                       gn_eval *d_parent_out, uint32_t *d_offsets, gn_board *d_children, uint16_t *d_moves,
                       gn_eval *d_child_out, size_t cap, uint32_t *d_goffsets, uint16_t *d_gmoves,
@@ -2870,6 +2949,7 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
   case GN_STAT_HOST_REPLAY_NS:
   case GN_STAT_HOST_COMPUTE_NS:
   case GN_STAT_HOST_DOWNLOAD_NS:
+  case GN_STAT_RANK_NS:
   case GN_STAT_HOST_TAIL_NS: { // the last host-buffer call, max over devices
     double m = 0;
     for (auto &dp : ctx->devs) {
@@ -2878,6 +2958,7 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
                       : option == GN_STAT_HOST_REPLAY_NS  ? d.t_replay
                       : option == GN_STAT_HOST_COMPUTE_NS ? d.t_compute
                       : option == GN_STAT_HOST_DOWNLOAD_NS ? d.t_download
+                      : option == GN_STAT_RANK_NS          ? d.t_rank
                                                            : d.t_tail);
     }
     *value = (int64_t)(m * 1e6);

@@ -248,6 +248,16 @@ hipError_t launch_replay_games(const gn_board *roots, size_t ng, const uint64_t 
 hipError_t launch_gather_boards(const gn_board *src, const uint32_t *idx, size_t n, gn_board *dst, hipStream_t s);
 // gn_eval -> gn_child (ABI v4 child records for the host-buffer calls)
 hipError_t launch_pack_children(const gn_eval *in, size_t n, gn_child *out, hipStream_t s);
+// Ranked lines (include/gpu_nnue.h gn_line): lines[i * K + k] = line k + 1 of parent i, from its
+// children [offsets[i], offsets[i + 1]) (moves, records rec of one expansion), 1 <= K <= GN_MAX_LINES.
+// The parents as write_children unpacked them with the pipeline's 64-bit offsets (an entry is
+// read only where the parent has children), or packed with the C-ABI's 32-bit offsets.
+hipError_t launch_rank_children(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
+                                const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
+                                gn_line *lines, hipStream_t s);
+hipError_t launch_rank_children(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
+                                const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
+                                gn_line *lines, hipStream_t s);
 // narrowing copy of offsets for the C-ABI
 hipError_t launch_offsets_u32(const uint64_t *in, size_t n, uint32_t *out, hipStream_t s);
 // exclusive scan of n + 1 counts (counts[n] must be 0); temp grows on demand

@@ -1037,6 +1037,113 @@ hipError_t launch_pack_children(const gn_eval *in, size_t n, gn_child *out, hipS
   return hipGetLastError();
 }
 
+// ---- ranked lines per position (MultiPV; include/gpu_nnue.h gn_line) ---------------------
+// A segmented top-K over an expansion's child records: a group of GN_RANK_WIDTH lanes per
+// parent (64: a wave; 32: two parents per wave, segments averaging ~31 children), a lane per
+// child, the group looping over a segment longer than itself.  Each lane makes its child
+// (do_move from the parent the group holds) and asks any_legal, which stops at the first legal
+// move: needed for every child, a stalemating move not being a check.  The lane's line is one
+// sortable key, (value + 32768) << 18 | (0xFFFF - move) << 2 | no-moves << 1 | in-check: larger
+// value first, then the smaller move; the two flag bits ride below the move, where they cannot
+// change the order (a parent's moves are distinct).  0 is no line: value >= -32000.
+// K rounds of a cross-lane maximum (xor butterfly) over the lanes' keys and the running top K
+// (lane k's `top`, from the segment's earlier iterations) give the new top K, round k's winner
+// to lane k, the winner retiring; lanes 0..K-1 then write the parent's K lines, 12 B each, as
+// one contiguous store.
+#ifndef GN_RANK_WIDTH
+#define GN_RANK_WIDTH 32
+#endif
+static_assert(GN_RANK_WIDTH == 32 || GN_RANK_WIDTH == 64, "a parent per half wave or per wave");
+constexpr int RANK_WG = 256;
+
+__device__ __forceinline__ uint64_t group_max(uint64_t v) {
+#pragma unroll
+  for (int o = GN_RANK_WIDTH / 2; o; o >>= 1) {
+    const uint64_t w = __shfl_xor(v, o, GN_RANK_WIDTH);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+__device__ __forceinline__ bool rank_parent(const Board &src, Board &B) { B = src; return true; }
+__device__ __forceinline__ bool rank_parent(const gn_board &src, Board &B) { return unpack(src, B); }
+
+template <class Parent, class Off>
+__global__ void __launch_bounds__(RANK_WG)
+    rank_children_kernel(const Parent *__restrict__ parents, size_t n, const Off *__restrict__ offsets,
+                         const uint16_t *__restrict__ moves, const gn_eval *__restrict__ rec, gn_eval_params P,
+                         const Tables *__restrict__ tables, int K, gn_line *__restrict__ lines) {
+  __shared__ Tables T;
+  load_tables(T, tables);
+  constexpr int W = GN_RANK_WIDTH;
+  const int lane = threadIdx.x & (W - 1);
+  // a bounded grid striding over the parents (the 4 KiB table load once per workgroup)
+  const size_t stride = (size_t)gridDim.x * (RANK_WG / W);
+  for (size_t p = (size_t)blockIdx.x * (RANK_WG / W) + threadIdx.x / W; p < n; p += stride) {
+    const uint64_t c0 = offsets[p], c1 = offsets[p + 1];
+    uint64_t top = 0; // lanes 0..K-1: the running top K (0: none yet)
+    Board B;
+    // (a parent without children -- bad, mated, stalemated, or skipped by the caller -- is never
+    // unpacked or read as a Board: its unpacked entry is not written)
+    const bool ok = c1 > c0 && rank_parent(parents[p], B);
+    for (uint64_t c = c0; ok && c < c1; c += W) {
+      uint64_t key = 0;
+      if (c + lane < c1) {
+        const uint32_t mv = moves[c + lane];
+        const gn_eval r = rec[c + lane];
+        const Board C = do_move(B, (uint16_t)mv, nullptr);
+        const uint32_t check = (r.flags & GN_FLAG_IN_CHECK) ? 1u : 0u;
+        const uint32_t none = any_legal(C, T) ? 0u : 1u;
+        const int32_t v = negate_ply(none ? (check ? -VALUE_MATE : 0) : r.final_v);
+        key = (uint64_t)(uint32_t)(v + 32768) << 18 | (uint64_t)(0xFFFFu - mv) << 2 | none << 1 | check;
+      }
+      uint64_t next = 0;
+      for (int k = 0; k < K; ++k) {
+        const uint64_t mine = key > top ? key : top;
+        const uint64_t m = group_max(mine);
+        if (!m) break; // (uniform in the group) fewer than K lines so far
+        if (key == m) key = 0;
+        if (top == m) top = 0;
+        if (lane == k) next = m;
+      }
+      top = next;
+    }
+    if (lane < K) {
+      gn_line l = {0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE};
+      if (top) {
+        uint32_t fl = ((top & 1) ? GN_FLAG_IN_CHECK : 0u) | ((top & 2) ? GN_FLAG_NO_MOVES : 0u);
+        l.value = (int32_t)(top >> 18) - 32768;
+        l.move = (uint16_t)(0xFFFFu - (uint32_t)((top >> 2) & 0xFFFFu));
+        l.score = rule_score(l.value, wdl_material(B, P), P, fl);
+        l.flags = (uint16_t)fl;
+      }
+      lines[p * (size_t)K + lane] = l;
+    }
+  }
+}
+
+template <class Parent, class Off>
+static hipError_t rank_children_t(const Parent *parents, size_t n, const Off *offsets, const uint16_t *moves,
+                                  const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
+                                  gn_line *lines, hipStream_t s) {
+  if (!n) return hipSuccess;
+  constexpr size_t per_wg = RANK_WG / GN_RANK_WIDTH, max_blocks = 8192;
+  const size_t blocks = std::min<size_t>((n + per_wg - 1) / per_wg, max_blocks);
+  hipLaunchKernelGGL((rank_children_kernel<Parent, Off>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets, moves,
+                     rec, P, tables, K, lines);
+  return hipGetLastError();
+}
+hipError_t launch_rank_children(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
+                                const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
+                                gn_line *lines, hipStream_t s) {
+  return rank_children_t(unpacked, n, offsets, moves, rec, P, tables, K, lines, s);
+}
+hipError_t launch_rank_children(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
+                                const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
+                                gn_line *lines, hipStream_t s) {
+  return rank_children_t(parents, n, offsets, moves, rec, P, tables, K, lines, s);
+}
+
 hipError_t launch_classify(const gn_board *boards, size_t n, const gn_eval_params &P, uint8_t *need_small,
                            uint8_t *need_big, hipStream_t s) {
   if (!n) return hipSuccess;

@@ -35,8 +35,11 @@ BOARD_DTYPE = np.dtype([("occ", "<u8"), ("pc", "u1", (16,)), ("stm_ep", "u1"), (
 CHILD_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("cp_flags", "<i4")])
 # ... and decoded (decode_children / children_from_evals), the form the tests compare
 CHILD_VIEW_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("final_cp", "<i4"), ("flags", "<u2")])
+# gn_line: one ranked line of a position (MultiPV; gpu_nnue.h at gn_line), 12 bytes
+LINE_DTYPE = np.dtype([("value", "<i4"), ("score", "<i4"), ("move", "<u2"), ("flags", "<u2")])
+MAX_LINES = 8
 EVAL_SIZE, BOARD_SIZE, CHILD_SIZE = EVAL_DTYPE.itemsize, BOARD_DTYPE.itemsize, CHILD_DTYPE.itemsize
-assert EVAL_SIZE == 24 and BOARD_SIZE == 32 and CHILD_SIZE == 12
+assert EVAL_SIZE == 24 and BOARD_SIZE == 32 and CHILD_SIZE == 12 and LINE_DTYPE.itemsize == 12
 ABI_VERSION = 4
 
 EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_abi_version",
@@ -48,11 +51,12 @@ EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_
            "gn_time_expand_device", "gn_random_games_device", "gn_replay_game", "gn_evaluate_games",
            "gn_net_sha256", "gn_partition", "gn_checksum_device",
            "gn_boards_to_fens", "gn_load_net_archive", "gn_archive_read", "gn_expand2_device",
-           "gn_random_games_uci"]
+           "gn_random_games_uci", "gn_rank_children_device", "gn_evaluate_games_lines"]
 OPT_INCREMENTAL_CHILDREN, OPT_XCD_SWIZZLE, OPT_KING_SORT, OPT_CHAIN, OPT_KING_CACHE = 1, 2, 3, 4, 5
 OPT_CHUNK_PARENTS, OPT_COALESCE, OPT_STREAM_SLICES, OPT_FAST_BATCH, OPT_EXPAND_PIPELINE = 6, 7, 8, 9, 10
 STAT_PLAN_NS, STAT_STREAM_NS, STAT_SCRATCH_PADS, STAT_FINISH_NS = 101, 102, 103, 104
 STAT_BATCH_LAUNCHES, STAT_BATCH_CALLS, STAT_FAST_BATCHES, STAT_FAST_FALLBACKS = 117, 118, 119, 120
+STAT_RANK_NS = 121
 HOST_STAGES = {"parse": 110, "upload": 111, "replay": 112, "compute": 113, "download": 114, "tail": 115, "total": 116}
 EXPAND_STAGES = ["count_scan", "total_readback", "write_children", "classify", "small_net", "big_net", "finalize",
                  "score"]
@@ -167,6 +171,8 @@ def lib():
         "gn_expand2_device": [vp, i32, vp, sz, i32, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, C.POINTER(sz),
                               C.POINTER(sz), vp],
         "gn_random_games_uci": [C.c_uint64, sz, sz, i32, vp, sz],
+        "gn_rank_children_device": [vp, i32, vp, sz, vp, vp, vp, i32, vp, vp],
+        "gn_evaluate_games_lines": [vp, vp, sz, i32, i32, vp, vp, vp, sz, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -465,6 +471,28 @@ class GpuNnue:
             return offs, status, pos[:p], coffs[:p + 1], cmv[:t], cev[:t], (pcap, ccap)
         raise GnError(E_CAPACITY, "capacity retry failed")
 
+    def evaluate_games_lines(self, games, n_lines, mode=MODE_FULL, cap=None):
+        """gn_evaluate_games_lines over [(root_fen, moves, skip)]: (position_offsets, game_status,
+        positions[EVAL_DTYPE], lines[positions, n_lines] as LINE_DTYPE).  cap: the position
+        capacity (None: sized by a first call, as the C caller's GN_E_CAPACITY retry)."""
+        ng = len(games)
+        arr, _keep = _games_array(games)
+        offs = np.zeros(ng + 1, dtype=np.uint32)
+        status = np.zeros(max(ng, 1), dtype=np.int32)
+        pcap = 0 if cap is None else cap
+        for _ in range(2):
+            pos = np.zeros(max(pcap, 1), dtype=EVAL_DTYPE)
+            lines = np.zeros((max(pcap, 1), max(n_lines, 1)), dtype=LINE_DTYPE)
+            rc = lib().gn_evaluate_games_lines(self.h, arr, ng, mode, n_lines, offs.ctypes.data, status.ctypes.data,
+                                               pos.ctypes.data, pcap, lines.ctypes.data)
+            if rc == E_CAPACITY and cap is None and int(offs[-1]) > pcap:
+                pcap = int(offs[-1])
+                continue
+            _check(rc)
+            p = int(offs[-1])
+            return offs, status, pos[:p], lines[:p]
+        raise GnError(E_CAPACITY, "capacity retry failed")
+
     def host_stages(self):
         """Stage times (ms) of the last gn_evaluate_games / gn_expand_and_evaluate (GN_STAT_HOST_*)."""
         return {k: self.get_option(v) / 1e6 for k, v in HOST_STAGES.items()}
@@ -533,6 +561,13 @@ class GpuNnue:
                                       d_children.ptr, d_moves.ptr, d_child_out.ptr, cap, C.byref(total),
                                       stream))
         return total.value
+
+    def rank_children_device(self, d_parents, n, d_offsets, d_moves, d_child_out, n_lines, d_lines,
+                             stream=None, slot=0):
+        """gn_rank_children_device: d_lines[n * n_lines] (LINE_DTYPE) from a preceding expand_device's
+        offsets, moves and child records.  Asynchronous on the stream."""
+        _check(lib().gn_rank_children_device(self.h, slot, d_parents.ptr, n, d_offsets.ptr, d_moves.ptr,
+                                             d_child_out.ptr, n_lines, d_lines.ptr, stream))
 
     def expand2_device(self, d_parents, n, mode, out, stream=None, slot=0):
         """Depth 2 (gn_expand2_device).  out: DeviceBuffers po, off, ch (child boards), mv, co,

@@ -169,6 +169,9 @@ extern "C" {
 #define GN_STAT_HOST_TAIL_NS 115      /* the downloads still running after the last chunk
                                          computed (not overlapped)                        */
 #define GN_STAT_HOST_TOTAL_NS 116     /* the whole call                                    */
+#define GN_STAT_RANK_NS 121           /* rank_children_kernel in the last
+                                         gn_evaluate_games_lines, summed over its chunks
+                                         (0 after any other host-buffer call)              */
 #define GN_STAT_BATCH_LAUNCHES 117    /* merged gn_evaluate_batch launches since load ...   */
 #define GN_STAT_BATCH_CALLS 118       /* ... and the calls they served (GN_OPT_COALESCE)    */
 #define GN_STAT_FAST_BATCHES 119      /* evaluations run by the captured small-batch graphs
@@ -238,6 +241,38 @@ typedef struct gn_child {
 } gn_child;
 #define GN_CHILD_FINAL_CP(c) ((int32_t)((uint32_t)(c).cp_flags << 8) >> 8)
 #define GN_CHILD_FLAGS(c) ((uint32_t)(c).cp_flags >> 24)
+
+/* One ranked line of a position (MultiPV): what fishnet's `multipv` asks the engine for
+ * (Work::Analysis in the reference's src/api.rs; src/stockfish.rs sends `setoption name MultiPV`
+ * and fills scores[multipv][depth] / pvs[multipv][depth] of a PositionResponse from the `info`
+ * lines).  gn_rank_children_device and gn_evaluate_games_lines return n_lines of them per
+ * position, 1 <= n_lines <= GN_MAX_LINES.
+ * The rule, for a position p a call evaluates (not skipped, not bad) with at least one legal
+ * move, over every legal move m with child c:
+ *   value(m) = negate_ply(V(c)): negated, mate values one ply further from the mate, where
+ *   V(c) = -VALUE_MATE (-32000) when c has no legal move and is in check (m mates),
+ *   V(c) = 0 when c has no legal move and is not in check (m stalemates),
+ *   V(c) = c's static final_v in the call's mode otherwise -- also when c is in check (the
+ *   values gn_eval documents as "still computed").
+ * This is the score rule above at depth 1, without its recursion into replies that give check.
+ * Lines are ordered by value descending, ties to the smaller 16-bit move encoding (the score
+ * rule's tie rule).  A position with fewer legal moves than n_lines has empty lines after its
+ * last move (value 0, score 0, move 0, flags GN_FLAG_NO_SCORE); a skipped, bad, checkmated or
+ * stalemated position has only empty lines.
+ * Line 1 and gn_eval.score: for a position in check, line 1's score / move / GN_FLAG_MATE equal
+ * that position's gn_eval.score / best_move / GN_FLAG_MATE whenever none of its replies is
+ * itself in check with a legal move; otherwise they may differ, the score rule going one level
+ * deeper at such a reply. */
+#define GN_MAX_LINES 8 /* lichess sends multipv <= 5 */
+typedef struct gn_line {
+  int32_t value;  /* the rule value, p's side-to-move POV, Stockfish units              */
+  int32_t score;  /* rule_score(value, p's win-rate material): cp, or the mate distance
+                     with GN_FLAG_MATE (as gn_eval.score)                                */
+  uint16_t move;  /* Stockfish encoding, castling = king takes rook                      */
+  uint16_t flags; /* GN_FLAG_MATE; GN_FLAG_IN_CHECK: the move gives check;
+                     GN_FLAG_NO_MOVES: the move ends the game (mate or stalemate);
+                     GN_FLAG_NO_SCORE: an empty line                                     */
+} gn_line;
 
 /* Packed position, 32 bytes, the device input format.
  *   occ      occupied squares (bit s = square s, a1 = 0 .. h8 = 63)
@@ -385,6 +420,17 @@ GN_API int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, 
                              size_t position_cap, uint32_t *child_offsets, uint16_t *child_moves,
                              gn_child *child_out, size_t child_cap);
 
+/* gn_evaluate_games with children, except for what it downloads: instead of every legal child,
+ * lines[position * n_lines + k] = line k + 1 of each position (gn_line; position_cap * n_lines
+ * entries), ranked on the device as each chunk of the expansion finishes (rank_children_kernel
+ * where the children would be packed for the host; the drain thread copies positions x n_lines
+ * lines).  Same chunking (GN_OPT_CHUNK_PARENTS), two-slot overlap and sharding; position_offsets,
+ * game_status, position_out and GN_E_CAPACITY for the positions exactly as gn_evaluate_games.
+ * n_lines outside 1..GN_MAX_LINES: GN_E_INVALID.  GN_STAT_RANK_NS: the ranking's time. */
+GN_API int gn_evaluate_games_lines(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                   uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
+                                   size_t position_cap, gn_line *lines);
+
 /* The partitioner the library uses to shard work over the devices of a context and
  * that multi-process callers use to shard over ranks: contiguous ranges of n_items
  * items, bounds[k] = first item of shard k, bounds[n_shards] = n_items; shard k
@@ -445,6 +491,13 @@ GN_API int gn_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_pare
  * nets the row stream's own count (bias, carry and king-cache rows included:
  * GN_OPT_CHAIN, GN_OPT_KING_CACHE), else parent refreshes + child deltas /
  * king-move refreshes; 0 when not incremental. */
+/* Ranks the outputs of a preceding gn_expand_device of the same parents (d_offsets, d_moves,
+ * d_child_out as it wrote them): d_lines[i * n_lines + k] = line k + 1 of parent i (gn_line).
+ * Asynchronous on `stream` (NULL = the context's own), no read-back.  n_lines outside
+ * 1..GN_MAX_LINES: GN_E_INVALID. */
+GN_API int gn_rank_children_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                   const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out,
+                                   int n_lines, gn_line *d_lines, void *stream);
 /* Depth 2 (grandchildren): gn_expand_device, then every child's legal children
  * evaluated incrementally from the child's accumulator (a sibling block refreshes each
  * child from its predecessor through the king cache).  d_goffsets: total + 1 offsets of

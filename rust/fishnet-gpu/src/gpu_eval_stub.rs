@@ -11,13 +11,20 @@
 //! replies (depth 1, the reply as best move and pv), else the static evaluation's `cp`.
 //! This stub only maps those fields; a record without a score (a position the library
 //! refuses) fails the chunk like an engine error, never the queue.
+//!
+//! MultiPV: when the work asks for more than one line (`chunk.work.multipv() > 1`, what
+//! stockfish.rs:263 sends as `setoption name MultiPV`), the positions go through
+//! `GpuNnue::evaluate_lines` and rows 1..=K of `scores` / `pvs` are filled at depth 1 from the
+//! ranked lines (include/gpu_nnue.h at gn_line; the pv is the single move), `best_move` being
+//! line 1's move.  A position without a legal move has no lines and keeps its `mate 0` / `cp 0`
+//! at depth 0.  With multipv = 1 nothing changes.
 use std::{num::NonZeroU8, sync::Arc, time::Duration};
 
 use shakmaty::{fen::Fen, uci::UciMove, CastlingMode, Chess, EnPassantMode, Position as _};
 
 use crate::{
     api::Score,
-    gpu_nnue::{move_to_uci, GpuEval, GpuNnue},
+    gpu_nnue::{move_to_uci, GpuEval, GpuLine, GpuNnue},
     ipc::{Chunk, ChunkFailed, Matrix, Position, PositionResponse},
 };
 use gpu_nnue_sys as sys;
@@ -79,6 +86,17 @@ pub fn score_of(e: &GpuEval) -> Option<Score> {
     }
 }
 
+/// The score of a ranked line, or None for an empty line.
+pub fn line_score(l: &GpuLine) -> Option<Score> {
+    if l.flags & sys::GN_FLAG_NO_SCORE != 0 {
+        None
+    } else if l.flags & sys::GN_FLAG_MATE != 0 {
+        Some(Score::Mate(i64::from(l.score)))
+    } else {
+        Some(Score::Cp(i64::from(l.score)))
+    }
+}
+
 impl GpuEvalStub {
     pub fn new(nnue: Arc<GpuNnue>) -> GpuEvalStub {
         GpuEvalStub { nnue }
@@ -89,6 +107,10 @@ impl GpuEvalStub {
         // an illegal move fails the chunk, as queue.rs:576 fails the batch
         let fens = replay_chunk(&chunk.positions).ok_or(ChunkFailed { batch_id })?;
         let nnue = self.nnue.clone();
+        let k = usize::from(chunk.work.multipv().get()).min(sys::MAX_LINES);
+        if k > 1 {
+            return self.go_lines(chunk, fens, k).await;
+        }
         // N workers call at once through the shared context: the library merges their
         // concurrent calls into one launch (GN_OPT_COALESCE, bench.py secondary.dropin)
         let evals = tokio::task::spawn_blocking(move || nnue.evaluate_batch(&fens))
@@ -112,6 +134,53 @@ impl GpuEvalStub {
                 let best_move: Option<UciMove> = searched.then(|| move_to_uci(e.best_move));
                 if let Some(m) = &best_move {
                     pvs.set(NonZeroU8::MIN, depth, vec![m.clone()]);
+                }
+                Ok(PositionResponse {
+                    work: pos.work,
+                    position_index: pos.position_index,
+                    url: pos.url,
+                    scores,
+                    pvs,
+                    best_move,
+                    depth,
+                    nodes: 1,
+                    time: Duration::ZERO,
+                    nps: None,
+                })
+            })
+            .collect()
+    }
+
+    /// multipv = k > 1: rows 1..=k of scores / pvs at depth 1 from the position's ranked lines.
+    async fn go_lines(&mut self, chunk: Chunk, fens: Vec<Fen>, k: usize) -> Result<Vec<PositionResponse>, ChunkFailed> {
+        let batch_id = chunk.work.id();
+        let nnue = self.nnue.clone();
+        let (evals, lines) = tokio::task::spawn_blocking(move || nnue.evaluate_lines(&fens, k))
+            .await
+            .map_err(|_| ChunkFailed { batch_id })?
+            .map_err(|_| ChunkFailed { batch_id })?;
+        chunk
+            .positions
+            .into_iter()
+            .zip(evals)
+            .zip(lines.chunks(k))
+            .map(|((pos, e), ls)| {
+                let mut scores = Matrix::new();
+                let mut pvs = Matrix::new();
+                let mut best_move: Option<UciMove> = None;
+                let mut depth: u8 = 0;
+                for (row, l) in (1u8..).zip(ls) {
+                    let Some(score) = line_score(l) else { break };
+                    let multipv = NonZeroU8::new(row).expect("rows start at 1");
+                    let m = move_to_uci(l.r#move);
+                    depth = 1;
+                    scores.set(multipv, depth, score);
+                    pvs.set(multipv, depth, vec![m.clone()]);
+                    best_move.get_or_insert(m);
+                }
+                if depth == 0 {
+                    // no legal move (mate 0 / cp 0), as with multipv = 1
+                    scores.set(NonZeroU8::MIN, depth, score_of(&e).ok_or(ChunkFailed { batch_id })?);
                 }
                 Ok(PositionResponse {
                     work: pos.work,

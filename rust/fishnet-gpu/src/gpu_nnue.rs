@@ -21,6 +21,7 @@ use shakmaty::{fen::Fen, uci::UciMove, Role, Square};
 
 pub use sys::gn_child as GpuChild;
 pub use sys::gn_eval as GpuEval;
+pub use sys::gn_line as GpuLine;
 
 pub struct GpuNnue(*mut sys::gn_ctx);
 
@@ -107,6 +108,35 @@ impl GpuNnue {
         // SAFETY: ptrs / out have fens.len() elements and outlive the call.
         check(unsafe { sys::gn_evaluate_batch(self.0, ptrs.as_ptr(), ptrs.len(), out.as_mut_ptr()) })?;
         Ok(out)
+    }
+
+    /// evaluate_batch plus the best `n_lines` moves of every position (MultiPV, 1..=8): the
+    /// records as evaluate_batch returns them and `n_lines` ranked lines per position
+    /// (lines[i * n_lines + k] = line k + 1 of position i; empty lines carry GN_FLAG_NO_SCORE;
+    /// include/gpu_nnue.h at gn_line).  Each FEN goes to gn_evaluate_games_lines as a game without
+    /// moves, so the children are ranked on the GPU and only the lines come back.  A FEN the
+    /// library refuses fails the call, as it would fail the chunk.
+    pub fn evaluate_lines(&self, fens: &[Fen], n_lines: usize) -> Result<(Vec<GpuEval>, Vec<GpuLine>), GpuError> {
+        let owned: Vec<CString> = fens.iter().map(|f| CString::new(f.to_string()).unwrap()).collect();
+        let gs: Vec<sys::gn_game> = owned
+            .iter()
+            .map(|root| sys::gn_game { root_fen: root.as_ptr(), uci_moves: ptr::null(), skip_positions: ptr::null(), n_skip: 0 })
+            .collect();
+        let mut offsets = vec![0u32; fens.len() + 1];
+        let mut status = vec![0i32; fens.len()];
+        let mut evals = vec![GpuEval::default(); fens.len()];
+        let mut lines = vec![GpuLine::default(); fens.len() * n_lines];
+        // SAFETY: a game without moves is one position, so fens.len() positions is the capacity
+        // needed; every buffer has the length the call is told.
+        check(unsafe {
+            sys::gn_evaluate_games_lines(self.0, gs.as_ptr(), gs.len(), sys::GN_MODE_FULL, n_lines as i32,
+                                         offsets.as_mut_ptr(), status.as_mut_ptr(), evals.as_mut_ptr(), fens.len(),
+                                         lines.as_mut_ptr())
+        })?;
+        if let Some(&code) = status.iter().find(|&&s| s != sys::GN_OK) {
+            return Err(last_error(code));
+        }
+        Ok((evals, lines))
     }
 
     /// Whole acquired batches: replay root FEN + UCI moves (skipPositions honoured) and

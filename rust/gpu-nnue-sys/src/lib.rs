@@ -54,6 +54,7 @@ pub const GN_STAT_BATCH_LAUNCHES: c_int = 117;
 pub const GN_STAT_BATCH_CALLS: c_int = 118;
 pub const GN_STAT_FAST_BATCHES: c_int = 119;
 pub const GN_STAT_FAST_FALLBACKS: c_int = 120;
+pub const GN_STAT_RANK_NS: c_int = 121;
 
 // per-position flags
 pub const GN_FLAG_IN_CHECK: u16 = 1;
@@ -101,6 +102,22 @@ impl gn_child {
     pub fn flags(&self) -> u16 {
         ((self.cp_flags as u32) >> 24) as u16
     }
+}
+
+/// The header's GN_MAX_LINES: the most lines per position the ranking calls return.
+pub const MAX_LINES: usize = 8;
+
+/// One ranked line of a position (MultiPV, 12 bytes): the rule value of a legal move, its score
+/// (`cp`, or the mate distance with GN_FLAG_MATE), the move and its flags (GN_FLAG_IN_CHECK: the
+/// move gives check; GN_FLAG_NO_MOVES: it ends the game; GN_FLAG_NO_SCORE: an empty line); see
+/// the header at gn_line.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct gn_line {
+    pub value: i32,
+    pub score: i32,
+    pub r#move: u16,
+    pub flags: u16,
 }
 
 /// Packed position (32 bytes), the device input format.
@@ -186,6 +203,9 @@ extern "C" {
                              with_children: c_int, position_offsets: *mut u32, game_status: *mut i32,
                              position_out: *mut gn_eval, position_cap: usize, child_offsets: *mut u32,
                              child_moves: *mut u16, child_out: *mut gn_child, child_cap: usize) -> c_int;
+    pub fn gn_evaluate_games_lines(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
+                                   n_lines: c_int, position_offsets: *mut u32, game_status: *mut i32,
+                                   position_out: *mut gn_eval, position_cap: usize, lines: *mut gn_line) -> c_int;
     pub fn gn_partition(weights: *const u32, n_items: usize, n_shards: c_int, bounds: *mut usize) -> c_int;
     pub fn gn_perft(ctx: *mut gn_ctx, fen: *const c_char, depth: c_int, nodes: *mut u64) -> c_int;
     pub fn gn_pack_fens(fens: *const *const c_char, n: usize, out: *mut gn_board, ok: *mut u8) -> c_int;
@@ -203,6 +223,9 @@ extern "C" {
                             d_parent_out: *mut gn_eval, d_offsets: *mut u32, d_children: *mut gn_board,
                             d_moves: *mut u16, d_child_out: *mut gn_eval, cap: usize, total: *mut usize,
                             stream: *mut c_void) -> c_int;
+    pub fn gn_rank_children_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                                   d_offsets: *const u32, d_moves: *const u16, d_child_out: *const gn_eval,
+                                   n_lines: c_int, d_lines: *mut gn_line, stream: *mut c_void) -> c_int;
     pub fn gn_expand2_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize, mode: c_int,
                              d_parent_out: *mut gn_eval, d_offsets: *mut u32, d_children: *mut gn_board,
                              d_moves: *mut u16, d_child_out: *mut gn_eval, cap: usize, d_goffsets: *mut u32,
@@ -238,6 +261,7 @@ mod tests {
     fn layouts() {
         assert_eq!(std::mem::size_of::<gn_eval>(), 24);
         assert_eq!(std::mem::size_of::<gn_child>(), 12);
+        assert_eq!(std::mem::size_of::<gn_line>(), 12);
         let c = gn_child { psqt: 0, positional: 0, cp_flags: (0x00FF_FFFEu32 | 65u32 << 24) as i32 };
         assert_eq!((c.final_cp(), c.flags()), (-2, 65));
         assert_eq!(std::mem::size_of::<gn_board>(), 32);
