@@ -194,11 +194,13 @@ GN_HD int piece_nibble(uint64_t lo, uint64_t hi, int k) {
   return (int)(((k < 16 ? lo : hi) >> (4 * (k & 15))) & 15);
 }
 
-// Unpacks and validates a gn_board.  Returns false for anything the device
-// must not touch (bad piece nibble, not exactly one king per side, > 32 pieces,
-// pawns on a back rank, bad en-passant square).  Whether the side not to move
-// is in check is NOT checked here.
-GN_HD bool unpack(const gn_board &p, Board &B) {
+// Reads the fields of a gn_board into B.  Returns false for what a Board cannot hold or a
+// text cannot spell: fewer than 2 or more than 32 pieces, a piece nibble that is no piece, an
+// en-passant field above 64.  Unused nibbles, `reserved` and the low bits of a castle nibble
+// whose bit 3 is clear are not read.  This is NOT the gate for a caller's board (unpack
+// below): alone it serves boards the library made itself (a legal child of a valid parent)
+// and readers that touch no king square (the net selection's material count).
+GN_HD bool unpack_fields(const gn_board &p, Board &B) {
   for (int i = 0; i < 7; ++i) B.byType[i] = 0;
   B.byColor[0] = B.byColor[1] = 0;
   Bitboard occ = p.occ;
@@ -216,8 +218,6 @@ GN_HD bool unpack(const gn_board &p, Board &B) {
     or_color(B, pc >> 3, sqbb(s));
   }
   B.byType[0] = p.occ;
-  ok &= popcnt(B.byType[KING] & B.byColor[WHITE]) == 1 && popcnt(B.byType[KING] & B.byColor[BLACK]) == 1;
-  ok &= (B.byType[PAWN] & 0xFF000000000000FFull) == 0;
   B.stm = p.stm_ep >> 7;
   B.ep = p.stm_ep & 0x7F;
   if (B.ep > SQ_NONE) ok = false;
@@ -229,6 +229,47 @@ GN_HD bool unpack(const gn_board &p, Board &B) {
   B.fullmove = p.fullmove;
   return ok;
 }
+
+// The one gate for a position that did not come from this library's own move generator (a
+// caller's gn_board, a FEN text): the contract at gn_board in include/gpu_nnue.h.  Returns
+// false for a position nothing may be generated from or evaluated: more than 32 pieces, not
+// exactly one king per side, a pawn on a back rank, the side not to move in check (its king
+// could be captured, and every later king_square of that child would be undefined).
+// Otherwise normalises B as Position::set does (host_board.h) and returns true: a castling
+// right survives only with an own rook on that square of the own back rank, the king on that
+// rank and the rook on the slot's side of it; the en-passant square only on the mover's sixth
+// rank, attacked by a pawn of the mover, with an enemy pawn behind it and the square and the
+// one before it empty.  rule50 and fullmove are taken as they are.
+GN_HD bool position_ok(Board &B, const Tables &T) {
+  const Bitboard occ = B.byType[0], pawns = B.byType[PAWN];
+  const Bitboard wk = B.byType[KING] & B.byColor[WHITE], bk = B.byType[KING] & B.byColor[BLACK];
+  const int us = B.stm, them = us ^ 1;
+  const Bitboard ours = color_bb(B, us), theirs = color_bb(B, them);
+  if (popcnt(occ) > 32 || popcnt(wk) != 1 || popcnt(bk) != 1) return false;
+  if ((pawns & 0xFF000000000000FFull) || B.ep > SQ_NONE) return false;
+  if (attackers_to(B, T, lsb(us ? wk : bk), occ) & ours) return false;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = B.castle_rook[i];
+    if (r == SQ_NONE) continue;
+    const int c = i >> 1, back = c ? 7 : 0, ksq = lsb(c ? bk : wk);
+    const bool rook = (B.byType[ROOK] & color_bb(B, c) & sqbb(r)) != 0;
+    const bool side = (i & 1) ? r < ksq : r > ksq;
+    if (!rook || (r >> 3) != back || (ksq >> 3) != back || !side) B.castle_rook[i] = SQ_NONE;
+  }
+  if (B.ep != SQ_NONE) {
+    const int ep = B.ep, up = us == WHITE ? 8 : -8;
+    bool keep = (ep >> 3) == (us == WHITE ? 5 : 2);
+    if (keep)
+      keep = (T.pawn[them][ep] & pawns & ours) != 0 && (pawns & theirs & sqbb(ep - up)) != 0 &&
+             !(occ & (sqbb(ep) | sqbb(ep + up)));
+    if (!keep) B.ep = SQ_NONE;
+  }
+  return true;
+}
+
+// A caller's gn_board: its fields, then the gate.  False: the device must not touch it.
+GN_HD bool unpack(const gn_board &p, Board &B, const Tables &T) { return unpack_fields(p, B) && position_ok(B, T); }
 
 GN_HD void pack(const Board &B, gn_board &p) {
   p.occ = B.byType[0];

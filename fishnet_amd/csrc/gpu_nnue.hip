@@ -814,6 +814,7 @@ struct GenOpts {
   // the planned big-net path reads no child board after this (finalize makes each child from its
   // unpacked parent and move), so library-internal child boards are not written
   bool skip_internal = false;
+  bool trusted = false;    // the parents are the library's own boards (level 2's: level 1's children): no gate
   size_t limit = SIZE_MAX; // more children than this fail the call (GN_E_CAPACITY) before anything is written
 };
 // Child generation into d.cur: counts -> exclusive scan (offsets, n + 1) -> children boards
@@ -836,7 +837,7 @@ static int generate_children(Dev &d, const gn_board *parents, size_t n, gn_board
     HIP_TRY(x.eoff.ensure(n + 1));
     HIP_TRY(hipMemsetAsync(d.ebound.p + n, 0, sizeof(uint64_t), s));
   }
-  HIP_TRY(launch_count_children(parents, n, d.tables, x.counts.p, s, x.planned ? d.ebound.p : nullptr));
+  HIP_TRY(launch_count_children(parents, n, d.tables, x.counts.p, s, x.planned ? d.ebound.p : nullptr, o.trusted));
   HIP_TRY(exclusive_scan_u64(x.counts.p, x.offsets.p, n + 1, x.scan_tmp, x.scan_bytes, s));
   if (x.planned) HIP_TRY(exclusive_scan_u64(d.ebound.p, x.eoff.p, n + 1, x.scan_tmp, x.scan_bytes, s));
   if (o.ev) HIP_TRY(hipEventRecord(o.ev[0], s));
@@ -864,7 +865,7 @@ static int generate_children(Dev &d, const gn_board *parents, size_t n, gn_board
   if (t) {
     HIP_TRY(launch_write_children(parents, n, d.tables, x.offsets.p, 0, t, children, moves, x.owner.p,
                                   o.deltas ? d.deltas.p : nullptr, x.chain_k > 1 ? d.nslot.p : nullptr, x.chain_k,
-                                  o.rows, s, x.unpacked.p));
+                                  o.rows, s, x.unpacked.p, o.trusted));
   }
   if (o.ev) HIP_TRY(hipEventRecord(o.ev[2], s));
   return GN_OK;
@@ -1060,7 +1061,7 @@ static int resolve_scores(gn_ctx *ctx, Dev &d, const gn_board *boards, size_t n,
   HIP_TRY(L.boards.ensure(m));
   HIP_TRY(L.counts.ensure(m + 1));
   HIP_TRY(L.offsets.ensure(m + 1));
-  HIP_TRY(launch_score_gather(boards, L.sel.p, L.pos.p, n, L.idx.p, L.boards.p, s));
+  HIP_TRY(launch_score_gather(boards, L.sel.p, L.pos.p, n, replies ? nullptr : d.tables, L.idx.p, L.boards.p, s));
   if (replies) {
     uint64_t t = 0;
     HIP_TRY(launch_score_replies(L.idx.p, m, d.cur.offsets.p, L.counts.p, L.offsets.p, d.cur.scan_tmp,
@@ -2374,7 +2375,7 @@ int gn_pack_fens(const char *const *fens, size_t n, gn_board *out, uint8_t *ok) 
 int gn_board_to_fen(const gn_board *board, char *buf, size_t buflen) {
   if (!board || !buf) return fail(GN_E_INVALID, "NULL argument");
   Board B;
-  if (!unpack(*board, B)) return fail(GN_E_INVALID, "invalid board");
+  if (!unpack(*board, B, host_tables())) return fail(GN_E_INVALID, "invalid board");
   if (board_to_fen(B, buf, buflen) < 0) return fail(GN_E_CAPACITY, "buffer too small");
   return GN_OK;
 }
@@ -2387,7 +2388,7 @@ int gn_boards_to_fens(const gn_board *boards, size_t n, char *buf, size_t stride
       for (size_t i = lo; i < hi; ++i) {
         Board B;
         char *o = buf + i * stride;
-        if (!unpack(boards[i], B) || board_to_fen(B, o, stride) < 0) o[0] = '\0';
+        if (!unpack(boards[i], B, host_tables()) || board_to_fen(B, o, stride) < 0) o[0] = '\0';
       }
     });
   } catch (...) {
@@ -2689,7 +2690,9 @@ int gn_expand2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, s
     *gtotal = g;
     return g ? fail(GN_E_CAPACITY, "%zu grandchildren exceed capacity %zu", g, gcap) : GN_OK;
   }
-  rc = generate_children(*d, d_children, t, nullptr, d_gmoves, &g, s, gen_opts(ctx, *d, t, mode, gcap));
+  GenOpts g2 = gen_opts(ctx, *d, t, mode, gcap);
+  g2.trusted = true; // level 1's children, written above
+  rc = generate_children(*d, d_children, t, nullptr, d_gmoves, &g, s, g2);
   *gtotal = g;
   if (g > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "%zu grandchildren exceed 32-bit offsets", g);
   HIP_TRY(launch_offsets_u32(d->cur.offsets.p, t + 1, d_goffsets, s));

@@ -64,9 +64,9 @@ inline bool parse_fen(const char *fen, Board &B) {
   while (*s == ' ') ++s;
   if (*s == 'w' || *s == 'b') B.stm = (*s++ == 'b');
   else if (*s) return false;
+  // (the castling letters below need each side's king square; position_ok checks the rest)
   if (popcnt(B.byType[KING] & B.byColor[WHITE]) != 1 || popcnt(B.byType[KING] & B.byColor[BLACK]) != 1)
     return false;
-  if (popcnt(B.byType[0]) > 32 || (B.byType[PAWN] & 0xFF000000000000FFull)) return false;
   while (*s == ' ') ++s;
   while (*s && *s != ' ') {
     char t = *s++;
@@ -89,12 +89,7 @@ inline bool parse_fen(const char *fen, Board &B) {
   }
   while (*s == ' ') ++s;
   if (s[0] >= 'a' && s[0] <= 'h' && s[1] == (B.stm == WHITE ? '6' : '3')) {
-    int ep = (s[1] - '1') * 8 + (s[0] - 'a');
-    int us = B.stm, up = us == WHITE ? 8 : -8;
-    bool ok = (T.pawn[us ^ 1][ep] & B.byType[PAWN] & color_bb(B, us)) != 0 &&
-              (B.byType[PAWN] & color_bb(B, us ^ 1) & sqbb(ep - up)) != 0 &&
-              !(B.byType[0] & (sqbb(ep) | sqbb(ep + up)));
-    if (ok) B.ep = (uint8_t)ep;
+    B.ep = (uint8_t)((s[1] - '1') * 8 + (s[0] - 'a')); // kept only if position_ok finds it capturable
   }
   while (*s && *s != ' ') ++s;
   while (*s == ' ') ++s;
@@ -108,9 +103,7 @@ inline bool parse_fen(const char *fen, Board &B) {
       B.fullmove = (uint16_t)(f < 1 ? 1 : f > 65535 ? 65535 : f);
     }
   }
-  int oksq = king_square(B, B.stm ^ 1);
-  if (attackers_to(B, T, oksq, B.byType[0]) & color_bb(B, B.stm)) return false;
-  return true;
+  return position_ok(B, T); // the gate a caller's gn_board passes too (chess.h)
 }
 
 inline int board_to_fen(const Board &B, char *out, size_t cap) {

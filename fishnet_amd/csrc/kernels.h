@@ -189,7 +189,7 @@ hipError_t launch_finalize(const gn_board *boards, size_t n, int mode, const int
 // GN_FLAG_SEARCHED; writes score / flags / best_move of out[idx[j]] and sv[idx[j]] if sv).
 hipError_t launch_score_select(const gn_eval *out, size_t n, uint64_t *sel, hipStream_t s);
 hipError_t launch_score_gather(const gn_board *boards, const uint64_t *sel, const uint64_t *pos, size_t n,
-                               uint32_t *idx, gn_board *sb, hipStream_t s);
+                               const Tables *tables, uint32_t *idx, gn_board *sb, hipStream_t s);
 // Replies already evaluated by an expansion (records rec / moves at [off[i], off[i + 1]) of
 // parent i, the parents unpacked by write_children): compact offsets coff (m + 1, scan of
 // counts; *total_host = coff[m], synchronous), then (_fill) ce / cb / cm = the selected
@@ -218,18 +218,20 @@ hipError_t launch_score_reduce2(const gn_board *sb1, size_t m1, const uint64_t *
 hipError_t launch_reply_level(const gn_board *boards, size_t n, const Tables *tables, uint64_t *off, size_t cap,
                               gn_board *rb, uint16_t *rm, uint32_t *flag, int first, hipStream_t s);
 // legal-move counts per board (invalid boards: 0); ebound (optional): per parent an
-// upper bound of the planned expansion's list entries (stream.hip)
+// upper bound of the planned expansion's list entries (stream.hip).  The boards pass the gate
+// (chess.h unpack) unless trusted: the library's own boards (a legal child of a valid parent).
 hipError_t launch_count_children(const gn_board *boards, size_t n, const Tables *tables, uint64_t *counts,
-                                 hipStream_t s, uint64_t *ebound = nullptr);
+                                 hipStream_t s, uint64_t *ebound = nullptr, bool trusted = false);
 // children of every board at offsets[i] (exclusive prefix sums of counts): their moves,
 // owning board (owner, scratch) and, for children [c0, c0 + nc) (all children of these
 // boards), the child boards, deltas and chained-walk links.  moves / owner: required.
 // unpacked (optional, n entries): the boards unpacked once by the per-board pass, so that the
-// per-child pass reads its parent instead of unpacking it again.
+// per-child pass reads its parent instead of unpacking it again.  Without it the per-child pass
+// reads boards as they are: they must be canonical (trusted, or stored by score_gather_kernel).
 hipError_t launch_write_children(const gn_board *boards, size_t n, const Tables *tables, const uint64_t *offsets,
                                  size_t c0, size_t nc, gn_board *children, uint16_t *moves, uint32_t *owner,
                                  ChildDelta *deltas, uint8_t *next_slot, int chain_k, unsigned long long *rows,
-                                 hipStream_t s, Board *unpacked = nullptr);
+                                 hipStream_t s, Board *unpacked = nullptr, bool trusted = false);
 // sum of legal-move counts over all boards into *total (added; caller zeroes)
 hipError_t launch_count_sum(const gn_board *boards, size_t n, const Tables *tables,
                             unsigned long long *total, hipStream_t s);

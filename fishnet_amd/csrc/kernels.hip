@@ -229,7 +229,7 @@ __global__ void __launch_bounds__(2 * (L1 / 16) * PAR) __attribute__((amdgpu_wav
         Board B;
         uint8_t sm = 0, bg = 0;
         const gn_board g = boards[i];
-        if (unpack(g, B)) {
+        if (unpack_fields(g, B)) {
           const Material m = material(B, P);
           const int us = B.stm;
           const int simple = P.piece_value[0] * (m.pawns[us] - m.pawns[us ^ 1]) + (m.npm[us] - m.npm[us ^ 1]);
@@ -773,7 +773,7 @@ __global__ void classify_kernel(const gn_board *__restrict__ boards, size_t n, g
   if (i >= n) return;
   Board B;
   uint8_t s = 0, b = 0;
-  if (unpack(boards[i], B)) {
+  if (unpack_fields(boards[i], B)) {
     const Material m = material(B, P);
     const int us = B.stm;
     const int simple = P.piece_value[0] * (m.pawns[us] - m.pawns[us ^ 1]) + (m.npm[us] - m.npm[us ^ 1]);
@@ -793,6 +793,9 @@ __global__ void reeval_kernel(const int2 *__restrict__ out_small, const uint8_t 
   if (abs(nnue) < P.reeval_threshold) need_big[i] = 1;
 }
 
+// CHILD: position i is the child unpacked[owner[i]] + moves[i], the library's own (an expansion's
+// children: 30 of 31 positions, whose instantiation holds no gate code); else boards[i], gated.
+template <bool CHILD>
 __global__ void finalize_kernel(const gn_board *__restrict__ boards, size_t n, int mode,
                                 const int2 *__restrict__ out_small, const int2 *__restrict__ out_big,
                                 const uint8_t *__restrict__ need_small, const uint8_t *__restrict__ need_big,
@@ -819,14 +822,14 @@ __global__ void finalize_kernel(const gn_board *__restrict__ boards, size_t n, i
       }
       return out_big[j];
     };
-    const uint32_t ow = unpacked ? owner[i] : 0u;
-    const uint16_t mv = unpacked ? moves[i] : (uint16_t)0;
+    const uint32_t ow = CHILD ? owner[i] : 0u;
+    const uint16_t mv = CHILD ? moves[i] : (uint16_t)0;
 #else
     // the owner and move, then (part) the position's slice sums, all loaded before anything waits:
     // the sums' HBM round trip runs beside the owner -> parent board chain instead of after the
     // board work (owner, parent, pinfo, sums were three round trips in a row)
-    const uint32_t ow = unpacked ? owner[i] : 0u;
-    const uint16_t mv = unpacked ? moves[i] : (uint16_t)0;
+    const uint32_t ow = CHILD ? owner[i] : 0u;
+    const uint16_t mv = CHILD ? moves[i] : (uint16_t)0;
     int2 info = make_int2(0, -1);
     int4v sums[4];
     if (part) {
@@ -841,9 +844,9 @@ __global__ void finalize_kernel(const gn_board *__restrict__ boards, size_t n, i
 #endif
     Board B;
     gn_eval e = {0, 0, 0, 0, 0, 0, 0};
-    if (unpacked) {
+    if constexpr (CHILD) {
       B = do_move(unpacked[ow], mv, nullptr); // a legal child of a valid parent
-    } else if (!unpack(boards[i], B)) {
+    } else if (!unpack(boards[i], B, T)) {
       e.flags = GN_FLAG_BAD_FEN | GN_FLAG_NO_SCORE;
       out[i] = e;
       continue;
@@ -903,14 +906,25 @@ __global__ void score_select_kernel(const gn_eval *__restrict__ out, size_t n, u
 }
 
 // the selected positions, compacted: idx[k] = i, sb[k] = boards[i] for k = pos[i]
+// (a selected board is the caller's: it passed the gate in finalize and is stored as the gate left
+// it, so that the passes over sb -- write_children without an unpacked parent -- read a canonical
+// board; the few table words are read from global memory, once per position in check.  tables
+// NULL: sb is read for its material only (an expansion's replies are already evaluated): a copy)
 __global__ void score_gather_kernel(const gn_board *__restrict__ boards, const uint64_t *__restrict__ sel,
-                                    const uint64_t *__restrict__ pos, size_t n, uint32_t *__restrict__ idx,
-                                    gn_board *__restrict__ sb) {
+                                    const uint64_t *__restrict__ pos, size_t n, const Tables *__restrict__ tables,
+                                    uint32_t *__restrict__ idx, gn_board *__restrict__ sb) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || !sel[i]) return;
   const uint64_t k = pos[i];
   idx[k] = (uint32_t)i;
-  sb[k] = boards[i];
+  gn_board b = boards[i];
+  if (tables) {
+    Board B;
+    const bool ok = unpack(b, B, *tables);
+    b = gn_board{};
+    if (ok) pack(B, b);
+  }
+  sb[k] = b;
 }
 
 // An expansion's selected parents (idx) already have every reply evaluated (records rec,
@@ -973,7 +987,7 @@ __device__ __forceinline__ void score_reduce_one(size_t j, const gn_board *__res
     if (v > best || (v == best && mv < bm)) best = v, bm = mv;
   }
   Board B;
-  unpack(sb[j], B);
+  unpack_fields(sb[j], B); // (selected: it passed the gate)
   const uint32_t i = idx ? idx[j] : (uint32_t)j;
   gn_eval e = out[i];
   uint32_t fl = (e.flags | GN_FLAG_SEARCHED) & ~GN_FLAG_MATE;
@@ -1065,8 +1079,8 @@ __device__ __forceinline__ uint64_t group_max(uint64_t v) {
   return v;
 }
 
-__device__ __forceinline__ bool rank_parent(const Board &src, Board &B) { B = src; return true; }
-__device__ __forceinline__ bool rank_parent(const gn_board &src, Board &B) { return unpack(src, B); }
+__device__ __forceinline__ bool rank_parent(const Board &src, Board &B, const Tables &) { B = src; return true; }
+__device__ __forceinline__ bool rank_parent(const gn_board &src, Board &B, const Tables &T) { return unpack(src, B, T); }
 
 template <class Parent, class Off>
 __global__ void __launch_bounds__(RANK_WG)
@@ -1085,7 +1099,7 @@ __global__ void __launch_bounds__(RANK_WG)
     Board B;
     // (a parent without children -- bad, mated, stalemated, or skipped by the caller -- is never
     // unpacked or read as a Board: its unpacked entry is not written)
-    const bool ok = c1 > c0 && rank_parent(parents[p], B);
+    const bool ok = c1 > c0 && rank_parent(parents[p], B, T);
     for (uint64_t c = c0; ok && c < c1; c += W) {
       uint64_t key = 0;
       if (c + lane < c1) {
@@ -1170,10 +1184,14 @@ hipError_t launch_finalize(const gn_board *boards, size_t n, int mode, const int
   // LDS once (8,192 workgroups: 2.55 -> 2.36 ms per expansion against one per 256 positions)
   constexpr size_t max_blocks = 8192;
   const size_t blocks = std::min<size_t>(blocks_for(n, 256), max_blocks);
-  hipLaunchKernelGGL(finalize_kernel, dim3(blocks), dim3(256), 0, s, boards, n, mode, out_small, out_big, need_small,
-                     need_big, P, tables, out, owner, moves, unpacked, score, counts, bnet,
-                     sliced ? sliced->part : nullptr, sliced ? sliced->pinfo : nullptr, sliced ? sliced->npos : 0,
-                     sliced ? sliced->qoff : 0);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, boards, n, mode, out_small, out_big, need_small,
+                       need_big, P, tables, out, owner, moves, unpacked, score, counts, bnet,
+                       sliced ? sliced->part : nullptr, sliced ? sliced->pinfo : nullptr, sliced ? sliced->npos : 0,
+                       sliced ? sliced->qoff : 0);
+  };
+  if (unpacked) launch(finalize_kernel<true>);
+  else launch(finalize_kernel<false>);
   return hipGetLastError();
 }
 
@@ -1183,9 +1201,9 @@ hipError_t launch_score_select(const gn_eval *out, size_t n, uint64_t *sel, hipS
 }
 
 hipError_t launch_score_gather(const gn_board *boards, const uint64_t *sel, const uint64_t *pos, size_t n,
-                               uint32_t *idx, gn_board *sb, hipStream_t s) {
+                               const Tables *tables, uint32_t *idx, gn_board *sb, hipStream_t s) {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(score_gather_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, boards, sel, pos, n, idx, sb);
+  hipLaunchKernelGGL(score_gather_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, boards, sel, pos, n, tables, idx, sb);
   return hipGetLastError();
 }
 
@@ -1233,6 +1251,11 @@ hipError_t launch_score_replies_fill(const uint32_t *idx, size_t m, const uint64
 #ifndef GN_RL_THREADS
 #define GN_RL_THREADS 512
 #endif
+// (first: the boards are the caller's positions and pass the gate; the second level's are the first's
+// replies, the library's own, or empty slots)
+__device__ __forceinline__ bool level_board(const gn_board &b, Board &B, const Tables &T, int first) {
+  return first ? unpack(b, B, T) : unpack_fields(b, B);
+}
 __global__ void __launch_bounds__(GN_RL_THREADS) reply_level_kernel(const gn_board *__restrict__ boards, uint32_t n,
                                                            const Tables *__restrict__ tables, uint64_t *__restrict__ off,
                                                            uint32_t cap, gn_board *__restrict__ rb,
@@ -1250,7 +1273,7 @@ __global__ void __launch_bounds__(GN_RL_THREADS) reply_level_kernel(const gn_boa
   for (uint32_t i = lo; i < hi; ++i) {
     uint32_t cnt = 0;
     Board B;
-    if (unpack(boards[i], B) && in_check(B, T))
+    if (level_board(boards[i], B, T, first) && in_check(B, T))
       gen_legal(B, T, [&](uint16_t m) {
         if (c + cnt < MAXM) smv[t][c + cnt] = m, spos[t][c + cnt] = (uint8_t)(i - lo);
         ++cnt;
@@ -1279,7 +1302,7 @@ __global__ void __launch_bounds__(GN_RL_THREADS) reply_level_kernel(const gn_boa
     off[i] = base < cap ? base : cap;
     if (spill && cnt) { // this thread's replies did not fit its segment: made here, in order
       Board B;
-      unpack(boards[i], B);
+      level_board(boards[i], B, T, first);
       uint32_t r = base;
       gen_legal(B, T, [&](uint16_t m) {
         if (r < cap) {
@@ -1303,7 +1326,7 @@ __global__ void __launch_bounds__(GN_RL_THREADS) reply_level_kernel(const gn_boa
     const uint32_t k = r - (part[u] - cu);
     const uint16_t m = smv[u][k];
     Board B;
-    unpack(boards[u * q + spos[u][k]], B);
+    level_board(boards[u * q + spos[u][k]], B, T, first);
     pack(do_move(B, m, nullptr), rb[r]);
     rm[r] = m;
   }
@@ -1343,14 +1366,15 @@ hipError_t launch_score_reduce(const gn_board *sb, size_t m, const uint32_t *idx
 
 // ------------------------------------------------------- movegen kernels --
 __global__ void count_children_kernel(const gn_board *__restrict__ boards, size_t n, const Tables *__restrict__ tables,
-                                      uint64_t *__restrict__ counts, uint64_t *__restrict__ ebound) {
+                                      uint64_t *__restrict__ counts, uint64_t *__restrict__ ebound, int trusted) {
   __shared__ Tables T;
   load_tables(T, tables);
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   Board B;
   uint64_t c = 0, kmoves = 0;
-  if (unpack(boards[i], B)) {
+  // (trusted: the library's own boards, children as the next level's parents, skip the gate)
+  if (trusted ? unpack_fields(boards[i], B) : unpack(boards[i], B, T)) {
     const Bitboard king = B.byType[KING] & color_bb(B, B.stm);
     gen_legal(B, T, [&](uint16_t m) {
       ++c;
@@ -1389,18 +1413,18 @@ __global__ void count_children_kernel(const gn_board *__restrict__ boards, size_
 __global__ void child_moves_kernel(const gn_board *__restrict__ boards, size_t n, const Tables *__restrict__ tables,
                                    const uint64_t *__restrict__ offsets, uint16_t *__restrict__ moves,
                                    uint32_t *__restrict__ owner, uint8_t *__restrict__ next_slot, int chain_k,
-                                   unsigned long long *__restrict__ rows, Board *__restrict__ unpacked) {
+                                   unsigned long long *__restrict__ rows, Board *__restrict__ unpacked, int trusted) {
   __shared__ Tables T;
   load_tables(T, tables);
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t slot = 255;
   Board B;
-  if (!unpack(boards[i], B)) {
+  if (!(trusted ? unpack_fields(boards[i], B) : unpack(boards[i], B, T))) {
     if (next_slot) next_slot[i] = 255;
     return;
   }
-  if (unpacked) unpacked[i] = B; // for child_boards_kernel (a valid board has children only)
+  if (unpacked) unpacked[i] = B; // for child_boards_kernel (a valid board has children only), as the gate left it
   // S (0: no link possible) and the next board's bitboards
   Board N;
   Bitboard S = 0;
@@ -1408,7 +1432,7 @@ __global__ void child_moves_kernel(const gn_board *__restrict__ boards, size_t n
     const gn_board nb = boards[i + 1];
     const int pn = popcnt(nb.occ);
     if (pn >= 2 && pn <= 32) { // a child has 2..32 pieces
-      unpack(nb, N);           // a bad piece nibble leaves its square out of N's types: in S
+      unpack_fields(nb, N);          // a bad piece nibble leaves its square out of N's types: in S
       S = (B.byColor[0] ^ N.byColor[0]) | (B.byColor[1] ^ N.byColor[1]) | (B.byType[0] ^ N.byType[0]);
 #pragma unroll
       for (int t = PAWN; t <= KING; ++t) S |= B.byType[t] ^ N.byType[t];
@@ -1469,7 +1493,7 @@ __global__ void child_boards_kernel(const gn_board *__restrict__ boards, size_t 
     const uint32_t i = owner[c];
     Board B;
     if (unpacked) B = unpacked[i]; // the siblings share it (one cache line run per parent)
-    else unpack(boards[i], B);     // valid: an invalid parent has no children
+    else unpack_fields(boards[i], B); // canonical: the count and move passes gated it (score_gather_kernel)
     Dirty d;
     const Board C = do_move(B, moves[c], &d);
     if (children) pack(C, children[c]); // stored when the caller keeps the boards
@@ -1501,7 +1525,7 @@ __global__ void count_sum_kernel(const gn_board *__restrict__ boards, size_t n, 
   unsigned long long c = 0;
   if (i < n) {
     Board B;
-    if (unpack(boards[i], B)) gen_legal(B, T, [&](uint16_t) { ++c; });
+    if (unpack_fields(boards[i], B)) gen_legal(B, T, [&](uint16_t) { ++c; });
   }
   for (int off = 32; off; off >>= 1) c += __shfl_down(c, off, 64);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
@@ -1555,7 +1579,7 @@ __global__ void replay_games_kernel(const gn_board *__restrict__ roots, size_t n
   const uint64_t m0 = moff[g], m1 = moff[g + 1];
   gn_board *dst = boards + m0 + g;
   Board B;
-  unpack(roots[g], B); // validated by the host's FEN parser
+  unpack_fields(roots[g], B); // validated by the host's FEN parser
   dst[0] = roots[g];
   int32_t st = 0;
   for (uint64_t k = m0; k < m1; ++k) {
@@ -1662,21 +1686,21 @@ __global__ void offsets_u32_kernel(const uint64_t *__restrict__ in, size_t n, ui
 }
 
 hipError_t launch_count_children(const gn_board *boards, size_t n, const Tables *tables, uint64_t *counts,
-                                 hipStream_t s, uint64_t *ebound) {
+                                 hipStream_t s, uint64_t *ebound, bool trusted) {
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(count_children_kernel, dim3(blocks_for(n, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, n, tables, counts,
-                     ebound);
+                     ebound, trusted ? 1 : 0);
   return hipGetLastError();
 }
 
 hipError_t launch_write_children(const gn_board *boards, size_t n, const Tables *tables, const uint64_t *offsets,
                                  size_t c0, size_t nc, gn_board *children, uint16_t *moves, uint32_t *owner,
                                  ChildDelta *deltas, uint8_t *next_slot, int chain_k, unsigned long long *rows,
-                                 hipStream_t s, Board *unpacked) {
+                                 hipStream_t s, Board *unpacked, bool trusted) {
   if (!n) return hipSuccess;
   if (!moves || !owner) return hipErrorInvalidValue;
   hipLaunchKernelGGL(child_moves_kernel, dim3(blocks_for(n, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, n, tables, offsets, moves,
-                     owner, next_slot, chain_k, rows, unpacked);
+                     owner, next_slot, chain_k, rows, unpacked, trusted ? 1 : 0);
   if (nc)
     hipLaunchKernelGGL(child_boards_kernel, dim3(blocks_for(nc, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, c0, nc, moves, owner,
                        children, deltas, rows, unpacked);

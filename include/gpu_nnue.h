@@ -283,7 +283,39 @@ typedef struct gn_line {
  *            or 64 when none
  *   castle   4 nibbles [white O-O, white O-O-O, black O-O, black O-O-O]:
  *            bit 3 = right present, bits 0..2 = file of the castling rook
- *   rule50   half-move clock; fullmove = full-move number                    */
+ *   rule50   half-move clock; fullmove = full-move number
+ *
+ * A board a caller makes itself (gn_evaluate_device, gn_expand_device,
+ * gn_expand2_device, gn_rank_children_device, gn_time_*, gn_board_to_fen) behaves
+ * exactly like the FEN text that spells its fields without validating them --
+ * castling rights as Shredder file letters, the en-passant field as its square
+ * name, rule50 and fullmove as numbers -- handed to gn_evaluate_batch /
+ * gn_expand_and_evaluate.  One gate decides this on the host and on the device
+ * (position_ok, fishnet_amd/csrc/chess.h).
+ * Rejected: the record is exactly (0, 0, 0, 0, 0, GN_FLAG_BAD_FEN |
+ * GN_FLAG_NO_SCORE, 0), the position has no children, only empty lines and no
+ * grandchildren, gn_board_to_fen fails with GN_E_INVALID and gn_boards_to_fens
+ * writes "":
+ *   - popcount(occ) < 2 or > 32;
+ *   - a piece nibble of an occupied square whose type is 0 or 7 (0, 7, 8, 15);
+ *   - not exactly one king per colour;
+ *   - a pawn on rank 1 or rank 8;
+ *   - stm_ep & 0x7F above 64;
+ *   - the side not to move is in check.
+ * Normalised, then valid (every result is that of the canonical board):
+ *   - `reserved` and the nibbles beyond popcount(occ) are ignored;
+ *   - the low bits of a castle nibble are ignored when bit 3 is clear;
+ *   - a castling right is dropped unless an own rook stands on that square of the
+ *     own back rank, the own king stands on that rank, and the rook is on the
+ *     king's right for slots 0 / 2, on its left for slots 1 / 3 (a text spells a
+ *     right by its file alone; a right in the other side's slot has no spelling);
+ *   - the en-passant square is none unless it is on rank 6 (white to move) or
+ *     rank 3 (black to move), a pawn of the side to move attacks it, an enemy
+ *     pawn stands behind it, and it and the square before it are empty;
+ *   - rule50 and fullmove are taken as they are, any 16-bit value: rule50 enters
+ *     the evaluation, fullmove 0 is valid (a FEN text's 0 reads as 1).
+ * Boards the library writes (children, gn_pack_fens, gn_random_*) are canonical:
+ * reserved = 0, unused nibbles 0, no right or en-passant square the gate drops. */
 typedef struct gn_board {
   uint64_t occ;
   uint8_t pc[16];

@@ -235,8 +235,9 @@ def test_incremental_stress_wrap(oracle_lib):
         assert got == {int(m): tuple(k) for m, k in zip(m_exp, G.children_from_evals(k_exp))}, fen
 
 
-def test_expand_device_matches_host(gpu_ctx):
+def test_expand_device_matches_host(gpu_ctx, oracle_lib):
     from fishnet_amd import gpu_nnue as G
+    from test_gpu_raw_boards import check_boards_out
     boards = G.random_positions(99, 0, 300, 160)
     fens = [G.board_to_fen(b) for b in boards]
     hp, hoffs, hmoves, hkids = gpu_ctx.expand_and_evaluate(fens, 0)
@@ -250,8 +251,7 @@ def test_expand_device_matches_host(gpu_ctx):
     assert np.array_equal(bufs["mv"].download(np.uint16, cap), hmoves)
     assert np.array_equal(G.children_from_evals(bufs["co"].download(G.EVAL_DTYPE, cap)), hkids)
     assert np.array_equal(bufs["po"].download(G.EVAL_DTYPE, n), hp)
-    kids = bufs["ch"].download(G.BOARD_DTYPE, 40)
-    assert [G.board_to_fen(k) for k in kids[:3]]
+    assert check_boards_out(G, oracle_lib, boards, hoffs, hmoves, bufs["ch"].download(G.BOARD_DTYPE, cap)) == cap
     with pytest.raises(G.GnError):
         gpu_ctx.expand_device(bufs["b"], n, 0, bufs["po"], bufs["off"], bufs["ch"], bufs["mv"], bufs["co"], cap - 1)
 
