@@ -13,6 +13,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -345,13 +346,26 @@ struct Dev {
   DevBuf<gn_line> ln2[2];  // or ranked: the chunk's lines (gn_evaluate_games_lines)
   hipEvent_t rev[2] = {nullptr, nullptr}; // around a chunk's rank_children_kernel (GN_STAT_RANK_NS)
   DevBuf<uint16_t> mv2[2];
+  // gn_evaluate_lines2: one chunk's depth-2 expansion (gn_expand2_device's outputs, library-owned
+  // and grown to the chunk's exact counts) and its lines
+  struct Lines2 {
+    DevBuf<gn_eval> po, co, gco;
+    DevBuf<uint32_t> off, goff;
+    DevBuf<gn_board> ch;
+    DevBuf<uint16_t> mv, gmv;
+    DevBuf<gn_line2> ln;
+    void release() {
+      po.release(), co.release(), gco.release(), off.release(), goff.release(), ch.release(), mv.release();
+      gmv.release(), ln.release();
+    }
+  } l2;
   DevBuf<gn_board> roots, rboards, par;
   DevBuf<uint64_t> moff;
   DevBuf<uint16_t> codes, smoves;
   DevBuf<int32_t> rstatus;
   DevBuf<uint32_t> gidx;
   // stage times of the last host-buffer call on this device (GN_STAT_HOST_*), ms
-  double t_upload = 0, t_replay = 0, t_compute = 0, t_download = 0, t_tail = 0, t_rank = 0;
+  double t_upload = 0, t_replay = 0, t_compute = 0, t_download = 0, t_tail = 0, t_rank = 0, t_rank2 = 0;
   // the drop-in's small-batch graphs (FastBatch): two per size class (128 << k positions) and mode,
   // so that a second call's launch queues on the stream behind a first one in flight
   std::unique_ptr<FastBatch> fast[6][3][2];
@@ -557,6 +571,7 @@ static void destroy(gn_ctx *ctx) {
     d.ebound.release(), d.pool.release();
     d.bkeys.release(), d.bkeys2.release(), d.bidx.release();
     d.lv[0].release(), d.lv[1].release();
+    d.l2.release();
     for (auto &row : d.fast)
       for (auto &pair : row)
         for (auto &f : pair) f.reset();
@@ -1442,7 +1457,7 @@ static int run_shards(gn_ctx *ctx, const std::vector<size_t> &b, F &&f) {
 }
 
 static void reset_host_stats(gn_ctx *ctx) {
-  for (auto &dp : ctx->devs) dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = 0;
+  for (auto &dp : ctx->devs) dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = 0;
 }
 
 // Chunk bounds of a shard's m parents: cut only where `starts` allows (the first parent of each
@@ -2642,18 +2657,20 @@ int gn_rank_children_device(gn_ctx *ctx, int device_slot, const gn_board *d_pare
   return GN_OK;
 }
 
-int gn_expand2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, int mode,
-                      gn_eval *d_parent_out, uint32_t *d_offsets, gn_board *d_children, uint16_t *d_moves,
-                      gn_eval *d_child_out, size_t cap, uint32_t *d_goffsets, uint16_t *d_gmoves,
-                      gn_eval *d_grand_out, size_t gcap, size_t *total, size_t *gtotal, void *stream) {
-  Dev *d = slot(ctx, device_slot);
-  if (!d || !total || !gtotal) return fail(GN_E_INVALID, "bad argument");
-  if (n && (!d_parents || !d_offsets)) return fail(GN_E_INVALID, "NULL buffer");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
-  SeqGuard sg(*d, s);
-  HIP_TRY(sg.e);
+// gn_expand2_device's work on stream s (d.mu held, the launch sequence begun).  size_grand
+// (optional, gn_evaluate_lines2): called with the grandchild count once level 1 is done, it
+// provides the level-2 buffers (d_goffsets: total + 1, d_gmoves / d_grand_out / gcap: the count)
+// instead of the caller's.
+struct Expand2Grand {
+  uint32_t *d_goffsets;
+  uint16_t *d_gmoves;
+  gn_eval *d_grand_out;
+  size_t gcap;
+};
+static int expand2_on(gn_ctx *ctx, Dev *d, const gn_board *d_parents, size_t n, int mode, gn_eval *d_parent_out,
+                      uint32_t *d_offsets, gn_board *d_children, uint16_t *d_moves, gn_eval *d_child_out, size_t cap,
+                      Expand2Grand gr, size_t *total, size_t *gtotal, hipStream_t s,
+                      const std::function<int(size_t, size_t, Expand2Grand &)> *size_grand = nullptr) {
   *total = *gtotal = 0;
   if (!n) return GN_OK;
   // a size query (NULL child buffers or too small): the counts, GN_E_CAPACITY
@@ -2678,24 +2695,28 @@ int gn_expand2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, s
   if ((rc = check_plan(*d, s)) != GN_OK) return rc;
   const Replies rp{d_child_out, d_moves}; // level 1's replies
   if ((rc = resolve_scores(ctx, *d, d_parents, n, mode, d_parent_out, nullptr, s, 2, &rp)) != GN_OK) return rc;
+  size_t g = 0;
+  if (size_grand) { // (the library's own level-2 buffers, grown to the exact count)
+    if (t) HIP_TRY(count_children(*d, d_children, t, s, &g));
+    if ((rc = (*size_grand)(t, g, gr)) != GN_OK) return rc;
+  }
   if (!t) {
-    HIP_TRY(hipMemsetAsync(d_goffsets, 0, sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(gr.d_goffsets, 0, sizeof(uint32_t), s));
     HIP_TRY(hipStreamSynchronize(s));
     return GN_OK;
   }
   // level 2: the children as parents (their grandchildren boards stay library-internal)
-  size_t g = 0;
-  if (!d_goffsets || !d_gmoves || !d_grand_out || !gcap) {
+  if (!gr.d_goffsets || !gr.d_gmoves || !gr.d_grand_out || !gr.gcap) {
     HIP_TRY(count_children(*d, d_children, t, s, &g));
     *gtotal = g;
-    return g ? fail(GN_E_CAPACITY, "%zu grandchildren exceed capacity %zu", g, gcap) : GN_OK;
+    return g ? fail(GN_E_CAPACITY, "%zu grandchildren exceed capacity %zu", g, gr.gcap) : GN_OK;
   }
-  GenOpts g2 = gen_opts(ctx, *d, t, mode, gcap);
+  GenOpts g2 = gen_opts(ctx, *d, t, mode, gr.gcap);
   g2.trusted = true; // level 1's children, written above
-  rc = generate_children(*d, d_children, t, nullptr, d_gmoves, &g, s, g2);
+  rc = generate_children(*d, d_children, t, nullptr, gr.d_gmoves, &g, s, g2);
   *gtotal = g;
   if (g > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "%zu grandchildren exceed 32-bit offsets", g);
-  HIP_TRY(launch_offsets_u32(d->cur.offsets.p, t + 1, d_goffsets, s));
+  HIP_TRY(launch_offsets_u32(d->cur.offsets.p, t + 1, gr.d_goffsets, s));
   if (rc) {
     HIP_TRY(hipStreamSynchronize(s));
     return rc;
@@ -2704,7 +2725,7 @@ int gn_expand2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, s
   // (the children as parents are child records here too: compared with level 1's below)
   EvalOpts as_children;
   as_children.score_parents = false;
-  rc = expand_evaluate(ctx, *d, d_children, t, d->cur.children.p, g, mode, d->io_out.p, d_grand_out, s, as_children);
+  rc = expand_evaluate(ctx, *d, d_children, t, d->cur.children.p, g, mode, d->io_out.p, gr.d_grand_out, s, as_children);
   if (rc) return rc;
   // the children evaluated twice (level 1 as children, level 2 as parents) must agree
   HIP_TRY(d->sum.ensure(2));
@@ -2716,6 +2737,40 @@ int gn_expand2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, s
   HIP_TRY(hipStreamSynchronize(s));
   if ((rc = check_plan(*d, s)) != GN_OK) return rc;
   if (cs[0] != cs[1]) return fail(GN_E_HIP, "depth 2: the children's level-1 and level-2 evaluations differ");
+  return GN_OK;
+}
+
+int gn_expand2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, int mode,
+                      gn_eval *d_parent_out, uint32_t *d_offsets, gn_board *d_children, uint16_t *d_moves,
+                      gn_eval *d_child_out, size_t cap, uint32_t *d_goffsets, uint16_t *d_gmoves,
+                      gn_eval *d_grand_out, size_t gcap, size_t *total, size_t *gtotal, void *stream) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d || !total || !gtotal) return fail(GN_E_INVALID, "bad argument");
+  if (n && (!d_parents || !d_offsets)) return fail(GN_E_INVALID, "NULL buffer");
+  std::lock_guard<std::mutex> lk(d->mu);
+  HIP_TRY(hipSetDevice(d->id));
+  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  SeqGuard sg(*d, s);
+  HIP_TRY(sg.e);
+  return expand2_on(ctx, d, d_parents, n, mode, d_parent_out, d_offsets, d_children, d_moves, d_child_out, cap,
+                    Expand2Grand{d_goffsets, d_gmoves, d_grand_out, gcap}, total, gtotal, s);
+}
+
+int gn_rank_lines2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
+                          const gn_board *d_children, const gn_eval *d_child_out, const uint16_t *d_moves,
+                          const uint32_t *d_goffsets, const uint16_t *d_gmoves, const gn_eval *d_grand_out, int n_lines,
+                          gn_line2 *d_lines, void *stream) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
+  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  // (the child and grandchild buffers may be NULL when no parent has a child: they are then never read)
+  if (n && (!d_parents || !d_offsets || !d_lines)) return fail(GN_E_INVALID, "NULL buffer");
+  std::lock_guard<std::mutex> lk(d->mu);
+  HIP_TRY(hipSetDevice(d->id));
+  SeqGuard sg(*d, stream ? (hipStream_t)stream : d->stream);
+  HIP_TRY(sg.e);
+  HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
+                             ctx->P, d->tables, n_lines, d_lines, sg.s));
   return GN_OK;
 }
 
@@ -2953,6 +3008,7 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
   case GN_STAT_HOST_COMPUTE_NS:
   case GN_STAT_HOST_DOWNLOAD_NS:
   case GN_STAT_RANK_NS:
+  case GN_STAT_RANK2_NS:
   case GN_STAT_HOST_TAIL_NS: { // the last host-buffer call, max over devices
     double m = 0;
     for (auto &dp : ctx->devs) {
@@ -2962,6 +3018,7 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
                       : option == GN_STAT_HOST_COMPUTE_NS ? d.t_compute
                       : option == GN_STAT_HOST_DOWNLOAD_NS ? d.t_download
                       : option == GN_STAT_RANK_NS          ? d.t_rank
+                      : option == GN_STAT_RANK2_NS         ? d.t_rank2
                                                            : d.t_tail);
     }
     *value = (int64_t)(m * 1e6);
@@ -3003,6 +3060,93 @@ int gn_expand_and_evaluate(gn_ctx *ctx, const char *const *parent_fens, size_t n
     if (rc) return rc;
     ctx->t_parse = ms_since(T0);
     rc = expand_boards_host(ctx, boards.data(), n, mode, parent_out, child_offsets, child_moves, child_out, cap);
+    ctx->t_total = ms_since(T0);
+    return rc;
+  } catch (const std::bad_alloc &) {
+    return fail(GN_E_NOMEM, "host allocation failed");
+  } catch (...) {
+    return fail(GN_E_INVALID, "unexpected exception");
+  }
+}
+
+// Two-ply ranked lines from host boards (gn_evaluate_lines2): each device's shard in chunks of
+// chunk parents; per chunk the depth-2 expansion into the device's Lines2 buffers (expand2_on),
+// rank_lines2_kernel, and one download of the chunk's parent records and lines.
+static int lines2_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int mode, int K, gn_eval *out,
+                              gn_line2 *lines) {
+  const size_t nd = ctx->devs.size();
+  std::vector<size_t> b(nd + 1);
+  partition(nullptr, n, (int)nd, b.data());
+  std::vector<std::unique_lock<std::mutex>> locks; // every device lock for the whole call
+  for (auto &dp : ctx->devs) locks.emplace_back(dp->mu);
+  // 1,024 parents are ~1 M grandchildren: a few hundred MB of records, boards and partial sums
+  const size_t chunk = ctx->chunk_parents > 0 ? (size_t)ctx->chunk_parents : 1024;
+  return run_shards(ctx, b, [&](size_t, Dev &d, size_t lo, size_t hi) -> int {
+    HIP_TRY(hipSetDevice(d.id));
+    hipStream_t s = d.stream;
+    SeqGuard sg(d, s);
+    HIP_TRY(sg.e);
+    Dev::Lines2 &x = d.l2;
+    auto t0 = Clock::now();
+    HIP_TRY(d.par.ensure(hi - lo));
+    HIP_TRY(hipMemcpyAsync(d.par.p, boards + lo, (hi - lo) * sizeof(gn_board), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    d.t_upload += ms_since(t0);
+    const std::function<int(size_t, size_t, Expand2Grand &)> size_grand = [&](size_t t, size_t g, Expand2Grand &gr) -> int {
+      HIP_TRY(x.goff.ensure(t + 1));
+      HIP_TRY(x.gmv.ensure(std::max<size_t>(g, 1)));
+      HIP_TRY(x.gco.ensure(std::max<size_t>(g, 1)));
+      gr = Expand2Grand{x.goff.p, x.gmv.p, x.gco.p, std::max<size_t>(g, 1)};
+      return GN_OK;
+    };
+    for (size_t a = lo; a < hi; a += chunk) {
+      const size_t mp = std::min(chunk, hi - a);
+      const gn_board *par = d.par.p + (a - lo);
+      t0 = Clock::now();
+      size_t t = 0, g = 0;
+      HIP_TRY(count_children(d, par, mp, s, &t));
+      const size_t cap = std::max<size_t>(t, 1);
+      HIP_TRY(x.po.ensure(mp));
+      HIP_TRY(x.off.ensure(mp + 1));
+      HIP_TRY(x.ch.ensure(cap));
+      HIP_TRY(x.mv.ensure(cap));
+      HIP_TRY(x.co.ensure(cap));
+      HIP_TRY(x.ln.ensure(mp * (size_t)K));
+      int rc = expand2_on(ctx, &d, par, mp, mode, x.po.p, x.off.p, x.ch.p, x.mv.p, x.co.p, cap, Expand2Grand{}, &t, &g, s,
+                          &size_grand);
+      if (rc) return rc;
+      HIP_TRY(hipEventRecord(d.rev[0], s));
+      HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables, K,
+                                 x.ln.p, s));
+      HIP_TRY(hipEventRecord(d.rev[1], s));
+      HIP_TRY(hipStreamSynchronize(s));
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, d.rev[0], d.rev[1]));
+      d.t_rank2 += ms;
+      d.t_compute += ms_since(t0), t0 = Clock::now();
+      HIP_TRY(hipMemcpyAsync(out + a, x.po.p, mp * sizeof(gn_eval), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(lines + a * (size_t)K, x.ln.p, mp * (size_t)K * sizeof(gn_line2), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      d.t_download += ms_since(t0);
+    }
+    return GN_OK;
+  });
+}
+
+int gn_evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,
+                       gn_line2 *lines) {
+  if (!slot(ctx, 0)) return fail(GN_E_INVALID, "bad context");
+  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  if (n && (!fens || !out || !lines)) return fail(GN_E_INVALID, "NULL argument");
+  if (!n) return GN_OK;
+  try {
+    const auto T0 = Clock::now();
+    reset_host_stats(ctx);
+    std::vector<gn_board> boards(n);
+    int rc = gn_pack_fens(fens, n, boards.data(), nullptr);
+    if (rc) return rc;
+    ctx->t_parse = ms_since(T0);
+    rc = lines2_boards_host(ctx, boards.data(), n, mode, n_lines, out, lines);
     ctx->t_total = ms_since(T0);
     return rc;
   } catch (const std::bad_alloc &) {

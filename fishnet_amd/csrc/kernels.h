@@ -260,6 +260,17 @@ hipError_t launch_rank_children(const Board *unpacked, size_t n, const uint64_t 
 hipError_t launch_rank_children(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
                                 const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
                                 gn_line *lines, hipStream_t s);
+// Two-ply ranked lines (include/gpu_nnue.h gn_line2): lines[i * K + k] = line k + 1 of parent i, from
+// a depth-2 expansion's outputs: the children [offsets[i], offsets[i + 1]) (boards, records rec,
+// moves) and each child c's grandchildren [goffsets[c], goffsets[c + 1]) (gmoves, records grec).
+// One launch, no scratch memory; children / grandchild arrays are not read when no parent has a
+// child.  (The kernel is templated on the parent form and offset type like rank_children_kernel;
+// the host path feeds it the same packed parents and 32-bit offsets as the C-ABI: level 2 of the
+// expansion has overwritten the buffer set's unpacked parents and 64-bit offsets by then.)
+hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t *offsets, const gn_board *children,
+                              const gn_eval *rec, const uint16_t *moves, const uint32_t *goffsets,
+                              const uint16_t *gmoves, const gn_eval *grec, const gn_eval_params &P,
+                              const Tables *tables, int K, gn_line2 *lines, hipStream_t s);
 // narrowing copy of offsets for the C-ABI
 hipError_t launch_offsets_u32(const uint64_t *in, size_t n, uint32_t *out, hipStream_t s);
 // exclusive scan of n + 1 counts (counts[n] must be 0); temp grows on demand

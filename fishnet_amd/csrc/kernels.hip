@@ -1070,13 +1070,31 @@ hipError_t launch_pack_children(const gn_eval *in, size_t n, gn_child *out, hipS
 static_assert(GN_RANK_WIDTH == 32 || GN_RANK_WIDTH == 64, "a parent per half wave or per wave");
 constexpr int RANK_WG = 256;
 
-__device__ __forceinline__ uint64_t group_max(uint64_t v) {
+template <int W>
+__device__ __forceinline__ uint64_t group_max_w(uint64_t v) {
 #pragma unroll
-  for (int o = GN_RANK_WIDTH / 2; o; o >>= 1) {
-    const uint64_t w = __shfl_xor(v, o, GN_RANK_WIDTH);
+  for (int o = W / 2; o; o >>= 1) {
+    const uint64_t w = __shfl_xor(v, o, W);
     v = w > v ? w : v;
   }
   return v;
+}
+__device__ __forceinline__ uint64_t group_max(uint64_t v) { return group_max_w<GN_RANK_WIDTH>(v); }
+
+// K rounds of the cross-lane maximum over the lanes' keys and the running top K (lane k's `top`):
+// the new top K, round k's winner to lane k, the winner retiring.  Keys are distinct or 0.
+template <int W>
+__device__ __forceinline__ uint64_t top_k_rounds(uint64_t key, uint64_t top, int lane, int K) {
+  uint64_t next = 0;
+  for (int k = 0; k < K; ++k) {
+    const uint64_t mine = key > top ? key : top;
+    const uint64_t m = group_max_w<W>(mine);
+    if (!m) break; // (uniform in the group) fewer than K lines so far
+    if (key == m) key = 0;
+    if (top == m) top = 0;
+    if (lane == k) next = m;
+  }
+  return next;
 }
 
 __device__ __forceinline__ bool rank_parent(const Board &src, Board &B, const Tables &) { B = src; return true; }
@@ -1156,6 +1174,127 @@ hipError_t launch_rank_children(const gn_board *parents, size_t n, const uint32_
                                 const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
                                 gn_line *lines, hipStream_t s) {
   return rank_children_t(parents, n, offsets, moves, rec, P, tables, K, lines, s);
+}
+
+// ---- two-ply ranked lines (include/gpu_nnue.h gn_line2) -----------------------------------
+// The consumer of a depth-2 expansion's records: the grandchildren reduced to each child's best
+// reply, the children to the parent's top K, in one launch and without scratch memory.  A
+// workgroup takes one parent at a time; its eight 32-lane groups take the parent's children
+// round-robin (group q: children q, q + 8, ...).  A group unpacks its child (the library's own
+// board: unpack_fields, no gate, as level 2 of the expansion reads it), a lane takes a grandchild
+// (do_move from the child, any_legal, its key (V + 32768) << 16 | 0xFFFF - reply with
+// V = negate_ply(V1(g))), keeps a running maximum over segments longer than 32, and one butterfly
+// per child gives R(c) and the reply.  A child without grandchildren needs no board: mated or
+// stalemated by its record's check bit.  The child's key is rank_children_kernel's packing with
+// the reply below the move: (value + 32768) << 34 | (0xFFFF - move) << 18 | reply << 2 |
+// no-moves << 1 | in-check, value = negate_ply(R(c)); 0 is no line.  Each group keeps its own
+// top list sorted in its lanes (lane k: the group's k-th best so far) and inserts a child's key
+// with one __shfl_up: any number of children, no staging array.  The eight groups' top 8 then
+// meet in LDS (64 keys) and wave 0 merges them by the K-round maximum over two 32-key passes;
+// lanes 0..K-1 of group 0 store the parent's K lines, 16 B each, as one contiguous run.
+// Control flow: the loop over a parent's children and the branch on a parent without children
+// are uniform in the workgroup (both barriers are reached by every lane or by none); the loop
+// over a child's grandchildren runs until no lane of the wave has one left (__any), so both
+// groups of a wave reach every shuffle together.
+template <class Parent, class Off>
+__global__ void __launch_bounds__(RANK_WG)
+    rank_lines2_kernel(const Parent *__restrict__ parents, size_t n, const Off *__restrict__ offsets,
+                       const gn_board *__restrict__ children, const gn_eval *__restrict__ rec,
+                       const uint16_t *__restrict__ moves, const Off *__restrict__ goffsets,
+                       const uint16_t *__restrict__ gmoves, const gn_eval *__restrict__ grec, gn_eval_params P,
+                       const Tables *__restrict__ tables, int K, gn_line2 *__restrict__ lines) {
+  __shared__ Tables T;
+  __shared__ uint64_t merge[RANK_WG / 32 * GN_MAX_LINES]; // each group's top 8
+  load_tables(T, tables);
+  constexpr int W = 32, GROUPS = RANK_WG / W;
+  const int lane = threadIdx.x & (W - 1), q = threadIdx.x / W;
+  for (size_t p = blockIdx.x; p < n; p += gridDim.x) {
+    const uint64_t c0 = offsets[p], c1 = offsets[p + 1];
+    if (c0 == c1) { // bad, mated or stalemated: never unpacked, K empty lines
+      if (threadIdx.x < K) lines[p * (size_t)K + threadIdx.x] = gn_line2{0, 0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE, 0};
+      continue;
+    }
+    uint64_t top = 0; // lane k: this group's k-th best child key so far (0: none)
+    for (uint64_t cb = c0; cb < c1; cb += GROUPS) {
+      const uint64_t c = cb + q;
+      const bool have = c < c1;
+      uint64_t g0 = 0, g1 = 0;
+      uint32_t mv = 0, check = 0;
+      if (have) {
+        g0 = goffsets[c], g1 = goffsets[c + 1];
+        mv = moves[c];
+        check = (rec[c].flags & GN_FLAG_IN_CHECK) ? 1u : 0u;
+      }
+      const uint32_t none = g0 == g1 ? 1u : 0u;
+      uint64_t best = 0; // the lane's best reply key
+      if (__any(g0 < g1)) {
+        Board C;
+        if (!none) unpack_fields(children[c], C);
+        for (uint64_t g = g0; __any(g < g1); g += W) {
+          if (g + lane < g1) {
+            const uint32_t gm = gmoves[g + lane];
+            const gn_eval r = grec[g + lane];
+            const Board G = do_move(C, (uint16_t)gm, nullptr);
+            const int32_t v1 = any_legal(G, T) ? r.final_v : (r.flags & GN_FLAG_IN_CHECK) ? -VALUE_MATE : 0;
+            const uint64_t k = (uint64_t)(uint32_t)(negate_ply(v1) + 32768) << 16 | (0xFFFFu - gm);
+            best = k > best ? k : best;
+          }
+        }
+      }
+      best = group_max_w<W>(best);
+      uint64_t key = 0;
+      if (have) {
+        const int32_t R = none ? (check ? -VALUE_MATE : 0) : (int32_t)(best >> 16) - 32768;
+        const uint32_t reply = none ? 0u : 0xFFFFu - (uint32_t)(best & 0xFFFFu);
+        key = (uint64_t)(uint32_t)(negate_ply(R) + 32768) << 34 | (uint64_t)(0xFFFFu - mv) << 18 |
+              (uint64_t)reply << 2 | none << 1 | check;
+      }
+      // sorted insert: lane k takes the key if it beats top[k] but not top[k - 1], the neighbour's
+      // old value if it beats both
+      const uint64_t up = __shfl_up(top, 1, W);
+      if (key > top) top = (lane > 0 && key > up) ? up : key;
+    }
+    if (lane < GN_MAX_LINES) merge[q * GN_MAX_LINES + lane] = lane < K ? top : 0;
+    __syncthreads();
+    if (threadIdx.x < 64) { // wave 0, both of its groups alike (the shuffles stay wave-uniform)
+      uint64_t t2 = top_k_rounds<W>(merge[lane], 0, lane, K);
+      t2 = top_k_rounds<W>(merge[W + lane], t2, lane, K);
+      if (threadIdx.x < K) {
+        Board B;
+        rank_parent(parents[p], B, T); // (it has children: it passed the gate)
+        gn_line2 l = {0, 0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE, 0};
+        if (t2) {
+          uint32_t fl = ((t2 & 1) ? GN_FLAG_IN_CHECK : 0u) | ((t2 & 2) ? GN_FLAG_NO_MOVES : 0u);
+          l.value = (int32_t)(t2 >> 34) - 32768;
+          l.move = (uint16_t)(0xFFFFu - (uint32_t)((t2 >> 18) & 0xFFFFu));
+          l.reply = (uint16_t)((t2 >> 2) & 0xFFFFu);
+          l.score = rule_score(l.value, wdl_material(B, P), P, fl);
+          l.flags = (uint16_t)fl;
+          l.plies = (t2 & 2) ? 1 : 2;
+        }
+        lines[p * (size_t)K + threadIdx.x] = l;
+      }
+    }
+    __syncthreads(); // the merge slots are read: the next parent may overwrite them
+  }
+}
+
+template <class Parent, class Off>
+static hipError_t rank_lines2_t(const Parent *parents, size_t n, const Off *offsets, const gn_board *children,
+                                const gn_eval *rec, const uint16_t *moves, const Off *goffsets, const uint16_t *gmoves,
+                                const gn_eval *grec, const gn_eval_params &P, const Tables *tables, int K,
+                                gn_line2 *lines, hipStream_t s) {
+  if (!n) return hipSuccess;
+  const size_t blocks = std::min<size_t>(n, 8192);
+  hipLaunchKernelGGL((rank_lines2_kernel<Parent, Off>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets, children,
+                     rec, moves, goffsets, gmoves, grec, P, tables, K, lines);
+  return hipGetLastError();
+}
+hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t *offsets, const gn_board *children,
+                              const gn_eval *rec, const uint16_t *moves, const uint32_t *goffsets,
+                              const uint16_t *gmoves, const gn_eval *grec, const gn_eval_params &P,
+                              const Tables *tables, int K, gn_line2 *lines, hipStream_t s) {
+  return rank_lines2_t(parents, n, offsets, children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines, s);
 }
 
 hipError_t launch_classify(const gn_board *boards, size_t n, const gn_eval_params &P, uint8_t *need_small,

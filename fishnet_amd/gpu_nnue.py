@@ -38,8 +38,12 @@ CHILD_VIEW_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("final_cp"
 # gn_line: one ranked line of a position (MultiPV; gpu_nnue.h at gn_line), 12 bytes
 LINE_DTYPE = np.dtype([("value", "<i4"), ("score", "<i4"), ("move", "<u2"), ("flags", "<u2")])
 MAX_LINES = 8
+# gn_line2: one ranked two-ply line (a two-move PV and its minimax value; gpu_nnue.h at gn_line2), 16 bytes
+LINE2_DTYPE = np.dtype([("value", "<i4"), ("score", "<i4"), ("move", "<u2"), ("reply", "<u2"), ("flags", "<u2"),
+                        ("plies", "<u2")])
 EVAL_SIZE, BOARD_SIZE, CHILD_SIZE = EVAL_DTYPE.itemsize, BOARD_DTYPE.itemsize, CHILD_DTYPE.itemsize
 assert EVAL_SIZE == 24 and BOARD_SIZE == 32 and CHILD_SIZE == 12 and LINE_DTYPE.itemsize == 12
+assert LINE2_DTYPE.itemsize == 16
 ABI_VERSION = 4
 
 EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_abi_version",
@@ -51,12 +55,13 @@ EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_
            "gn_time_expand_device", "gn_random_games_device", "gn_replay_game", "gn_evaluate_games",
            "gn_net_sha256", "gn_partition", "gn_checksum_device",
            "gn_boards_to_fens", "gn_load_net_archive", "gn_archive_read", "gn_expand2_device",
-           "gn_random_games_uci", "gn_rank_children_device", "gn_evaluate_games_lines"]
+           "gn_random_games_uci", "gn_rank_children_device", "gn_evaluate_games_lines",
+           "gn_rank_lines2_device", "gn_evaluate_lines2"]
 OPT_INCREMENTAL_CHILDREN, OPT_XCD_SWIZZLE, OPT_KING_SORT, OPT_CHAIN, OPT_KING_CACHE = 1, 2, 3, 4, 5
 OPT_CHUNK_PARENTS, OPT_COALESCE, OPT_STREAM_SLICES, OPT_FAST_BATCH, OPT_EXPAND_PIPELINE = 6, 7, 8, 9, 10
 STAT_PLAN_NS, STAT_STREAM_NS, STAT_SCRATCH_PADS, STAT_FINISH_NS = 101, 102, 103, 104
 STAT_BATCH_LAUNCHES, STAT_BATCH_CALLS, STAT_FAST_BATCHES, STAT_FAST_FALLBACKS = 117, 118, 119, 120
-STAT_RANK_NS = 121
+STAT_RANK_NS, STAT_RANK2_NS = 121, 122
 HOST_STAGES = {"parse": 110, "upload": 111, "replay": 112, "compute": 113, "download": 114, "tail": 115, "total": 116}
 EXPAND_STAGES = ["count_scan", "total_readback", "write_children", "classify", "small_net", "big_net", "finalize",
                  "score"]
@@ -173,6 +178,8 @@ def lib():
         "gn_random_games_uci": [C.c_uint64, sz, sz, i32, vp, sz],
         "gn_rank_children_device": [vp, i32, vp, sz, vp, vp, vp, i32, vp, vp],
         "gn_evaluate_games_lines": [vp, vp, sz, i32, i32, vp, vp, vp, sz, vp],
+        "gn_rank_lines2_device": [vp, i32, vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+        "gn_evaluate_lines2": [vp, vp, sz, i32, i32, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -493,6 +500,16 @@ class GpuNnue:
             return offs, status, pos[:p], lines[:p]
         raise GnError(E_CAPACITY, "capacity retry failed")
 
+    def evaluate_lines2(self, fens, n_lines, mode=MODE_FULL):
+        """gn_evaluate_lines2: (positions[EVAL_DTYPE], lines[positions, n_lines] as LINE2_DTYPE): the
+        best n_lines two-ply lines (move, best reply, minimax value) of every FEN."""
+        n = len(fens)
+        arr, _keep = _fen_array(fens)
+        out = np.zeros(n, dtype=EVAL_DTYPE)
+        lines = np.zeros((n, max(n_lines, 1)), dtype=LINE2_DTYPE)
+        _check(lib().gn_evaluate_lines2(self.h, arr, n, mode, n_lines, out.ctypes.data, lines.ctypes.data))
+        return out, lines
+
     def host_stages(self):
         """Stage times (ms) of the last gn_evaluate_games / gn_expand_and_evaluate (GN_STAT_HOST_*)."""
         return {k: self.get_option(v) / 1e6 for k, v in HOST_STAGES.items()}
@@ -568,6 +585,14 @@ class GpuNnue:
         offsets, moves and child records.  Asynchronous on the stream."""
         _check(lib().gn_rank_children_device(self.h, slot, d_parents.ptr, n, d_offsets.ptr, d_moves.ptr,
                                              d_child_out.ptr, n_lines, d_lines.ptr, stream))
+
+    def rank_lines2_device(self, d_parents, n, out, n_lines, d_lines, stream=None, slot=0):
+        """gn_rank_lines2_device: d_lines[n * n_lines] (LINE2_DTYPE) from a preceding expand2_device's
+        outputs (out: its dict of DeviceBuffers off, ch, co, mv, goff, gmv, gco).  Asynchronous on
+        the stream."""
+        p = lambda k: out[k].ptr if out.get(k) is not None else None
+        _check(lib().gn_rank_lines2_device(self.h, slot, d_parents.ptr, n, p("off"), p("ch"), p("co"), p("mv"),
+                                           p("goff"), p("gmv"), p("gco"), n_lines, d_lines.ptr, stream))
 
     def expand2_device(self, d_parents, n, mode, out, stream=None, slot=0):
         """Depth 2 (gn_expand2_device).  out: DeviceBuffers po, off, ch (child boards), mv, co,

@@ -70,7 +70,10 @@ extern "C" {
                                          gn_evaluate_games with children): parents per chunk,
                                          cut at game starts; 0 (default): automatic (whole
                                          games, >= 165,888 parents per chunk, a short last
-                                         chunk).  Results are identical for every value.   */
+                                         chunk).  gn_evaluate_lines2 (depth 2, ~1,000
+                                         grandchildren per parent): exactly this many parents
+                                         per chunk; 0 (default): 1,024.  Results are
+                                         identical for every value.                         */
 #define GN_OPT_COALESCE 7             /* 1 (default): concurrent gn_evaluate_batch calls on one
                                          context are merged into one launch (each call
                                          queues; one call leads a launch over every queued
@@ -172,6 +175,9 @@ extern "C" {
 #define GN_STAT_RANK_NS 121           /* rank_children_kernel in the last
                                          gn_evaluate_games_lines, summed over its chunks
                                          (0 after any other host-buffer call)              */
+#define GN_STAT_RANK2_NS 122          /* rank_lines2_kernel in the last gn_evaluate_lines2,
+                                         summed over its chunks (the slowest device; 0 after
+                                         any other host-buffer call)                       */
 #define GN_STAT_BATCH_LAUNCHES 117    /* merged gn_evaluate_batch launches since load ...   */
 #define GN_STAT_BATCH_CALLS 118       /* ... and the calls they served (GN_OPT_COALESCE)    */
 #define GN_STAT_FAST_BATCHES 119      /* evaluations run by the captured small-batch graphs
@@ -273,6 +279,44 @@ typedef struct gn_line {
                      GN_FLAG_NO_MOVES: the move ends the game (mate or stalemate);
                      GN_FLAG_NO_SCORE: an empty line                                     */
 } gn_line;
+
+/* One ranked two-ply line of a position: a two-move principal variation (fishnet's
+ * pvs[multipv][depth] is a Vec<UciMove>, not a single move) with its minimax value.
+ * gn_rank_lines2_device and gn_evaluate_lines2 return n_lines of them per position,
+ * 1 <= n_lines <= GN_MAX_LINES.  A gn_line values a move by its child's static evaluation, also
+ * where the child is in check, and cannot see that the move hangs a mate in one; a gn_line2
+ * values it by the opponent's best reply.
+ * The rule, for a position p a call evaluates (not bad) with at least one legal move, over every
+ * legal move m with child c:
+ *   V1(g) for a grandchild g is gn_line's V: -VALUE_MATE (-32000) when g has no legal move and is
+ *   in check, 0 when g has no legal move and is not in check, g's static final_v in the call's
+ *   mode otherwise;
+ *   c has a legal move: R(c) = max over c's legal replies r (grandchild g) of negate_ply(V1(g)),
+ *   ties to the smaller 16-bit move encoding; reply = that r, plies = 2.  This holds when c is in
+ *   check too: c's own static value is never used;
+ *   c has no legal move: R(c) = -VALUE_MATE when c is in check (m mates), 0 when it is not (m
+ *   stalemates); reply = 0, plies = 1, GN_FLAG_NO_MOVES;
+ *   value(m) = negate_ply(R(c)), score = rule_score(value, p's win-rate material): the same
+ *   negate_ply and rule_score as everywhere else (gn_eval.score above).
+ * Lines are ordered by value descending, ties to the smaller `move`.  Missing lines are empty,
+ * (0, 0, 0, 0, GN_FLAG_NO_SCORE, 0); a bad, checkmated or stalemated position has only empty
+ * lines.
+ * Relation to gn_line: take the children as parents with their grandchildren's records; for a
+ * child c with a legal move, (R(c), reply) is exactly line 1's (value, move) from
+ * gn_rank_children_device.
+ * Relation to gn_eval.score: none is claimed.  The score rule searches only positions that are in
+ * check (and then only replies that give check); these lines search two plies everywhere. */
+typedef struct gn_line2 { /* 16 bytes */
+  int32_t value;  /* minimax value after two plies, p's side-to-move POV, Stockfish units  */
+  int32_t score;  /* rule_score(value, p's win-rate material): cp, or the mate distance with
+                     GN_FLAG_MATE                                                          */
+  uint16_t move;  /* p's move (Stockfish encoding, castling = king takes rook)             */
+  uint16_t reply; /* the opponent's best reply to it; 0 when the move ends the game        */
+  uint16_t flags; /* GN_FLAG_MATE; GN_FLAG_IN_CHECK: the move gives check; GN_FLAG_NO_MOVES:
+                     the move ends the game; GN_FLAG_NO_SCORE: an empty line               */
+  uint16_t plies; /* moves in the PV: 2, or 1 when the move ends the game, 0 for an empty
+                     line                                                                  */
+} gn_line2;
 
 /* Packed position, 32 bytes, the device input format.
  *   occ      occupied squares (bit s = square s, a1 = 0 .. h8 = 63)
@@ -463,6 +507,18 @@ GN_API int gn_evaluate_games_lines(gn_ctx *ctx, const gn_game *games, size_t n_g
                                    uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                                    size_t position_cap, gn_line *lines);
 
+/* Two-ply ranked lines from FENs: out[i] = position i's record (byte-equal to
+ * gn_expand_and_evaluate's parent_out for the same FENs and mode), lines[i * n_lines + k] = line
+ * k + 1 of position i (gn_line2).  The FENs are sharded equally over the context's devices; each
+ * shard runs in chunks of GN_OPT_CHUNK_PARENTS parents (0: 1,024): the depth-2 expansion into
+ * library-owned buffers, rank_lines2_kernel, one download of the chunk's records and lines
+ * (24 + 16 * n_lines bytes per position; no child or grandchild reaches the host).  A bad FEN
+ * gets the GN_FLAG_BAD_FEN record and empty lines; the call still returns GN_OK.  Results are
+ * identical for every chunk size and device count.  n_lines outside 1..GN_MAX_LINES:
+ * GN_E_INVALID.  GN_STAT_HOST_* and GN_STAT_RANK2_NS: the call's stage times. */
+GN_API int gn_evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines,
+                              gn_eval *out, gn_line2 *lines); /* lines[n * n_lines] */
+
 /* The partitioner the library uses to shard work over the devices of a context and
  * that multi-process callers use to shard over ranks: contiguous ranges of n_items
  * items, bounds[k] = first item of shard k, bounds[n_shards] = n_items; shard k
@@ -539,6 +595,16 @@ GN_API int gn_expand2_device(gn_ctx *ctx, int device_slot, const gn_board *d_par
                              gn_eval *d_parent_out, uint32_t *d_offsets, gn_board *d_children, uint16_t *d_moves,
                              gn_eval *d_child_out, size_t cap, uint32_t *d_goffsets, uint16_t *d_gmoves,
                              gn_eval *d_grand_out, size_t gcap, size_t *total, size_t *gtotal, void *stream);
+/* Ranks the outputs of a preceding gn_expand2_device of the same parents (d_offsets, d_children,
+ * d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out as it wrote them): d_lines[i * n_lines + k]
+ * = line k + 1 of parent i (gn_line2).  One launch (rank_lines2_kernel): nothing but 16 * n_lines
+ * bytes per parent needs to leave the device.  Asynchronous on `stream` (NULL = the context's
+ * own), no read-back.  n_lines outside 1..GN_MAX_LINES: GN_E_INVALID.  The child and grandchild
+ * buffers may be NULL when no parent has a child. */
+GN_API int gn_rank_lines2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                 const uint32_t *d_offsets, const gn_board *d_children, const gn_eval *d_child_out,
+                                 const uint16_t *d_moves, const uint32_t *d_goffsets, const uint16_t *d_gmoves,
+                                 const gn_eval *d_grand_out, int n_lines, gn_line2 *d_lines, void *stream);
 GN_API int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, int mode,
                                  int iters, float *ms_total, size_t *total, float *stage_ms, uint64_t *ft_rows,
                                  gn_eval *d_parent_out, uint32_t *d_offsets, uint16_t *d_moves,

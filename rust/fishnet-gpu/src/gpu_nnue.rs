@@ -22,6 +22,7 @@ use shakmaty::{fen::Fen, uci::UciMove, Role, Square};
 pub use sys::gn_child as GpuChild;
 pub use sys::gn_eval as GpuEval;
 pub use sys::gn_line as GpuLine;
+pub use sys::gn_line2 as GpuLine2;
 
 pub struct GpuNnue(*mut sys::gn_ctx);
 
@@ -136,6 +137,27 @@ impl GpuNnue {
         if let Some(&code) = status.iter().find(|&&s| s != sys::GN_OK) {
             return Err(last_error(code));
         }
+        Ok((evals, lines))
+    }
+
+    /// The best `n_lines` two-ply lines of every position (1..=8): the records as evaluate_batch
+    /// returns them and, per position, `n_lines` lines of a move, the opponent's best reply and the
+    /// minimax value after both (lines[i * n_lines + k] = line k + 1 of position i; `plies` is the
+    /// PV's length, 1 when the move ends the game; empty lines carry GN_FLAG_NO_SCORE;
+    /// include/gpu_nnue.h at gn_line2).  gn_evaluate_lines2 expands two plies and ranks on the GPU:
+    /// only the records and the lines come back.  A FEN the library refuses has the
+    /// GN_FLAG_BAD_FEN record and empty lines.
+    pub fn evaluate_lines2(&self, fens: &[Fen], n_lines: usize) -> Result<(Vec<GpuEval>, Vec<GpuLine2>), GpuError> {
+        let owned: Vec<CString> = fens.iter().map(|f| CString::new(f.to_string()).unwrap()).collect();
+        let ptrs: Vec<*const std::os::raw::c_char> = owned.iter().map(|c| c.as_ptr()).collect();
+        let mut evals = vec![GpuEval::default(); fens.len()];
+        let mut lines = vec![GpuLine2::default(); fens.len() * n_lines];
+        // SAFETY: ptrs / evals have fens.len() elements, lines fens.len() * n_lines; the call
+        // checks n_lines before it writes.
+        check(unsafe {
+            sys::gn_evaluate_lines2(self.0, ptrs.as_ptr(), ptrs.len(), sys::GN_MODE_FULL, n_lines as i32,
+                                    evals.as_mut_ptr(), lines.as_mut_ptr())
+        })?;
         Ok((evals, lines))
     }
 

@@ -55,6 +55,7 @@ pub const GN_STAT_BATCH_CALLS: c_int = 118;
 pub const GN_STAT_FAST_BATCHES: c_int = 119;
 pub const GN_STAT_FAST_FALLBACKS: c_int = 120;
 pub const GN_STAT_RANK_NS: c_int = 121;
+pub const GN_STAT_RANK2_NS: c_int = 122;
 
 // per-position flags
 pub const GN_FLAG_IN_CHECK: u16 = 1;
@@ -118,6 +119,21 @@ pub struct gn_line {
     pub score: i32,
     pub r#move: u16,
     pub flags: u16,
+}
+
+/// One ranked two-ply line of a position (16 bytes): a two-move principal variation (`move`, then
+/// the opponent's best `reply`; reply 0 and plies 1 when the move ends the game) with its minimax
+/// value and score; flags as gn_line's; an empty line is (0, 0, 0, 0, GN_FLAG_NO_SCORE, 0); see the
+/// header at gn_line2.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct gn_line2 {
+    pub value: i32,
+    pub score: i32,
+    pub r#move: u16,
+    pub reply: u16,
+    pub flags: u16,
+    pub plies: u16,
 }
 
 /// Packed position (32 bytes), the device input format.
@@ -206,6 +222,8 @@ extern "C" {
     pub fn gn_evaluate_games_lines(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
                                    n_lines: c_int, position_offsets: *mut u32, game_status: *mut i32,
                                    position_out: *mut gn_eval, position_cap: usize, lines: *mut gn_line) -> c_int;
+    pub fn gn_evaluate_lines2(ctx: *mut gn_ctx, fens: *const *const c_char, n: usize, mode: c_int, n_lines: c_int,
+                              out: *mut gn_eval, lines: *mut gn_line2) -> c_int;
     pub fn gn_partition(weights: *const u32, n_items: usize, n_shards: c_int, bounds: *mut usize) -> c_int;
     pub fn gn_perft(ctx: *mut gn_ctx, fen: *const c_char, depth: c_int, nodes: *mut u64) -> c_int;
     pub fn gn_pack_fens(fens: *const *const c_char, n: usize, out: *mut gn_board, ok: *mut u8) -> c_int;
@@ -226,6 +244,11 @@ extern "C" {
     pub fn gn_rank_children_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
                                    d_offsets: *const u32, d_moves: *const u16, d_child_out: *const gn_eval,
                                    n_lines: c_int, d_lines: *mut gn_line, stream: *mut c_void) -> c_int;
+    pub fn gn_rank_lines2_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                                 d_offsets: *const u32, d_children: *const gn_board, d_child_out: *const gn_eval,
+                                 d_moves: *const u16, d_goffsets: *const u32, d_gmoves: *const u16,
+                                 d_grand_out: *const gn_eval, n_lines: c_int, d_lines: *mut gn_line2,
+                                 stream: *mut c_void) -> c_int;
     pub fn gn_expand2_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize, mode: c_int,
                              d_parent_out: *mut gn_eval, d_offsets: *mut u32, d_children: *mut gn_board,
                              d_moves: *mut u16, d_child_out: *mut gn_eval, cap: usize, d_goffsets: *mut u32,
@@ -262,6 +285,7 @@ mod tests {
         assert_eq!(std::mem::size_of::<gn_eval>(), 24);
         assert_eq!(std::mem::size_of::<gn_child>(), 12);
         assert_eq!(std::mem::size_of::<gn_line>(), 12);
+        assert_eq!(std::mem::size_of::<gn_line2>(), 16);
         let c = gn_child { psqt: 0, positional: 0, cp_flags: (0x00FF_FFFEu32 | 65u32 << 24) as i32 };
         assert_eq!((c.final_cp(), c.flags()), (-2, 65));
         assert_eq!(std::mem::size_of::<gn_board>(), 32);
