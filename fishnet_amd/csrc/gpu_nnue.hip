@@ -16,6 +16,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -46,6 +47,19 @@ static int fail(int code, const char *fmt, ...) {
     if (e_ != hipSuccess) return fail(GN_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
                                       __FILE__, __LINE__);                                          \
   } while (0)
+
+// The exception fence: f's code, or the code and message of what it threw (nothing is thrown
+// across the C-ABI or out of a device's host thread).
+template <class F>
+static int guarded(F &&f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc &) {
+    return fail(GN_E_NOMEM, "host allocation failed");
+  } catch (...) {
+    return fail(GN_E_INVALID, "unexpected exception");
+  }
+}
 
 namespace gn {
 const Tables &host_tables() {
@@ -416,6 +430,24 @@ struct SeqGuard { // seq_begin now, seq_end when the scope ends (d.mu held throu
   }
   ~SeqGuard() {
     if (!ended) (void)seq_end(d, s);
+  }
+};
+
+// A single-device entry point's frame: the device's lock, the device made current, and a launch
+// sequence on the caller's stream (NULL: the device's own), for the object's lifetime.  rc is the
+// failure that kept the sequence from beginning (its message set), or GN_OK.
+struct DevCall {
+  std::lock_guard<std::mutex> lk;
+  const hipStream_t s;
+  std::optional<SeqGuard> sg; // (ends before the lock is released)
+  int rc;
+  DevCall(Dev &d, void *stream = nullptr) : lk(d.mu), s(stream ? (hipStream_t)stream : d.stream) {
+    rc = [&]() -> int {
+      HIP_TRY(hipSetDevice(d.id));
+      sg.emplace(d, s);
+      HIP_TRY(sg->e);
+      return GN_OK;
+    }();
   }
 };
 
@@ -1135,17 +1167,15 @@ static void partition(const uint32_t *weights, size_t n, int ns, size_t *bounds)
   bounds[ns] = n;
 }
 
-// Runs f(k) for every device k on its own host thread (one device: inline) with that
-// device's lock held; returns the first failing code with its message.
+// Runs f(k) for every device k on its own host thread (one device: inline); returns the first
+// failing code with its message.
 template <class F>
-static int for_each_device(gn_ctx *ctx, F &&f) {
+static int device_threads(gn_ctx *ctx, F &&f) {
   const size_t nd = ctx->devs.size();
   std::vector<int> rcs(nd, GN_OK);
   std::vector<std::string> errs(nd);
   auto work = [&](size_t k) {
-    Dev &d = *ctx->devs[k];
-    std::lock_guard<std::mutex> lk(d.mu);
-    rcs[k] = f(k, d);
+    rcs[k] = f(k);
     if (rcs[k]) errs[k] = g_err;
   };
   if (nd == 1) work(0);
@@ -1160,6 +1190,15 @@ static int for_each_device(gn_ctx *ctx, F &&f) {
       return rcs[k];
     }
   return GN_OK;
+}
+// ... f(k, d) with device k's lock held.
+template <class F>
+static int for_each_device(gn_ctx *ctx, F &&f) {
+  return device_threads(ctx, [&](size_t k) -> int {
+    Dev &d = *ctx->devs[k];
+    std::lock_guard<std::mutex> lk(d.mu);
+    return f(k, d);
+  });
 }
 
 // A FastBatch for nb positions in mode: buffers, pinned staging, the captured graph (d.mu held).
@@ -1288,15 +1327,10 @@ static int evaluate_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, i
     Dev &d = *ctx->devs[0];
     std::unique_lock<std::mutex> lk(d.mu);
     bool done = false;
-    int rc;
-    try {
-      rc = fast_run(ctx, d, lk, boards, n, mode, out, &done);
-    } catch (const std::bad_alloc &) {
-      rc = fail(GN_E_NOMEM, "host allocation failed");
-    }
+    const int rc = guarded([&]() -> int { return fast_run(ctx, d, lk, boards, n, mode, out, &done); });
     if (rc || done) return rc;
   }
-  try {
+  return guarded([&]() -> int {
     std::vector<size_t> b(ctx->devs.size() + 1);
     partition(nullptr, n, (int)ctx->devs.size(), b.data());
     return for_each_device(ctx, [&](size_t k, Dev &d) -> int {
@@ -1316,11 +1350,7 @@ static int evaluate_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, i
       HIP_TRY(hipStreamSynchronize(d.stream));
       return GN_OK;
     });
-  } catch (const std::bad_alloc &) {
-    return fail(GN_E_NOMEM, "host allocation failed");
-  } catch (...) {
-    return fail(GN_E_INVALID, "unexpected exception");
-  }
+  });
 }
 
 // Concurrent gn_evaluate_batch calls merged into one launch (group commit): a call queues
@@ -1335,11 +1365,7 @@ static int evaluate_coalesced(gn_ctx *ctx, const gn_board *boards, size_t n, int
   auto &C = ctx->co;
   BatchReq me{boards, n, mode, out};
   std::unique_lock<std::mutex> lk(C.mu);
-  try {
-    C.q.push_back(&me);
-  } catch (const std::bad_alloc &) {
-    return fail(GN_E_NOMEM, "host allocation failed");
-  }
+  if (const int rc = guarded([&]() -> int { return C.q.push_back(&me), GN_OK; })) return rc;
   // every exit (an exception included) takes this call's request off the queue, so that no
   // later leader touches it after this stack frame is gone
   struct Dequeue {
@@ -1361,40 +1387,31 @@ static int evaluate_coalesced(gn_ctx *ctx, const gn_board *boards, size_t n, int
     // the queue is split before the context is marked busy: an allocation failure here leaves
     // the context free and this call off the queue (Dequeue)
     std::vector<BatchReq *> mine, rest;
-    try {
-      mine.reserve(C.q.size()), rest.reserve(C.q.size());
-    } catch (const std::bad_alloc &) {
-      return fail(GN_E_NOMEM, "host allocation failed");
-    }
+    if (const int rc = guarded([&]() -> int { return mine.reserve(C.q.size()), rest.reserve(C.q.size()), GN_OK; }))
+      return rc;
     for (BatchReq *r : C.q) (r->mode == mode ? mine : rest).push_back(r);
     C.q.swap(rest);
     for (BatchReq *r : mine) r->taken = true;
     ++C.active;
     lk.unlock();
-    // from here to the re-lock nothing may throw outside the try block: this launch is counted in
+    // from here to the re-lock nothing may throw outside the fence: this launch is counted in
     // C.active and only this thread takes it out
-    int rc = GN_OK;
     char err[256] = "";
-    try {
-      if (mine.size() == 1) { // (this call's own request: it was queued and not taken)
-        rc = evaluate_boards_host(ctx, mine[0]->boards, mine[0]->n, mode, mine[0]->out);
-      } else {
-        size_t tot = 0;
-        for (BatchReq *r : mine) tot += r->n;
-        std::vector<gn_board> all(tot);
-        std::vector<gn_eval> res(tot);
-        size_t at = 0;
-        for (BatchReq *r : mine) std::copy(r->boards, r->boards + r->n, all.begin() + at), at += r->n;
-        rc = evaluate_boards_host(ctx, all.data(), tot, mode, res.data());
-        at = 0;
-        if (rc == GN_OK)
-          for (BatchReq *r : mine) std::copy(res.begin() + at, res.begin() + at + r->n, r->out), at += r->n;
-      }
-    } catch (const std::bad_alloc &) {
-      rc = fail(GN_E_NOMEM, "host allocation failed");
-    } catch (...) {
-      rc = fail(GN_E_INVALID, "unexpected exception");
-    }
+    const int rc = guarded([&]() -> int {
+      if (mine.size() == 1) // (this call's own request: it was queued and not taken)
+        return evaluate_boards_host(ctx, mine[0]->boards, mine[0]->n, mode, mine[0]->out);
+      size_t tot = 0;
+      for (BatchReq *r : mine) tot += r->n;
+      std::vector<gn_board> all(tot);
+      std::vector<gn_eval> res(tot);
+      size_t at = 0;
+      for (BatchReq *r : mine) std::copy(r->boards, r->boards + r->n, all.begin() + at), at += r->n;
+      const int r0 = evaluate_boards_host(ctx, all.data(), tot, mode, res.data());
+      at = 0;
+      if (r0 == GN_OK)
+        for (BatchReq *r : mine) std::copy(res.begin() + at, res.begin() + at + r->n, r->out), at += r->n;
+      return r0;
+    });
     if (rc) snprintf(err, sizeof err, "%s", g_err.c_str());
     lk.lock();
     for (BatchReq *r : mine) r->rc = rc, memcpy(r->err, err, sizeof err), r->done = true;
@@ -1424,36 +1441,36 @@ static double ms_since(Clock::time_point t) {
   return std::chrono::duration<double, std::milli>(Clock::now() - t).count();
 }
 
-// f(k, d, lo, hi) on every device k whose shard [b[k], b[k + 1]) is not empty, one host thread
-// per device (the caller holds every device lock); the first failure's code and message.
+// Every device lock, in slot order: a host-buffer call holds them all from here to its return.
+static std::vector<std::unique_lock<std::mutex>> lock_devices(gn_ctx *ctx) {
+  std::vector<std::unique_lock<std::mutex>> locks;
+  for (auto &dp : ctx->devs) locks.emplace_back(dp->mu);
+  return locks;
+}
+
+// One phase of a host-buffer call: f(k, d) on every device k that busy(k) names, one host thread
+// per device (one device: inline), the caller holding every device lock (lock_devices).  f runs
+// with its device current and inside one launch sequence on d.stream; the first failure's code
+// and message.
+template <class Busy, class F>
+static int run_devices(gn_ctx *ctx, Busy &&busy, F &&f) {
+  return device_threads(ctx, [&](size_t k) -> int {
+    if (!busy(k)) return GN_OK;
+    return guarded([&]() -> int {
+      Dev &d = *ctx->devs[k];
+      HIP_TRY(hipSetDevice(d.id));
+      SeqGuard sg(d, d.stream);
+      HIP_TRY(sg.e);
+      return f(k, d);
+    });
+  });
+}
+// ... by item range: f(k, d, lo, hi) on every device k whose shard [b[k], b[k + 1]) is not empty.
 template <class F>
 static int run_shards(gn_ctx *ctx, const std::vector<size_t> &b, F &&f) {
-  const size_t nd = ctx->devs.size();
-  std::vector<int> rcs(nd, GN_OK);
-  std::vector<std::string> errs(nd);
-  auto work = [&](size_t k) {
-    if (b[k] >= b[k + 1]) return;
-    try {
-      rcs[k] = f(k, *ctx->devs[k], b[k], b[k + 1]);
-    } catch (const std::bad_alloc &) {
-      rcs[k] = fail(GN_E_NOMEM, "host allocation failed");
-    } catch (...) {
-      rcs[k] = fail(GN_E_INVALID, "unexpected exception");
-    }
-    if (rcs[k]) errs[k] = g_err;
-  };
-  if (nd == 1) work(0);
-  else {
-    std::vector<std::thread> th;
-    for (size_t k = 0; k < nd; ++k) th.emplace_back(work, k);
-    for (auto &t : th) t.join();
-  }
-  for (size_t k = 0; k < nd; ++k)
-    if (rcs[k]) {
-      g_err = errs[k];
-      return rcs[k];
-    }
-  return GN_OK;
+  return run_devices(
+      ctx, [&](size_t k) { return b[k] < b[k + 1]; },
+      [&](size_t k, Dev &d) -> int { return f(k, d, b[k], b[k + 1]); });
 }
 
 static void reset_host_stats(gn_ctx *ctx) {
@@ -1629,13 +1646,21 @@ static int run_expansions(gn_ctx *ctx, Dev &d, int mode, size_t count, size_t la
   return rc;
 }
 
-// Pass 2 of a shard (see above).  off: the shard's child offsets from pass 1; results to
-// parent_out[0, m) (optional), child_moves / child_out[0, off[m]) (the caller's arrays at this
-// shard's base).  n_lines > 0 (gn_evaluate_games_lines): no child reaches the host; each chunk's
-// children are ranked on the device and lines[0, m * n_lines) receives n_lines lines per parent.
+// Where a shard's results go (expand_pipelined), each pointer at the shard's base: parent_out[0, m)
+// (optional) and child_moves / child_out[0, off[m]); or, n_lines > 0 (gn_evaluate_games_lines), no
+// child reaches the host: each chunk's children are ranked on the device and lines[0, m * n_lines)
+// receives n_lines lines per parent.
+struct ExpandOut {
+  gn_eval *parent_out = nullptr;
+  uint16_t *child_moves = nullptr;
+  gn_child *child_out = nullptr;
+  int n_lines = 0;
+  gn_line *lines = nullptr;
+};
+// Pass 2 of a shard (see above).  off: the shard's child offsets from pass 1.
 static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m, int mode,
-                            const std::vector<uint64_t> &off, const std::vector<size_t> &chunks, gn_eval *parent_out,
-                            uint16_t *child_moves, gn_child *child_out, int n_lines = 0, gn_line *lines = nullptr) {
+                            const std::vector<uint64_t> &off, const std::vector<size_t> &chunks, const ExpandOut &o) {
+  const int n_lines = o.n_lines;
   hipStream_t s = d.stream;
   size_t maxp = 1, maxc = 1;
   for (size_t c = 0; c + 1 < chunks.size(); ++c)
@@ -1674,14 +1699,14 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
       hipError_t e = hipSetDevice(d.id);
       if (e == hipSuccess) e = hipStreamWaitEvent(d.copy, d.cev[k], 0);
       if (e == hipSuccess && n_lines)
-        e = hipMemcpyAsync(lines + pa * (size_t)n_lines, d.ln2[k].p, mp * (size_t)n_lines * sizeof(gn_line),
+        e = hipMemcpyAsync(o.lines + pa * (size_t)n_lines, d.ln2[k].p, mp * (size_t)n_lines * sizeof(gn_line),
                            hipMemcpyDeviceToHost, d.copy);
       if (e == hipSuccess && t && !n_lines)
-        e = hipMemcpyAsync(child_out + cb, d.cc2[k].p, t * sizeof(gn_child), hipMemcpyDeviceToHost, d.copy);
+        e = hipMemcpyAsync(o.child_out + cb, d.cc2[k].p, t * sizeof(gn_child), hipMemcpyDeviceToHost, d.copy);
       if (e == hipSuccess && t && !n_lines)
-        e = hipMemcpyAsync(child_moves + cb, d.mv2[k].p, t * sizeof(uint16_t), hipMemcpyDeviceToHost, d.copy);
-      if (e == hipSuccess && parent_out)
-        e = hipMemcpyAsync(parent_out + pa, d.po2[k].p, mp * sizeof(gn_eval), hipMemcpyDeviceToHost, d.copy);
+        e = hipMemcpyAsync(o.child_moves + cb, d.mv2[k].p, t * sizeof(uint16_t), hipMemcpyDeviceToHost, d.copy);
+      if (e == hipSuccess && o.parent_out)
+        e = hipMemcpyAsync(o.parent_out + pa, d.po2[k].p, mp * sizeof(gn_eval), hipMemcpyDeviceToHost, d.copy);
       if (e == hipSuccess) e = hipStreamSynchronize(d.copy);
       if (e != hipSuccess) drc[k] = GN_E_HIP, derr[k] = std::string("result download failed: ") + hipGetErrorString(e);
       dms[k] = ms_since(t1);
@@ -1748,18 +1773,14 @@ static int expand_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int
     child_offsets[0] = 0;
     return GN_OK;
   }
-  try {
+  return guarded([&]() -> int {
     const size_t nd = ctx->devs.size();
     std::vector<size_t> b(nd + 1);
     partition(nullptr, n, (int)nd, b.data());
-    std::vector<std::unique_lock<std::mutex>> locks; // every device lock for the whole call
-    for (auto &dp : ctx->devs) locks.emplace_back(dp->mu);
+    const auto locks = lock_devices(ctx);
     std::vector<std::vector<uint64_t>> off(nd);
     // pass 1: upload + child counts
     int rc = run_shards(ctx, b, [&](size_t k, Dev &d, size_t lo, size_t hi) -> int {
-      HIP_TRY(hipSetDevice(d.id));
-      SeqGuard sg(d, d.stream);
-      HIP_TRY(sg.e);
       const auto t0 = Clock::now();
       HIP_TRY(d.par.ensure(hi - lo));
       HIP_TRY(hipMemcpyAsync(d.par.p, boards + lo, (hi - lo) * sizeof(gn_board), hipMemcpyHostToDevice, d.stream));
@@ -1779,20 +1800,30 @@ static int expand_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int
     if (total && (!child_moves || !child_out)) return fail(GN_E_INVALID, "NULL child buffer");
     // pass 2: chunks of 81 parents' multiples (a FEN batch has no games: blocks of 81 = chain_len)
     return run_shards(ctx, b, [&](size_t k, Dev &d, size_t lo, size_t hi) -> int {
-      HIP_TRY(hipSetDevice(d.id));
-      SeqGuard sg(d, d.stream);
-      HIP_TRY(sg.e);
       const size_t m = hi - lo;
       std::vector<size_t> starts;
       for (size_t i = 81; i < m; i += 81) starts.push_back(i);
       return expand_pipelined(ctx, d, d.par.p, m, mode, off[k], chunk_plan(m, starts, ctx->chunk_parents),
-                              parent_out ? parent_out + lo : nullptr, child_moves + base[k], child_out + base[k]);
+                              {parent_out ? parent_out + lo : nullptr, child_moves + base[k], child_out + base[k]});
     });
-  } catch (const std::bad_alloc &) {
-    return fail(GN_E_NOMEM, "host allocation failed");
-  } catch (...) {
-    return fail(GN_E_INVALID, "unexpected exception");
-  }
+  });
+}
+
+// A host-buffer call over n FENs (gn_expand_and_evaluate, gn_evaluate_lines2): f(boards) on the
+// packed FENs, between the host stage times.
+template <class F>
+static int on_packed_fens(gn_ctx *ctx, const char *const *fens, size_t n, F &&f) {
+  return guarded([&]() -> int {
+    const auto T0 = Clock::now();
+    reset_host_stats(ctx);
+    std::vector<gn_board> boards(n);
+    int rc = gn_pack_fens(fens, n, boards.data(), nullptr);
+    if (rc) return rc;
+    ctx->t_parse = ms_since(T0);
+    rc = f(boards.data());
+    ctx->t_total = ms_since(T0);
+    return rc;
+  });
 }
 
 // ------------------------------------------------- lichess batch replay ----
@@ -1819,6 +1850,31 @@ struct Replay {
   std::string err;
 };
 
+// f(token, length) for each whitespace-separated token of s (space, \t, \n, \r; NULL: none) in
+// turn, until f returns false.
+template <class F>
+static void for_each_token(const char *s, F &&f) {
+  auto space = [](char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; };
+  for (s = s ? s : ""; *s;) {
+    while (space(*s)) ++s;
+    if (!*s) break;
+    const char *e = s;
+    while (*e && !space(*e)) ++e;
+    if (!f(s, (size_t)(e - s))) break;
+    s = e;
+  }
+}
+
+// skip[p] = 1 for the positions p < npos of g's skip list (indices beyond the game are ignored),
+// 0 for the rest; whether any is set.
+static bool skip_mask(const gn_game &g, size_t npos, std::vector<uint8_t> &skip) {
+  skip.assign(npos, 0);
+  bool any = false;
+  for (size_t k = 0; k < g.n_skip && g.skip_positions; ++k)
+    if (g.skip_positions[k] < npos) skip[g.skip_positions[k]] = 1, any = true;
+  return any;
+}
+
 static void replay_game(const gn_game &g, Replay &r) {
   Board B;
   if (!g.root_fen || !parse_fen(g.root_fen, B)) {
@@ -1828,29 +1884,22 @@ static void replay_game(const gn_game &g, Replay &r) {
   gn_board pb;
   pack(B, pb);
   r.boards.push_back(pb);
-  const char *s = g.uci_moves ? g.uci_moves : "";
-  while (*s) {
-    while (*s == ' ' || *s == '\t' || *s == '\n' || *s == '\r') ++s;
-    if (!*s) break;
-    const char *e = s;
-    while (*e && *e != ' ' && *e != '\t' && *e != '\n' && *e != '\r') ++e;
+  for_each_token(g.uci_moves, [&](const char *s, size_t len) {
     uint16_t m = 0;
-    if (!uci_to_move(B, s, (size_t)(e - s), m)) {
+    if (!uci_to_move(B, s, len, m)) {
       char buf[96];
-      snprintf(buf, sizeof(buf), "move %zu (%.*s) is not legal", r.moves.size() + 1, (int)std::min<ptrdiff_t>(e - s, 16), s);
+      snprintf(buf, sizeof(buf), "move %zu (%.*s) is not legal", r.moves.size() + 1, (int)std::min<size_t>(len, 16), s);
       r.rc = GN_E_ILLEGAL_MOVE, r.err = buf;
       r.boards.clear(), r.moves.clear();
-      return;
+      return false;
     }
     B = do_move(B, m);
     pack(B, pb);
     r.boards.push_back(pb);
     r.moves.push_back(m);
-    s = e;
-  }
-  r.skip.assign(r.boards.size(), 0);
-  for (size_t k = 0; k < g.n_skip; ++k)
-    if (g.skip_positions && g.skip_positions[k] < r.skip.size()) r.skip[g.skip_positions[k]] = 1;
+    return true;
+  });
+  if (!r.rc) skip_mask(g, r.boards.size(), r.skip);
 }
 
 // A game prepared on the host for the GPU replay: its root (Position::set on the root FEN)
@@ -1866,29 +1915,307 @@ static void prep_game(const gn_game &g, GamePrep &p) {
   if (!g.root_fen || !parse_fen(g.root_fen, B)) return;
   pack(B, p.root);
   p.ok = true;
-  const char *s = g.uci_moves ? g.uci_moves : "";
-  while (*s) {
-    while (*s == ' ' || *s == '\t' || *s == '\n' || *s == '\r') ++s;
-    if (!*s) break;
-    const char *e = s;
-    while (*e && *e != ' ' && *e != '\t' && *e != '\n' && *e != '\r') ++e;
-    p.codes.push_back(uci_code(s, (int)std::min<ptrdiff_t>(e - s, 6)) );
-    s = e;
-  }
+  for_each_token(g.uci_moves, [&](const char *s, size_t len) {
+    p.codes.push_back(uci_code(s, (int)std::min<size_t>(len, 6)));
+    return true;
+  });
 }
 
 // the text of a game's move k (1-based), for the error message (at most 16 characters)
 static std::string move_token(const gn_game &g, size_t k) {
-  const char *s = g.uci_moves ? g.uci_moves : "";
-  for (size_t i = 1; *s; ++i) {
-    while (*s == ' ' || *s == '\t' || *s == '\n' || *s == '\r') ++s;
-    if (!*s) break;
-    const char *e = s;
-    while (*e && *e != ' ' && *e != '\t' && *e != '\n' && *e != '\r') ++e;
-    if (i == k) return std::string(s, (size_t)std::min<ptrdiff_t>(e - s, 16));
-    s = e;
+  std::string tok;
+  size_t i = 0;
+  for_each_token(g.uci_moves, [&](const char *s, size_t len) {
+    if (++i == k) tok.assign(s, std::min<size_t>(len, 16));
+    return i < k;
+  });
+  return tok;
+}
+
+// ---- gn_evaluate_games, and (n_lines > 0) gn_evaluate_games_lines: the expansion with children,
+// whose chunks are ranked on the device instead of downloaded (no child array, no child capacity).
+
+// One device's share of a games call.  In place (the common case): every game of the device
+// replayed and none has a skipped position, so its evaluated positions are the replay's boards as
+// they lie (rboards: game j's position p at moff[j] + j + p) and one contiguous run of
+// position_out from p0: the expansion reads rboards in place and writes the caller's arrays
+// directly.  Otherwise the evaluated positions are gathered (src: board index, where: output
+// index) into contiguous parents (Dev::par), and their records (res, lres) scattered back.
+struct GameShard {
+  std::vector<size_t> games;        // the device's replayed games (global index)
+  std::vector<uint64_t> moff;       // their move-code offsets (games + 1)
+  std::vector<int32_t> status;      // their status (0 or the first illegal move, 1-based)
+  bool in_place = false;
+  size_t m = 0;                     // evaluated positions
+  size_t p0 = 0;                    // in place: the first one's index in position_out
+  std::vector<uint32_t> src, where; // gathered: each one's board in rboards / index in position_out
+  std::vector<size_t> starts;       // first evaluated position of each game (the chunks' cuts)
+  std::vector<gn_eval> res;         // gathered: the evaluated positions' records ...
+  std::vector<gn_line> lres;        // ... and lines
+  std::vector<uint64_t> off;        // child offsets from pass 1 (m + 1, relative)
+  uint64_t child_base = 0;          // the shard's first child in the caller's arrays
+  bool has() const { return m > 0; }
+  const gn_board *parents_of(const Dev &d) const { return in_place ? d.rboards.p : d.par.p; }
+  gn_eval *records_of(gn_eval *position_out) { return in_place ? position_out + p0 : res.data(); }
+};
+
+// A games call: gn_evaluate_games' arguments, and what its phases hand on.
+struct GamesCall {
+  gn_ctx *ctx;
+  const gn_game *games;
+  size_t n_games;
+  int mode, with_children, n_lines;
+  uint32_t *position_offsets, *child_offsets;
+  int32_t *game_status;
+  gn_eval *position_out;
+  size_t position_cap, child_cap;
+  uint16_t *child_moves;
+  gn_child *child_out;
+  gn_line *lines;
+  std::vector<GamePrep> prep;
+  std::vector<size_t> bounds;    // the devices' game ranges
+  std::vector<GameShard> shards; // one per device
+  std::vector<uint32_t> npos;    // positions per game (0: failed)
+  uint64_t total = 0;            // positions
+  bool all_in_place = true;
+  std::string last_err;          // the last failed game's message (gn_last_error after GN_OK)
+};
+
+// host: root FENs parsed, UCI moves tokenized (the wire form, AcquireResponseBody.moves); games
+// sharded over the devices, never split, weighted by their positions (moves + 1)
+static void games_prepare(GamesCall &c, Clock::time_point T0) {
+  c.prep.resize(c.n_games);
+  parallel_for(c.n_games, 64, [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; ++i) prep_game(c.games[i], c.prep[i]);
+  });
+  c.ctx->t_parse = ms_since(T0);
+  const size_t nd = c.ctx->devs.size();
+  std::vector<uint32_t> w(c.n_games);
+  for (size_t i = 0; i < c.n_games; ++i) w[i] = c.prep[i].ok ? (uint32_t)c.prep[i].codes.size() + 1 : 0;
+  c.bounds.resize(nd + 1);
+  partition(w.data(), c.n_games, (int)nd, c.bounds.data());
+  c.shards.resize(nd);
+}
+
+// phase A: a device replays its games [g0, g1) (replay_games_kernel) and reports their status
+static int games_replay(const GamesCall &c, GameShard &sh, Dev &d, size_t g0, size_t g1) {
+  auto &gl = sh.games;
+  auto &mo = sh.moff;
+  mo.push_back(0);
+  for (size_t g = g0; g < g1; ++g)
+    if (c.prep[g].ok) gl.push_back(g), mo.push_back(mo.back() + c.prep[g].codes.size());
+  const size_t ng = gl.size(), nm = mo.back();
+  if (!ng) return GN_OK;
+  std::vector<uint16_t> codes(std::max<size_t>(nm, 1));
+  std::vector<gn_board> roots(ng);
+  for (size_t j = 0; j < ng; ++j) {
+    roots[j] = c.prep[gl[j]].root;
+    std::copy(c.prep[gl[j]].codes.begin(), c.prep[gl[j]].codes.end(), codes.begin() + mo[j]);
   }
-  return "";
+  const auto t0 = Clock::now();
+  HIP_TRY(d.roots.ensure(ng));
+  HIP_TRY(d.moff.ensure(ng + 1));
+  HIP_TRY(d.codes.ensure(std::max<size_t>(nm, 1)));
+  HIP_TRY(d.rboards.ensure(nm + ng));
+  HIP_TRY(d.smoves.ensure(std::max<size_t>(nm, 1)));
+  HIP_TRY(d.rstatus.ensure(ng));
+  hipStream_t s = d.stream;
+  HIP_TRY(hipMemcpyAsync(d.roots.p, roots.data(), ng * sizeof(gn_board), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d.moff.p, mo.data(), (ng + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d.codes.p, codes.data(), codes.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  d.t_upload += ms_since(t0);
+  const auto t1 = Clock::now();
+  HIP_TRY(launch_replay_games(d.roots.p, ng, d.moff.p, d.codes.p, d.tables, d.rboards.p, d.smoves.p, d.rstatus.p, s));
+  sh.status.resize(ng);
+  HIP_TRY(hipMemcpyAsync(sh.status.data(), d.rstatus.p, ng * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  d.t_replay += ms_since(t1);
+  return GN_OK;
+}
+
+// host: every game's status and position offset into the caller's arrays, then the capacity and
+// NULL checks (the offsets and status are written whatever they find)
+static int games_offsets(GamesCall &c) {
+  std::vector<int32_t> gst(c.n_games, GN_OK);
+  c.npos.assign(c.n_games, 0);
+  for (const GameShard &sh : c.shards)
+    for (size_t j = 0; j < sh.games.size(); ++j) {
+      const size_t g = sh.games[j];
+      if (sh.status[j]) {
+        gst[g] = GN_E_ILLEGAL_MOVE;
+        c.last_err = "move " + std::to_string(sh.status[j]) + " (" + move_token(c.games[g], (size_t)sh.status[j]) +
+                     ") is not legal";
+      } else {
+        c.npos[g] = (uint32_t)(sh.moff[j + 1] - sh.moff[j] + 1);
+      }
+    }
+  for (size_t g = 0; g < c.n_games; ++g) {
+    if (!c.prep[g].ok) gst[g] = GN_E_INVALID, c.last_err = "bad root FEN";
+    c.game_status[g] = gst[g];
+    c.position_offsets[g] = (uint32_t)c.total;
+    c.total += c.npos[g];
+  }
+  if (c.total > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "positions exceed 32-bit offsets");
+  c.position_offsets[c.n_games] = (uint32_t)c.total;
+  if (c.total > c.position_cap)
+    return fail(GN_E_CAPACITY, "%zu positions exceed capacity %zu", (size_t)c.total, c.position_cap);
+  if (c.total && !c.position_out) return fail(GN_E_INVALID, "position_out is NULL");
+  if (c.total && c.n_lines && !c.lines) return fail(GN_E_INVALID, "lines is NULL");
+  return GN_OK;
+}
+
+// host: a shard's evaluated positions, in place or gathered (GameShard); the skipped positions'
+// records are written here
+static void games_layout(const GamesCall &c, GameShard &sh) {
+  std::vector<uint8_t> skip;
+  sh.in_place = true;
+  for (size_t j = 0; j < sh.games.size() && sh.in_place; ++j) {
+    const size_t g = sh.games[j];
+    sh.in_place = sh.status[j] == 0 && !(c.games[g].n_skip && skip_mask(c.games[g], c.npos[g], skip));
+  }
+  if (sh.in_place) {
+    sh.m = sh.games.empty() ? 0 : (size_t)sh.moff.back() + sh.games.size();
+    sh.p0 = sh.games.empty() ? 0 : c.position_offsets[sh.games[0]];
+    for (size_t j = 0; j < sh.games.size(); ++j) sh.starts.push_back((size_t)sh.moff[j] + j);
+    return;
+  }
+  for (size_t j = 0; j < sh.games.size(); ++j) {
+    const size_t g = sh.games[j];
+    if (!c.npos[g]) continue;
+    skip_mask(c.games[g], c.npos[g], skip);
+    sh.starts.push_back(sh.src.size());
+    for (uint32_t p = 0; p < c.npos[g]; ++p) {
+      const size_t at = c.position_offsets[g] + p;
+      if (skip[p]) {
+        c.position_out[at] = gn_eval{0, 0, 0, 0, 0, (uint16_t)(GN_FLAG_SKIPPED | GN_FLAG_NO_SCORE), 0};
+      } else {
+        sh.src.push_back((uint32_t)(sh.moff[j] + j + p));
+        sh.where.push_back((uint32_t)at);
+      }
+    }
+  }
+  sh.m = sh.src.size();
+}
+
+// phase B: (gathered) the evaluated positions gathered into contiguous parents; evaluated (no
+// children) or counted (pass 1 of the expansion)
+static int games_evaluate_or_count(const GamesCall &c, GameShard &sh, Dev &d) {
+  const size_t m = sh.m;
+  hipStream_t s = d.stream;
+  if (!sh.in_place) {
+    const auto t0 = Clock::now();
+    HIP_TRY(d.gidx.ensure(m));
+    HIP_TRY(d.par.ensure(m));
+    HIP_TRY(hipMemcpyAsync(d.gidx.p, sh.src.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_gather_boards(d.rboards.p, d.gidx.p, m, d.par.p, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    d.t_upload += ms_since(t0);
+    sh.res.resize(m);
+    sh.lres.resize(m * (size_t)c.n_lines);
+  }
+  if (c.with_children) return count_shard(d, sh.parents_of(d), m, sh.off);
+  const auto t1 = Clock::now();
+  HIP_TRY(d.io_out.ensure(m));
+  int r = evaluate_on(c.ctx, d, sh.parents_of(d), m, c.mode, d.io_out.p, s, nullptr);
+  if (!r) r = resolve_scores(c.ctx, d, sh.parents_of(d), m, c.mode, d.io_out.p, nullptr, s);
+  if (r) return r;
+  HIP_TRY(hipStreamSynchronize(s));
+  d.t_compute += ms_since(t1);
+  const auto t2 = Clock::now();
+  HIP_TRY(hipMemcpy(sh.records_of(c.position_out), d.io_out.p, m * sizeof(gn_eval), hipMemcpyDeviceToHost));
+  d.t_download += ms_since(t2);
+  return GN_OK;
+}
+
+// host, between the passes: every shard's child base and (gn_evaluate_games; the lines call
+// returns no children: no child offsets, no child capacity) the child offsets over all
+// positions, a skipped one's being the next position's; then the child capacity and NULL checks
+static int games_child_offsets(GamesCall &c) {
+  uint64_t ctot = 0;
+  for (GameShard &sh : c.shards) sh.child_base = ctot, ctot += sh.has() ? sh.off.back() : 0;
+  if (c.n_lines) return GN_OK;
+  if (ctot > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "children exceed 32-bit offsets");
+  uint32_t *const co = c.child_offsets;
+  if (!c.all_in_place)
+    for (size_t g = 0; g < c.n_games; ++g)
+      for (uint32_t p = 0; p < c.npos[g]; ++p) co[c.position_offsets[g] + p] = 0xFFFFFFFFu;
+  for (const GameShard &sh : c.shards) {
+    if (!sh.has()) continue;
+    if (sh.in_place)
+      for (size_t e = 0; e < sh.m; ++e) co[sh.p0 + e] = (uint32_t)(sh.child_base + sh.off[e]);
+    else
+      for (size_t e = 0; e < sh.where.size(); ++e) co[sh.where[e]] = (uint32_t)(sh.child_base + sh.off[e]);
+  }
+  if (!c.all_in_place) {
+    uint32_t next = (uint32_t)ctot;
+    for (size_t at = c.total; at-- > 0;) {
+      if (co[at] == 0xFFFFFFFFu) co[at] = next;
+      else next = co[at];
+    }
+  }
+  co[c.total] = (uint32_t)ctot;
+  if (ctot > c.child_cap) return fail(GN_E_CAPACITY, "%zu children exceed capacity %zu", (size_t)ctot, c.child_cap);
+  if (ctot && (!c.child_moves || !c.child_out)) return fail(GN_E_INVALID, "NULL child buffer");
+  return GN_OK;
+}
+
+// phase C: the expansion pipeline, chunks cut at game starts
+static int games_expand(const GamesCall &c, GameShard &sh, Dev &d) {
+  gn_eval *const rec = sh.records_of(c.position_out);
+  gn_line *const ln = sh.in_place ? c.lines + sh.p0 * (size_t)c.n_lines : sh.lres.data();
+  const ExpandOut o = c.n_lines ? ExpandOut{rec, nullptr, nullptr, c.n_lines, ln}
+                                : ExpandOut{rec, c.child_moves + sh.child_base, c.child_out + sh.child_base};
+  return expand_pipelined(c.ctx, d, sh.parents_of(d), sh.m, c.mode, sh.off,
+                          chunk_plan(sh.m, sh.starts, c.ctx->chunk_parents), o);
+}
+
+// host: the gathered shards' records and lines to their places in the caller's arrays; the
+// skipped positions' lines are empty
+static void games_scatter(const GamesCall &c) {
+  const size_t K = (size_t)c.n_lines;
+  for (const GameShard &sh : c.shards)
+    for (size_t e = 0; e < sh.where.size(); ++e) c.position_out[sh.where[e]] = sh.res[e];
+  if (!K) return;
+  if (!c.all_in_place)
+    for (size_t g = 0; g < c.n_games; ++g)
+      for (size_t at = c.position_offsets[g]; at < c.position_offsets[g + 1]; ++at)
+        if (c.position_out[at].flags & GN_FLAG_SKIPPED)
+          for (size_t j = 0; j < K; ++j) c.lines[at * K + j] = gn_line{0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE};
+  for (const GameShard &sh : c.shards)
+    for (size_t e = 0; e < sh.where.size(); ++e)
+      std::copy(sh.lres.begin() + e * K, sh.lres.begin() + (e + 1) * K, c.lines + (size_t)sh.where[e] * K);
+}
+
+static int evaluate_games(GamesCall c) {
+  if (!slot(c.ctx, 0)) return fail(GN_E_INVALID, "bad context");
+  if (c.n_games && (!c.games || !c.position_offsets || !c.game_status)) return fail(GN_E_INVALID, "NULL argument");
+  if (c.with_children && !c.n_lines && !c.child_offsets) return fail(GN_E_INVALID, "child_offsets is NULL");
+  if (c.mode < GN_MODE_FULL || c.mode > GN_MODE_SMALL) return fail(GN_E_INVALID, "bad mode %d", c.mode);
+  return guarded([&]() -> int {
+    const auto T0 = Clock::now();
+    gn_ctx *const ctx = c.ctx;
+    reset_host_stats(ctx);
+    games_prepare(c, T0);
+    const auto locks = lock_devices(ctx);
+    int rc = run_shards(ctx, c.bounds, [&](size_t k, Dev &d, size_t g0, size_t g1) -> int {
+      return games_replay(c, c.shards[k], d, g0, g1);
+    });
+    if (rc || (rc = games_offsets(c)) != GN_OK) return rc;
+    for (GameShard &sh : c.shards) games_layout(c, sh), c.all_in_place = c.all_in_place && sh.in_place;
+    auto has = [&](size_t k) { return c.shards[k].has(); };
+    rc = run_devices(ctx, has, [&](size_t k, Dev &d) -> int { return games_evaluate_or_count(c, c.shards[k], d); });
+    if (rc) return rc;
+    if (c.with_children) {
+      if ((rc = games_child_offsets(c)) != GN_OK) return rc;
+      rc = run_devices(ctx, has, [&](size_t k, Dev &d) -> int { return games_expand(c, c.shards[k], d); });
+      if (rc) return rc;
+    }
+    games_scatter(c);
+    ctx->t_total = ms_since(T0);
+    if (!c.last_err.empty()) g_err = c.last_err;
+    return GN_OK;
+  });
 }
 
 // ============================================================ C-ABI ========
@@ -1897,7 +2224,7 @@ extern "C" {
 int gn_replay_game(const gn_game *game, gn_board *positions, uint8_t *skipped, uint16_t *moves, size_t cap,
                    size_t *n_positions) {
   if (!game || !n_positions) return fail(GN_E_INVALID, "NULL argument");
-  try {
+  return guarded([&]() -> int {
     Replay r;
     replay_game(*game, r);
     *n_positions = r.boards.size();
@@ -1907,286 +2234,27 @@ int gn_replay_game(const gn_game *game, gn_board *positions, uint8_t *skipped, u
     if (skipped) memcpy(skipped, r.skip.data(), r.skip.size());
     if (moves && !r.moves.empty()) memcpy(moves, r.moves.data(), r.moves.size() * sizeof(uint16_t));
     return GN_OK;
-  } catch (const std::bad_alloc &) {
-    return fail(GN_E_NOMEM, "host allocation failed");
-  }
-}
-
-// gn_evaluate_games, and (n_lines > 0) gn_evaluate_games_lines: the expansion with children,
-// whose chunks are ranked on the device instead of downloaded (no child array, no child capacity).
-static int evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int with_children,
-                          uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out, size_t position_cap,
-                          uint32_t *child_offsets, uint16_t *child_moves, gn_child *child_out, size_t child_cap,
-                          int n_lines, gn_line *lines) {
-  if (!slot(ctx, 0)) return fail(GN_E_INVALID, "bad context");
-  if (n_games && (!games || !position_offsets || !game_status)) return fail(GN_E_INVALID, "NULL argument");
-  if (with_children && !n_lines && !child_offsets) return fail(GN_E_INVALID, "child_offsets is NULL");
-  if (mode < GN_MODE_FULL || mode > GN_MODE_SMALL) return fail(GN_E_INVALID, "bad mode %d", mode);
-  try {
-    const auto T0 = Clock::now();
-    reset_host_stats(ctx);
-    // host: root FENs parsed, UCI moves tokenized (the wire form, AcquireResponseBody.moves)
-    std::vector<GamePrep> prep(n_games);
-    parallel_for(n_games, 64, [&](size_t lo, size_t hi) {
-      for (size_t i = lo; i < hi; ++i) prep_game(games[i], prep[i]);
-    });
-    ctx->t_parse = ms_since(T0);
-    // games sharded over the devices, never split, weighted by their positions (moves + 1)
-    const size_t nd = ctx->devs.size();
-    std::vector<uint32_t> w(n_games);
-    for (size_t i = 0; i < n_games; ++i) w[i] = prep[i].ok ? (uint32_t)prep[i].codes.size() + 1 : 0;
-    std::vector<size_t> gb(nd + 1);
-    partition(w.data(), n_games, (int)nd, gb.data());
-    std::vector<std::unique_lock<std::mutex>> locks; // every device lock for the whole call
-    for (auto &dp : ctx->devs) locks.emplace_back(dp->mu);
-    // phase A: each device replays its games (replay_games_kernel) and reports their status
-    std::vector<std::vector<size_t>> glist(nd);  // the device's replayed games (global index)
-    std::vector<std::vector<uint64_t>> moff(nd); // their move-code offsets
-    std::vector<std::vector<int32_t>> st(nd);    // their status (0 or the first illegal move)
-    int rc = run_shards(ctx, gb, [&](size_t k, Dev &d, size_t g0, size_t g1) -> int {
-      HIP_TRY(hipSetDevice(d.id));
-      SeqGuard sg(d, d.stream);
-      HIP_TRY(sg.e);
-      auto &gl = glist[k];
-      auto &mo = moff[k];
-      mo.push_back(0);
-      for (size_t g = g0; g < g1; ++g)
-        if (prep[g].ok) gl.push_back(g), mo.push_back(mo.back() + prep[g].codes.size());
-      const size_t ng = gl.size(), nm = mo.back();
-      if (!ng) return GN_OK;
-      std::vector<uint16_t> codes(std::max<size_t>(nm, 1));
-      std::vector<gn_board> roots(ng);
-      for (size_t j = 0; j < ng; ++j) {
-        roots[j] = prep[gl[j]].root;
-        std::copy(prep[gl[j]].codes.begin(), prep[gl[j]].codes.end(), codes.begin() + mo[j]);
-      }
-      const auto t0 = Clock::now();
-      HIP_TRY(d.roots.ensure(ng));
-      HIP_TRY(d.moff.ensure(ng + 1));
-      HIP_TRY(d.codes.ensure(std::max<size_t>(nm, 1)));
-      HIP_TRY(d.rboards.ensure(nm + ng));
-      HIP_TRY(d.smoves.ensure(std::max<size_t>(nm, 1)));
-      HIP_TRY(d.rstatus.ensure(ng));
-      hipStream_t s = d.stream;
-      HIP_TRY(hipMemcpyAsync(d.roots.p, roots.data(), ng * sizeof(gn_board), hipMemcpyHostToDevice, s));
-      HIP_TRY(hipMemcpyAsync(d.moff.p, mo.data(), (ng + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-      HIP_TRY(hipMemcpyAsync(d.codes.p, codes.data(), codes.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      d.t_upload += ms_since(t0);
-      const auto t1 = Clock::now();
-      HIP_TRY(launch_replay_games(d.roots.p, ng, d.moff.p, d.codes.p, d.tables, d.rboards.p, d.smoves.p, d.rstatus.p, s));
-      st[k].resize(ng);
-      HIP_TRY(hipMemcpyAsync(st[k].data(), d.rstatus.p, ng * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      d.t_replay += ms_since(t1);
-      return GN_OK;
-    });
-    if (rc) return rc;
-    // host: status, position offsets; the evaluated (non-skipped) positions of each device
-    std::vector<int32_t> gst(n_games, GN_OK);
-    std::vector<uint32_t> npos(n_games, 0);
-    std::string last_err;
-    for (size_t k = 0; k < nd; ++k)
-      for (size_t j = 0; j < glist[k].size(); ++j) {
-        const size_t g = glist[k][j];
-        if (st[k][j]) {
-          gst[g] = GN_E_ILLEGAL_MOVE;
-          last_err = "move " + std::to_string(st[k][j]) + " (" + move_token(games[g], (size_t)st[k][j]) + ") is not legal";
-        } else {
-          npos[g] = (uint32_t)(moff[k][j + 1] - moff[k][j] + 1);
-        }
-      }
-    uint64_t total = 0;
-    for (size_t g = 0; g < n_games; ++g) {
-      if (!prep[g].ok) gst[g] = GN_E_INVALID, last_err = "bad root FEN";
-      game_status[g] = gst[g];
-      position_offsets[g] = (uint32_t)total;
-      total += npos[g];
-    }
-    if (total > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "positions exceed 32-bit offsets");
-    position_offsets[n_games] = (uint32_t)total;
-    if (total > position_cap) return fail(GN_E_CAPACITY, "%zu positions exceed capacity %zu", (size_t)total, position_cap);
-    if (total && !position_out) return fail(GN_E_INVALID, "position_out is NULL");
-    if (total && n_lines && !lines) return fail(GN_E_INVALID, "lines is NULL");
-    // The evaluated positions of each device.  Fast path (the common case): every game of the
-    // device replayed and none has a skipped position, so its positions are the replay's boards
-    // as they lie (rboards: game j's position p at moff[j] + j + p) and one contiguous run of
-    // position_out from p0[k]: the expansion reads rboards in place and writes the caller's
-    // arrays directly.  Otherwise the evaluated positions are gathered (src: board index,
-    // where: output index) into contiguous parents and their records scattered back.
-    std::vector<std::vector<uint32_t>> src(nd), where(nd);
-    std::vector<std::vector<size_t>> starts(nd); // first evaluated position of each game
-    std::vector<uint8_t> fast(nd, 0);
-    std::vector<size_t> mcount(nd, 0), p0(nd, 0);
-    std::vector<uint8_t> skip;
-    for (size_t k = 0; k < nd; ++k) {
-      bool f = true;
-      for (size_t j = 0; j < glist[k].size() && f; ++j) {
-        const size_t g = glist[k][j];
-        f = st[k][j] == 0;
-        for (size_t q = 0; q < games[g].n_skip && f; ++q)
-          f = !games[g].skip_positions || games[g].skip_positions[q] >= npos[g];
-      }
-      if (f) {
-        fast[k] = 1;
-        mcount[k] = glist[k].empty() ? 0 : (size_t)moff[k].back() + glist[k].size();
-        p0[k] = glist[k].empty() ? 0 : position_offsets[glist[k][0]];
-        for (size_t j = 0; j < glist[k].size(); ++j) starts[k].push_back((size_t)moff[k][j] + j);
-        continue;
-      }
-      for (size_t j = 0; j < glist[k].size(); ++j) {
-        const size_t g = glist[k][j];
-        if (!npos[g]) continue;
-        skip.assign(npos[g], 0);
-        for (size_t q = 0; q < games[g].n_skip; ++q)
-          if (games[g].skip_positions && games[g].skip_positions[q] < npos[g]) skip[games[g].skip_positions[q]] = 1;
-        starts[k].push_back(src[k].size());
-        for (uint32_t p = 0; p < npos[g]; ++p) {
-          const size_t at = position_offsets[g] + p;
-          if (skip[p]) {
-            position_out[at] = gn_eval{0, 0, 0, 0, 0, (uint16_t)(GN_FLAG_SKIPPED | GN_FLAG_NO_SCORE), 0};
-          } else {
-            src[k].push_back((uint32_t)(moff[k][j] + j + p));
-            where[k].push_back((uint32_t)at);
-          }
-        }
-      }
-      mcount[k] = src[k].size();
-    }
-    // phase B: (slow path) the evaluated positions gathered into contiguous parents; evaluated
-    // (no children) or counted (pass 1 of the expansion)
-    std::vector<std::vector<gn_eval>> res(nd);
-    std::vector<std::vector<gn_line>> lres(nd); // (slow path) the evaluated positions' lines
-    const size_t K = (size_t)n_lines;
-    std::vector<std::vector<uint64_t>> off(nd);
-    std::vector<size_t> db(nd + 1);
-    for (size_t k = 0; k <= nd; ++k) db[k] = k; // one "item" per device: run_shards' shard k = device k
-    auto has = [&](size_t k) { return mcount[k] > 0; };
-    auto parents_of = [&](size_t k) -> const gn_board * { return fast[k] ? ctx->devs[k]->rboards.p : ctx->devs[k]->par.p; };
-    auto records_of = [&](size_t k) -> gn_eval * { return fast[k] ? position_out + p0[k] : res[k].data(); };
-    rc = run_shards(ctx, db, [&](size_t k, Dev &d, size_t, size_t) -> int {
-      if (!has(k)) return GN_OK;
-      HIP_TRY(hipSetDevice(d.id));
-      SeqGuard sg(d, d.stream);
-      HIP_TRY(sg.e);
-      const size_t m = mcount[k];
-      hipStream_t s = d.stream;
-      if (!fast[k]) {
-        const auto t0 = Clock::now();
-        HIP_TRY(d.gidx.ensure(m));
-        HIP_TRY(d.par.ensure(m));
-        HIP_TRY(hipMemcpyAsync(d.gidx.p, src[k].data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(launch_gather_boards(d.rboards.p, d.gidx.p, m, d.par.p, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        d.t_upload += ms_since(t0);
-        res[k].resize(m);
-        lres[k].resize(m * K);
-      }
-      if (with_children) return count_shard(d, parents_of(k), m, off[k]);
-      const auto t1 = Clock::now();
-      HIP_TRY(d.io_out.ensure(m));
-      int r = evaluate_on(ctx, d, parents_of(k), m, mode, d.io_out.p, s, nullptr);
-      if (!r) r = resolve_scores(ctx, d, parents_of(k), m, mode, d.io_out.p, nullptr, s);
-      if (r) return r;
-      HIP_TRY(hipStreamSynchronize(s));
-      d.t_compute += ms_since(t1);
-      const auto t2 = Clock::now();
-      HIP_TRY(hipMemcpy(records_of(k), d.io_out.p, m * sizeof(gn_eval), hipMemcpyDeviceToHost));
-      d.t_download += ms_since(t2);
-      return GN_OK;
-    });
-    if (rc) return rc;
-    if (with_children) {
-      std::vector<uint64_t> cb(nd + 1, 0);
-      for (size_t k = 0; k < nd; ++k) cb[k + 1] = cb[k] + (has(k) ? off[k].back() : 0);
-      const uint64_t ctot = cb[nd];
-      if (!n_lines) { // (the lines call returns no children: no child offsets, no child capacity)
-        if (ctot > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "children exceed 32-bit offsets");
-        // child offsets over all positions (skipped ones: no children, the next position's offset)
-        const bool all_fast = std::all_of(fast.begin(), fast.end(), [](uint8_t f) { return f != 0; });
-        if (!all_fast)
-          for (size_t g = 0; g < n_games; ++g)
-            for (uint32_t p = 0; p < npos[g]; ++p) child_offsets[position_offsets[g] + p] = 0xFFFFFFFFu;
-        for (size_t k = 0; k < nd; ++k) {
-          if (!has(k)) continue;
-          if (fast[k])
-            for (size_t e = 0; e < mcount[k]; ++e) child_offsets[p0[k] + e] = (uint32_t)(cb[k] + off[k][e]);
-          else
-            for (size_t e = 0; e < where[k].size(); ++e) child_offsets[where[k][e]] = (uint32_t)(cb[k] + off[k][e]);
-        }
-        if (!all_fast) {
-          uint32_t next = (uint32_t)ctot;
-          for (size_t at = total; at-- > 0;) {
-            if (child_offsets[at] == 0xFFFFFFFFu) child_offsets[at] = next;
-            else next = child_offsets[at];
-          }
-        }
-        child_offsets[total] = (uint32_t)ctot;
-        if (ctot > child_cap) return fail(GN_E_CAPACITY, "%zu children exceed capacity %zu", (size_t)ctot, child_cap);
-        if (ctot && (!child_moves || !child_out)) return fail(GN_E_INVALID, "NULL child buffer");
-      }
-      // phase C: the expansion pipeline, chunks cut at game starts
-      rc = run_shards(ctx, db, [&](size_t k, Dev &d, size_t, size_t) -> int {
-        if (!has(k)) return GN_OK;
-        HIP_TRY(hipSetDevice(d.id));
-        SeqGuard sg(d, d.stream);
-        HIP_TRY(sg.e);
-        const size_t m = mcount[k];
-        if (n_lines)
-          return expand_pipelined(ctx, d, parents_of(k), m, mode, off[k], chunk_plan(m, starts[k], ctx->chunk_parents),
-                                  records_of(k), nullptr, nullptr, n_lines,
-                                  fast[k] ? lines + p0[k] * K : lres[k].data());
-        return expand_pipelined(ctx, d, parents_of(k), m, mode, off[k], chunk_plan(m, starts[k], ctx->chunk_parents),
-                                records_of(k), child_moves + cb[k], child_out + cb[k]);
-      });
-      if (rc) return rc;
-    }
-    for (size_t k = 0; k < nd; ++k)
-      for (size_t e = 0; e < where[k].size(); ++e) position_out[where[k][e]] = res[k][e];
-    if (n_lines) { // (slow path) skipped positions: empty lines; the evaluated ones' from lres
-      const bool all_fast = std::all_of(fast.begin(), fast.end(), [](uint8_t f) { return f != 0; });
-      if (!all_fast)
-        for (size_t g = 0; g < n_games; ++g)
-          for (size_t at = position_offsets[g]; at < position_offsets[g + 1]; ++at)
-            if (position_out[at].flags & GN_FLAG_SKIPPED)
-              for (size_t j = 0; j < K; ++j) lines[at * K + j] = gn_line{0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE};
-      for (size_t k = 0; k < nd; ++k)
-        for (size_t e = 0; e < where[k].size(); ++e)
-          std::copy(lres[k].begin() + e * K, lres[k].begin() + (e + 1) * K, lines + (size_t)where[k][e] * K);
-    }
-    ctx->t_total = ms_since(T0);
-    if (!last_err.empty()) g_err = last_err;
-    return GN_OK;
-  } catch (const std::bad_alloc &) {
-    return fail(GN_E_NOMEM, "host allocation failed");
-  } catch (...) {
-    return fail(GN_E_INVALID, "unexpected exception");
-  }
+  });
 }
 
 int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int with_children,
                       uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out, size_t position_cap,
                       uint32_t *child_offsets, uint16_t *child_moves, gn_child *child_out, size_t child_cap) {
-  return evaluate_games(ctx, games, n_games, mode, with_children, position_offsets, game_status, position_out,
-                        position_cap, child_offsets, child_moves, child_out, child_cap, 0, nullptr);
+  return evaluate_games({ctx, games, n_games, mode, with_children, 0, position_offsets, child_offsets, game_status,
+                         position_out, position_cap, child_cap, child_moves, child_out, nullptr});
 }
 
 int gn_evaluate_games_lines(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                             uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                             size_t position_cap, gn_line *lines) {
   if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
-  return evaluate_games(ctx, games, n_games, mode, 1, position_offsets, game_status, position_out, position_cap,
-                        nullptr, nullptr, nullptr, 0, n_lines, lines);
+  return evaluate_games({ctx, games, n_games, mode, 1, n_lines, position_offsets, nullptr, game_status, position_out,
+                         position_cap, 0, nullptr, nullptr, lines});
 }
 
 int gn_partition(const uint32_t *weights, size_t n_items, int n_shards, size_t *bounds) {
   if (n_shards <= 0 || !bounds) return fail(GN_E_INVALID, "bad shard count / NULL bounds");
-  try {
-    partition(weights, n_items, n_shards, bounds);
-  } catch (...) {
-    return fail(GN_E_INVALID, "unexpected exception");
-  }
-  return GN_OK;
+  return guarded([&]() -> int { return partition(weights, n_items, n_shards, bounds), GN_OK; });
 }
 
 int gn_abi_version(void) { return GN_ABI_VERSION; }
@@ -2220,7 +2288,7 @@ int gn_net_sha256(const uint8_t *data, size_t len, char *hex65) {
 }
 
 int gn_load_net(const char *big_path, const char *small_path, const int *devices, int n_devices, gn_ctx **out) {
-  try {
+  return guarded([&]() -> int {
     std::vector<uint8_t> b, s;
     if (big_path && !read_file(big_path, b)) return fail(GN_E_IO, "cannot read %s", big_path);
     if (small_path && !read_file(small_path, s)) return fail(GN_E_IO, "cannot read %s", small_path);
@@ -2229,11 +2297,7 @@ int gn_load_net(const char *big_path, const char *small_path, const int *devices
     if (small_path && (rc = check_net_name(small_path, s)) != GN_OK) return rc;
     return create(big_path ? b.data() : nullptr, b.size(), small_path ? s.data() : nullptr, s.size(), devices,
                   n_devices, out);
-  } catch (const std::bad_alloc &) {
-    return fail(GN_E_NOMEM, "host allocation failed");
-  } catch (...) {
-    return fail(GN_E_INVALID, "unexpected exception");
-  }
+  });
 }
 
 // L1 width of a .nnue image from its header hashes (0: not a supported net)
@@ -2259,7 +2323,7 @@ static int read_archive(const char *path, std::vector<uint8_t> &img, std::vector
 }
 
 int gn_archive_read(const char *path, const char *member, uint8_t *buf, size_t cap, size_t *size) {
-  try {
+  return guarded([&]() -> int {
     if (!member || !size) return fail(GN_E_INVALID, "bad argument");
     std::vector<uint8_t> img;
     std::vector<archive::Member> mem;
@@ -2273,16 +2337,12 @@ int gn_archive_read(const char *path, const char *member, uint8_t *buf, size_t c
         return GN_OK;
       }
     return fail(GN_E_IO, "%s has no member %s", path, member);
-  } catch (const std::bad_alloc &) {
-    return fail(GN_E_NOMEM, "host allocation failed");
-  } catch (...) {
-    return fail(GN_E_INVALID, "unexpected exception");
-  }
+  });
 }
 
 int gn_load_net_archive(const char *path, const char *big_member, const char *small_member, const int *devices,
                         int n_devices, gn_ctx **out) {
-  try {
+  return guarded([&]() -> int {
     std::vector<uint8_t> img;
     std::vector<archive::Member> mem;
     int rc = read_archive(path, img, mem);
@@ -2311,22 +2371,12 @@ int gn_load_net_archive(const char *path, const char *big_member, const char *sm
     return create(pick[0] ? img.data() + pick[0]->off : nullptr, pick[0] ? pick[0]->size : 0,
                   pick[1] ? img.data() + pick[1]->off : nullptr, pick[1] ? pick[1]->size : 0, devices, n_devices,
                   out);
-  } catch (const std::bad_alloc &) {
-    return fail(GN_E_NOMEM, "host allocation failed");
-  } catch (...) {
-    return fail(GN_E_INVALID, "unexpected exception");
-  }
+  });
 }
 
 int gn_load_net_memory(const uint8_t *big, size_t big_len, const uint8_t *small, size_t small_len, const int *devices,
                        int n_devices, gn_ctx **out) {
-  try {
-    return create(big, big_len, small, small_len, devices, n_devices, out);
-  } catch (const std::bad_alloc &) {
-    return fail(GN_E_NOMEM, "host allocation failed");
-  } catch (...) {
-    return fail(GN_E_INVALID, "unexpected exception");
-  }
+  return guarded([&]() -> int { return create(big, big_len, small, small_len, devices, n_devices, out); });
 }
 
 void gn_free(gn_ctx *ctx) { destroy(ctx); }
@@ -2430,15 +2480,13 @@ int gn_evaluate_device(gn_ctx *ctx, int device_slot, const gn_board *d_boards, s
   Dev *d = slot(ctx, device_slot);
   if (!d) return fail(GN_E_INVALID, "bad context or device slot");
   if (n && (!d_boards || !d_out)) return fail(GN_E_INVALID, "NULL buffer");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
-  SeqGuard sg(*d, s);
-  HIP_TRY(sg.e);
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  const hipStream_t s = call.s;
   int rc = evaluate_on(ctx, *d, d_boards, n, mode, d_out, s, nullptr);
   if (!rc) rc = resolve_scores(ctx, *d, d_boards, n, mode, d_out, nullptr, s);
   if (rc) return rc;
-  HIP_TRY(sg.finish()); // blocking (gpu_nnue.h): d_out is written when the call returns
+  HIP_TRY(call.sg->finish()); // blocking (gpu_nnue.h): d_out is written when the call returns
   return GN_OK;
 }
 
@@ -2447,10 +2495,8 @@ int gn_time_evaluate_device(gn_ctx *ctx, int device_slot, const gn_board *d_boar
   Dev *d = slot(ctx, device_slot);
   if (!d) return fail(GN_E_INVALID, "bad context or device slot");
   if (iters <= 0 || !ms_total) return fail(GN_E_INVALID, "bad iters / ms_total");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  SeqGuard sg(*d, d->stream);
-  HIP_TRY(sg.e);
+  DevCall call(*d);
+  if (call.rc) return call.rc;
   std::vector<hipEvent_t> ev((size_t)iters * 5 + 2, nullptr);
   auto cleanup = [&] {
     for (auto &e : ev)
@@ -2525,11 +2571,9 @@ int gn_random_positions_device(gn_ctx *ctx, int device_slot, uint64_t seed, size
   if (!d) return fail(GN_E_INVALID, "bad context or device slot");
   if (n && !d_out) return fail(GN_E_INVALID, "NULL buffer");
   if (max_plies < 0) return fail(GN_E_INVALID, "max_plies < 0");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  SeqGuard sg(*d, stream ? (hipStream_t)stream : d->stream);
-  HIP_TRY(sg.e);
-  HIP_TRY(launch_random_positions(seed, first_index, n, max_plies, d->tables, d_out, sg.s));
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_random_positions(seed, first_index, n, max_plies, d->tables, d_out, call.s));
   return GN_OK;
 }
 
@@ -2552,10 +2596,8 @@ int gn_device_free(gn_ctx *ctx, int device_slot, void *ptr) {
 int gn_memcpy_h2d(gn_ctx *ctx, int device_slot, void *dst, const void *src, size_t bytes) {
   Dev *d = slot(ctx, device_slot);
   if (!d) return fail(GN_E_INVALID, "bad argument");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  SeqGuard sg(*d, d->stream);
-  HIP_TRY(sg.e);
+  DevCall call(*d);
+  if (call.rc) return call.rc;
   HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   return GN_OK;
@@ -2564,10 +2606,8 @@ int gn_memcpy_h2d(gn_ctx *ctx, int device_slot, void *dst, const void *src, size
 int gn_memcpy_d2h(gn_ctx *ctx, int device_slot, void *dst, const void *src, size_t bytes) {
   Dev *d = slot(ctx, device_slot);
   if (!d) return fail(GN_E_INVALID, "bad argument");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  SeqGuard sg(*d, d->stream);
-  HIP_TRY(sg.e);
+  DevCall call(*d);
+  if (call.rc) return call.rc;
   HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   return GN_OK;
@@ -2587,16 +2627,12 @@ int gn_evaluate_batch_mode(gn_ctx *ctx, const char *const *fens, size_t n, int m
   if (!ctx) return fail(GN_E_INVALID, "ctx is NULL");
   if (n && (!fens || !out)) return fail(GN_E_INVALID, "NULL argument");
   if (!n) return GN_OK;
-  try {
+  return guarded([&]() -> int {
     std::vector<gn_board> boards(n);
     int rc = gn_pack_fens(fens, n, boards.data(), nullptr);
     if (rc) return rc;
     return evaluate_coalesced(ctx, boards.data(), n, mode, out);
-  } catch (const std::bad_alloc &) {
-    return fail(GN_E_NOMEM, "host allocation failed");
-  } catch (...) {
-    return fail(GN_E_INVALID, "unexpected exception");
-  }
+  });
 }
 
 int gn_evaluate_batch(gn_ctx *ctx, const char *const *fens, size_t n, gn_eval *out) {
@@ -2609,11 +2645,9 @@ int gn_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, si
   Dev *d = slot(ctx, device_slot);
   if (!d || !total) return fail(GN_E_INVALID, "bad argument");
   if (n && (!d_parents || !d_offsets)) return fail(GN_E_INVALID, "NULL buffer");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
-  SeqGuard sg(*d, s);
-  HIP_TRY(sg.e);
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  const hipStream_t s = call.s;
   *total = 0;
   if (!n) return GN_OK;
   if (!d_children || !d_moves || !d_child_out) return fail(GN_E_INVALID, "NULL child buffer");
@@ -2649,11 +2683,9 @@ int gn_rank_children_device(gn_ctx *ctx, int device_slot, const gn_board *d_pare
   if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
   // (d_moves / d_child_out may be NULL when no parent has a child: they are then never read)
   if (n && (!d_parents || !d_offsets || !d_lines)) return fail(GN_E_INVALID, "NULL buffer");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  SeqGuard sg(*d, stream ? (hipStream_t)stream : d->stream);
-  HIP_TRY(sg.e);
-  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables, n_lines, d_lines, sg.s));
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables, n_lines, d_lines, call.s));
   return GN_OK;
 }
 
@@ -2747,13 +2779,10 @@ int gn_expand2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, s
   Dev *d = slot(ctx, device_slot);
   if (!d || !total || !gtotal) return fail(GN_E_INVALID, "bad argument");
   if (n && (!d_parents || !d_offsets)) return fail(GN_E_INVALID, "NULL buffer");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
-  SeqGuard sg(*d, s);
-  HIP_TRY(sg.e);
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
   return expand2_on(ctx, d, d_parents, n, mode, d_parent_out, d_offsets, d_children, d_moves, d_child_out, cap,
-                    Expand2Grand{d_goffsets, d_gmoves, d_grand_out, gcap}, total, gtotal, s);
+                    Expand2Grand{d_goffsets, d_gmoves, d_grand_out, gcap}, total, gtotal, call.s);
 }
 
 int gn_rank_lines2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
@@ -2765,12 +2794,10 @@ int gn_rank_lines2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parent
   if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
   // (the child and grandchild buffers may be NULL when no parent has a child: they are then never read)
   if (n && (!d_parents || !d_offsets || !d_lines)) return fail(GN_E_INVALID, "NULL buffer");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  SeqGuard sg(*d, stream ? (hipStream_t)stream : d->stream);
-  HIP_TRY(sg.e);
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
   HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
-                             ctx->P, d->tables, n_lines, d_lines, sg.s));
+                             ctx->P, d->tables, n_lines, d_lines, call.s));
   return GN_OK;
 }
 
@@ -2779,11 +2806,9 @@ int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parent
                           uint32_t *d_offsets, uint16_t *d_moves, gn_eval *d_child_out, size_t cap) {
   Dev *d = slot(ctx, device_slot);
   if (!d || !ms_total || !total || iters <= 0) return fail(GN_E_INVALID, "bad argument");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  hipStream_t s = d->stream;
-  SeqGuard sg(*d, s);
-  HIP_TRY(sg.e);
+  DevCall call(*d);
+  if (call.rc) return call.rc;
+  const hipStream_t s = call.s;
   // start, [count+scan], [total read], [write], [classify], [small], [big], [finalize], the
   // planned big net's plan -> stream boundary, [score rule] (ends at e[9]), and the stream ->
   // finish boundary (e[10])
@@ -2870,10 +2895,8 @@ int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parent
 int gn_checksum_device(gn_ctx *ctx, int device_slot, const void *d_ptr, size_t bytes, uint64_t *sum) {
   Dev *d = slot(ctx, device_slot);
   if (!d || !sum || (bytes && !d_ptr)) return fail(GN_E_INVALID, "bad argument");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  SeqGuard sg(*d, d->stream);
-  HIP_TRY(sg.e);
+  DevCall call(*d);
+  if (call.rc) return call.rc;
   HIP_TRY(d->sum.ensure(2));
   HIP_TRY(hipMemsetAsync(d->sum.p, 0, sizeof(unsigned long long), d->stream));
   HIP_TRY(launch_checksum(d_ptr, bytes, d->sum.p, d->stream));
@@ -2890,11 +2913,9 @@ int gn_random_games_device(gn_ctx *ctx, int device_slot, uint64_t seed, size_t f
   if (!d) return fail(GN_E_INVALID, "bad context or device slot");
   if (n_games && !d_out) return fail(GN_E_INVALID, "NULL buffer");
   if (plies < 0 || plies > 1000) return fail(GN_E_INVALID, "plies out of range");
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  SeqGuard sg(*d, stream ? (hipStream_t)stream : d->stream);
-  HIP_TRY(sg.e);
-  HIP_TRY(launch_random_games(seed, first_game, n_games, plies, d->tables, d_out, sg.s));
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_random_games(seed, first_game, n_games, plies, d->tables, d_out, call.s));
   return GN_OK;
 }
 
@@ -3052,21 +3073,9 @@ int gn_expand_and_evaluate(gn_ctx *ctx, const char *const *parent_fens, size_t n
     if (child_offsets) child_offsets[0] = 0;
     return GN_OK;
   }
-  try {
-    const auto T0 = Clock::now();
-    reset_host_stats(ctx);
-    std::vector<gn_board> boards(n);
-    int rc = gn_pack_fens(parent_fens, n, boards.data(), nullptr);
-    if (rc) return rc;
-    ctx->t_parse = ms_since(T0);
-    rc = expand_boards_host(ctx, boards.data(), n, mode, parent_out, child_offsets, child_moves, child_out, cap);
-    ctx->t_total = ms_since(T0);
-    return rc;
-  } catch (const std::bad_alloc &) {
-    return fail(GN_E_NOMEM, "host allocation failed");
-  } catch (...) {
-    return fail(GN_E_INVALID, "unexpected exception");
-  }
+  return on_packed_fens(ctx, parent_fens, n, [&](const gn_board *boards) -> int {
+    return expand_boards_host(ctx, boards, n, mode, parent_out, child_offsets, child_moves, child_out, cap);
+  });
 }
 
 // Two-ply ranked lines from host boards (gn_evaluate_lines2): each device's shard in chunks of
@@ -3077,15 +3086,11 @@ static int lines2_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int
   const size_t nd = ctx->devs.size();
   std::vector<size_t> b(nd + 1);
   partition(nullptr, n, (int)nd, b.data());
-  std::vector<std::unique_lock<std::mutex>> locks; // every device lock for the whole call
-  for (auto &dp : ctx->devs) locks.emplace_back(dp->mu);
+  const auto locks = lock_devices(ctx);
   // 1,024 parents are ~1 M grandchildren: a few hundred MB of records, boards and partial sums
   const size_t chunk = ctx->chunk_parents > 0 ? (size_t)ctx->chunk_parents : 1024;
   return run_shards(ctx, b, [&](size_t, Dev &d, size_t lo, size_t hi) -> int {
-    HIP_TRY(hipSetDevice(d.id));
     hipStream_t s = d.stream;
-    SeqGuard sg(d, s);
-    HIP_TRY(sg.e);
     Dev::Lines2 &x = d.l2;
     auto t0 = Clock::now();
     HIP_TRY(d.par.ensure(hi - lo));
@@ -3139,21 +3144,9 @@ int gn_evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode,
   if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
   if (n && (!fens || !out || !lines)) return fail(GN_E_INVALID, "NULL argument");
   if (!n) return GN_OK;
-  try {
-    const auto T0 = Clock::now();
-    reset_host_stats(ctx);
-    std::vector<gn_board> boards(n);
-    int rc = gn_pack_fens(fens, n, boards.data(), nullptr);
-    if (rc) return rc;
-    ctx->t_parse = ms_since(T0);
-    rc = lines2_boards_host(ctx, boards.data(), n, mode, n_lines, out, lines);
-    ctx->t_total = ms_since(T0);
-    return rc;
-  } catch (const std::bad_alloc &) {
-    return fail(GN_E_NOMEM, "host allocation failed");
-  } catch (...) {
-    return fail(GN_E_INVALID, "unexpected exception");
-  }
+  return on_packed_fens(ctx, fens, n, [&](const gn_board *boards) -> int {
+    return lines2_boards_host(ctx, boards, n, mode, n_lines, out, lines);
+  });
 }
 
 int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {
@@ -3165,11 +3158,9 @@ int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {
     *nodes = 1;
     return GN_OK;
   }
-  std::lock_guard<std::mutex> lk(d->mu);
-  HIP_TRY(hipSetDevice(d->id));
-  hipStream_t s = d->stream;
-  SeqGuard sg(*d, s);
-  HIP_TRY(sg.e);
+  DevCall call(*d);
+  if (call.rc) return call.rc;
+  const hipStream_t s = call.s;
   gn_board root;
   pack(B, root);
   HIP_TRY(d->frontier.ensure(1));

@@ -341,3 +341,114 @@ def test_chained_links_of_special_moves_vs_oracle(gpu_ctx, oracle_nets, oracle_l
             assert tuple(o["evals"][i]) == tuple(p_exp), fen
             assert dict(zip(cm.tolist(), map(tuple, ce.tolist()))) == \
                 dict(zip(m_exp, map(tuple, G.children_from_evals(k_exp).tolist()))), fen
+
+
+# ---- the move string's tokens (whitespace-separated; tabs, CR LF and runs of spaces included) ----
+LONG_TOKEN = "e2e4 e2e4e2e4e2e4e2e4e2e4"  # move 2: 24 characters, 16 of them in the message
+PROMO_ROOT = "8/4P2k/8/8/8/8/8/K7 w - - 0 1"  # e7e8q is legal here
+
+
+def _mixed_whitespace(moves):
+    seps = ["\t", "\r\n", "   ", " \t ", "\n", "\r", " "]
+    return " \t" + "".join(t + seps[i % len(seps)] for i, t in enumerate(moves.split())) + "\r\n "
+
+
+def _replay_error(G, root, moves):
+    """(code, gn_last_error's message) of a game gn_replay_game fails."""
+    with pytest.raises(G.GnError) as e:
+        G.replay_game(root, moves)
+    return e.value.code, (G.lib().gn_last_error() or b"").decode()
+
+
+def test_mixed_whitespace_replays_as_single_spaces(G):
+    a, b = G.replay_game(START, OPERA, skip=[2]), G.replay_game(START, _mixed_whitespace(OPERA), skip=[2])
+    assert len(a[0]) == 34
+    for x, y in zip(a, b):
+        assert x.tobytes() == y.tobytes()
+    for blank in (" \t\r\n  ", ""):
+        boards, skipped, moves = G.replay_game(START, blank)
+        assert len(boards) == 1 and len(moves) == 0 and G.board_to_fen(boards[0]) == START
+
+
+def test_long_tokens_fail_at_their_index_with_16_characters(G):
+    code, msg = _replay_error(G, START, LONG_TOKEN)
+    assert code == G.E_ILLEGAL_MOVE and "move 2 (e2e4e2e4e2e4e2e4) " in msg
+    assert len(G.replay_game(PROMO_ROOT, "e7e8q h7g7")[0]) == 3
+    for tok, shown in (("e7e8qq", "e7e8qq"), ("e7e8qqq", "e7e8qqq"), ("e7e8q\x0b", "e7e8q\x0b")):
+        code, msg = _replay_error(G, PROMO_ROOT, tok)
+        assert code == G.E_ILLEGAL_MOVE and f"move 1 ({shown}) " in msg
+        code, msg = _replay_error(G, PROMO_ROOT, "e7e8q h7g7 \t" + tok)
+        assert code == G.E_ILLEGAL_MOVE and f"move 3 ({shown}) " in msg
+
+
+@pytest.mark.gpu
+def test_evaluate_games_tokens_equal_host_replay(gpu_ctx):
+    """gn_evaluate_games splits the move string as gn_replay_game does: the same bytes for mixed
+    whitespace, and for a failing game (one per call) the host replay's status and message."""
+    from fishnet_amd import gpu_nnue as G
+
+    def run(games, children):
+        arr, _keep = G._games_array(games)
+        r = gpu_ctx.evaluate_games_arrays(arr, len(games), 0, children=children)
+        return [x.tobytes() for x in (r[:6] if children else r[:3])], r[1]
+
+    for children in (False, True):
+        plain, status = run([(START, OPERA, [3]), (C960, "e2e4 e6e5", [])], children)
+        mixed, _ = run([(START, _mixed_whitespace(OPERA), [3]), (C960, "\te2e4\r\ne6e5\n", [])], children)
+        assert not status.any() and plain == mixed
+    for root, moves in ((START, LONG_TOKEN), (PROMO_ROOT, "e7e8qq"), (PROMO_ROOT, "e7e8q  h7g7\te7e8qqq")):
+        code, msg = _replay_error(G, root, moves)
+        _, status = run([(START, OPERA, []), (root, moves, []), (START, "e2e4", [])], False)
+        assert list(status) == [0, code, 0] and code == G.E_ILLEGAL_MOVE
+        assert (G.lib().gn_last_error() or b"").decode() == msg
+
+
+# ---- a shard that reads the replay's boards in place beside one that gathers ----
+K_MIXED = 3
+
+
+def _all_arrays(ctx, games):
+    """Every array gn_evaluate_games (without and with children) and gn_evaluate_games_lines return."""
+    from fishnet_amd import gpu_nnue as G
+    arr, _keep = G._games_array(games)
+    out = []
+    for children in (False, True):
+        r = ctx.evaluate_games_arrays(arr, len(games), 0, children=children)
+        out += [x.tobytes() for x in (r[:6] if children else r[:3])]
+    return out + [x.tobytes() for x in ctx.evaluate_games_lines(games, K_MIXED, 0)]
+
+
+@pytest.fixture(scope="module")
+def two_slots(synth_big_path, synth_small_path):
+    from fishnet_amd import gpu_nnue as G
+    ctx = G.GpuNnue(synth_big_path, synth_small_path, devices=[0, 0])
+    yield ctx
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_mixed_shards_equal_one_slot(gpu_ctx, two_slots):
+    from fishnet_amd import gpu_nnue as G
+    ucis = G.random_games_uci(0x5EED5A4D, 0, 6, 40)
+    skips = [(), (1000,), (), (), (0, 7, 40), (3, 4, 5, 999)]  # 1000 / 999: beyond the game, ignored
+    games = [(START, u, s) for u, s in zip(ucis, skips)]
+    npos = [len(u.split()) + 1 for u in ucis]
+    assert npos == [41] * 6
+
+    def skipped_shards(gs):  # per shard of the two-slot context: does it hold a skipped position?
+        w = [len(u.split()) + 1 for _, u, _ in gs]
+        b = G.partition(len(gs), 2, w)
+        return [any(p < w[g] for g in range(b[k], b[k + 1]) for p in gs[g][2]) for k in range(2)], b
+
+    assert skipped_shards(games)[0] == [False, True]
+    assert skipped_shards(games[::-1])[0] == [True, False]
+    assert skipped_shards(games[1:2])[1] == [0, 1, 1]  # the second shard is empty
+    ref = _all_arrays(gpu_ctx, games)
+    assert _all_arrays(two_slots, games) == ref
+    assert _all_arrays(two_slots, games[::-1]) == _all_arrays(gpu_ctx, games[::-1])
+    for g in (1, 4):  # in place alone, gathered alone
+        assert _all_arrays(two_slots, games[g:g + 1]) == _all_arrays(gpu_ctx, games[g:g + 1])
+    # an out-of-range skip index changes nothing
+    plain = [(r, u, () if s == (1000,) else s) for r, u, s in games]
+    assert _all_arrays(two_slots, plain) == ref
+    assert _all_arrays(gpu_ctx, plain[1:2]) == _all_arrays(gpu_ctx, games[1:2])
