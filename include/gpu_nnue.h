@@ -489,8 +489,16 @@ GN_API int gn_replay_game(const gn_game *game, gn_board *positions, uint8_t *ski
  * positions get GN_FLAG_SKIPPED and no children.  with_children != 0: also every
  * legal child of every evaluated position, child_offsets[total positions + 1]
  * indexed by position (as gn_expand_and_evaluate).  GN_E_CAPACITY when the
- * positions exceed position_cap or the children child_cap (the offsets are still
- * filled so the caller can retry with the right sizes). */
+ * positions exceed position_cap or the children child_cap, so that the caller can
+ * retry with the right sizes: position_offsets and game_status are filled in both
+ * cases.  The positions are checked first, before anything is evaluated or counted:
+ * when they exceed position_cap, child_offsets is not written at all (nor is any
+ * other output array), so a caller sizes the positions first
+ * (position_offsets[n_games]) and then, with position_cap large enough, the children:
+ * when only the children exceed child_cap, child_offsets is completely filled
+ * (child_offsets[total positions] = the children needed).  What the record, move
+ * and child arrays hold after GN_E_CAPACITY is unspecified; nothing is ever written
+ * beyond the capacities given. */
 GN_API int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int with_children,
                              uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                              size_t position_cap, uint32_t *child_offsets, uint16_t *child_moves,

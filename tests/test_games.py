@@ -346,6 +346,8 @@ def test_chained_links_of_special_moves_vs_oracle(gpu_ctx, oracle_nets, oracle_l
 # ---- the move string's tokens (whitespace-separated; tabs, CR LF and runs of spaces included) ----
 LONG_TOKEN = "e2e4 e2e4e2e4e2e4e2e4e2e4"  # move 2: 24 characters, 16 of them in the message
 PROMO_ROOT = "8/4P2k/8/8/8/8/8/K7 w - - 0 1"  # e7e8q is legal here
+# (root, moves) of games that fail at a token longer than a move
+LONG_TOKEN_GAMES = ((START, LONG_TOKEN), (PROMO_ROOT, "e7e8qq"), (PROMO_ROOT, "e7e8q  h7g7\te7e8qqq"))
 
 
 def _mixed_whitespace(moves):
@@ -396,7 +398,7 @@ def test_evaluate_games_tokens_equal_host_replay(gpu_ctx):
         plain, status = run([(START, OPERA, [3]), (C960, "e2e4 e6e5", [])], children)
         mixed, _ = run([(START, _mixed_whitespace(OPERA), [3]), (C960, "\te2e4\r\ne6e5\n", [])], children)
         assert not status.any() and plain == mixed
-    for root, moves in ((START, LONG_TOKEN), (PROMO_ROOT, "e7e8qq"), (PROMO_ROOT, "e7e8q  h7g7\te7e8qqq")):
+    for root, moves in LONG_TOKEN_GAMES:
         code, msg = _replay_error(G, root, moves)
         _, status = run([(START, OPERA, []), (root, moves, []), (START, "e2e4", [])], False)
         assert list(status) == [0, code, 0] and code == G.E_ILLEGAL_MOVE
