@@ -498,6 +498,36 @@ GN_HD Board do_move(const Board &B, uint16_t m, Dirty *d = nullptr) {
   return C;
 }
 
+// ---------------------------------------------------------- position key ----
+// The repetition key of a position (include/gpu_nnue.h at gn_history): a function of exactly its
+// identity -- piece placement, side to move, castling rook squares, en-passant square -- and of
+// nothing else (not rule50, not fullmove).  B must be canonical: gated by position_ok, or made by
+// do_move from a canonical board (which keeps the castling rights and the en-passant square
+// canonical).  Arithmetic only, no table: the 8 words
+//   w0..w5 = byType[PAWN..KING], w6 = byColor[WHITE],
+//   w7 = stm | ep << 8 | castle_rook[0] << 16 | [1] << 24 | [2] << 32 | [3] << 40
+// folded from h = 0x9E3779B97F4A7C15 by h = (h ^ w) * 0xBF58476D1CE4E5B9, h ^= h >> 29 (each step
+// a bijection of h for a given w), then splitmix64's last two steps h = (h ^ h >> 27) *
+// 0x94D049BB133111EB, h ^= h >> 31; a result of 0 becomes 1 (0 is the key of a rejected board).
+// Equal keys stand for equal identity: 64 bits, as Stockfish's own repetition test compares its
+// 64-bit Zobrist keys.  Host and device compute the same value.
+GN_HD uint64_t key_fold(uint64_t h, uint64_t w) {
+  h = (h ^ w) * 0xBF58476D1CE4E5B9ull;
+  return h ^ (h >> 29);
+}
+GN_HD uint64_t position_key(const Board &B) {
+  uint64_t h = 0x9E3779B97F4A7C15ull;
+#pragma unroll
+  for (int t = PAWN; t <= KING; ++t) h = key_fold(h, B.byType[t]);
+  h = key_fold(h, B.byColor[WHITE]);
+  h = key_fold(h, (uint64_t)B.stm | (uint64_t)B.ep << 8 | (uint64_t)B.castle_rook[0] << 16 |
+                      (uint64_t)B.castle_rook[1] << 24 | (uint64_t)B.castle_rook[2] << 32 |
+                      (uint64_t)B.castle_rook[3] << 40);
+  h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+  h ^= h >> 31;
+  return h ? h : 1;
+}
+
 // ------------------------------------------------------------- UCI moves ----
 // A lichess move token (AcquireResponseBody.moves, /root/reference/src/api.rs:306-321) as a
 // 16-bit code: from | to << 6 | promo << 12 (promo 0 none, 1..4 = n b r q); UCI_BAD for a

@@ -378,6 +378,12 @@ struct Dev {
   DevBuf<uint16_t> codes, smoves;
   DevBuf<int32_t> rstatus;
   DevBuf<uint32_t> gidx;
+  // gn_evaluate_games_lines_history: position_key of every board of rboards (n_rkeys of them), and
+  // one gn_history per evaluated position of the shard
+  DevBuf<uint64_t> rkeys;
+  size_t n_rkeys = 0;
+  DevBuf<gn_history> hist;
+  double t_keys = 0; // position_keys_kernel in that call (GN_STAT_KEYS_NS), ms
   // stage times of the last host-buffer call on this device (GN_STAT_HOST_*), ms
   double t_upload = 0, t_replay = 0, t_compute = 0, t_download = 0, t_tail = 0, t_rank = 0, t_rank2 = 0;
   // the drop-in's small-batch graphs (FastBatch): two per size class (128 << k positions) and mode,
@@ -613,7 +619,7 @@ static void destroy(gn_ctx *ctx) {
       if (d.cev[i]) (void)hipEventDestroy(d.cev[i]);
     }
     d.roots.release(), d.rboards.release(), d.par.release(), d.moff.release(), d.codes.release();
-    d.smoves.release(), d.rstatus.release(), d.gidx.release();
+    d.smoves.release(), d.rstatus.release(), d.gidx.release(), d.rkeys.release(), d.hist.release();
     if (d.copy) (void)hipStreamSynchronize(d.copy), (void)hipStreamDestroy(d.copy);
     if (d.done) (void)hipEventDestroy(d.done);
     if (d.stream) (void)hipStreamDestroy(d.stream);
@@ -1474,7 +1480,7 @@ static int run_shards(gn_ctx *ctx, const std::vector<size_t> &b, F &&f) {
 }
 
 static void reset_host_stats(gn_ctx *ctx) {
-  for (auto &dp : ctx->devs) dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = 0;
+  for (auto &dp : ctx->devs) dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = dp->t_keys = 0;
 }
 
 // Chunk bounds of a shard's m parents: cut only where `starts` allows (the first parent of each
@@ -1656,6 +1662,11 @@ struct ExpandOut {
   gn_child *child_out = nullptr;
   int n_lines = 0;
   gn_line *lines = nullptr;
+  // gn_evaluate_games_lines_history: the shard's keys (device, n_keys of them) and one gn_history per
+  // parent of the shard (device; chunk c's at history + chunks[c]); NULL: the plain ranking
+  const gn_history *history = nullptr;
+  const uint64_t *keys = nullptr;
+  size_t n_keys = 0;
 };
 // Pass 2 of a shard (see above).  off: the shard's child offsets from pass 1.
 static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m, int mode,
@@ -1736,8 +1747,13 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
           // (d.cur's offsets and unpacked parents are this chunk's: the front that overwrites the
           // set is queued after the synchronisation below)
           HIP_TRY(hipEventRecord(d.rev[0], s));
-          HIP_TRY(launch_rank_children(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P, d.tables,
-                                       n_lines, d.ln2[k].p, s));
+          if (o.history)
+            HIP_TRY(launch_rank_children_history(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P,
+                                                 d.tables, n_lines, d.ln2[k].p,
+                                                 RankHistory{o.keys, o.n_keys, o.history + pa}, s));
+          else
+            HIP_TRY(launch_rank_children(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P, d.tables,
+                                         n_lines, d.ln2[k].p, s));
           HIP_TRY(hipEventRecord(d.rev[1], s));
         } else {
           HIP_TRY(launch_pack_children(d.co2[k].p, t, d.cc2[k].p, s));
@@ -1952,6 +1968,7 @@ struct GameShard {
   std::vector<size_t> starts;       // first evaluated position of each game (the chunks' cuts)
   std::vector<gn_eval> res;         // gathered: the evaluated positions' records ...
   std::vector<gn_line> lres;        // ... and lines
+  std::vector<gn_history> hist;     // history call: each evaluated position's game so far, in rboards' indices
   std::vector<uint64_t> off;        // child offsets from pass 1 (m + 1, relative)
   uint64_t child_base = 0;          // the shard's first child in the caller's arrays
   bool has() const { return m > 0; }
@@ -1965,6 +1982,7 @@ struct GamesCall {
   const gn_game *games;
   size_t n_games;
   int mode, with_children, n_lines;
+  bool history; // gn_evaluate_games_lines_history: the lines with the game-history draws
   uint32_t *position_offsets, *child_offsets;
   int32_t *game_status;
   gn_eval *position_out;
@@ -2027,10 +2045,24 @@ static int games_replay(const GamesCall &c, GameShard &sh, Dev &d, size_t g0, si
   d.t_upload += ms_since(t0);
   const auto t1 = Clock::now();
   HIP_TRY(launch_replay_games(d.roots.p, ng, d.moff.p, d.codes.p, d.tables, d.rboards.p, d.smoves.p, d.rstatus.p, s));
+  if (c.history) { // the keys of every replayed board (a failed game's unwritten ones are never indexed),
+                   // queued behind the replay: the status read-back below waits for both
+    HIP_TRY(d.rkeys.ensure(nm + ng));
+    d.n_rkeys = nm + ng;
+    HIP_TRY(hipEventRecord(d.rev[0], s));
+    HIP_TRY(launch_position_keys(d.rboards.p, nm + ng, false, d.tables, d.rkeys.p, s));
+    HIP_TRY(hipEventRecord(d.rev[1], s));
+  }
   sh.status.resize(ng);
   HIP_TRY(hipMemcpyAsync(sh.status.data(), d.rstatus.p, ng * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  d.t_replay += ms_since(t1);
+  double keys_ms = 0;
+  if (c.history) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, d.rev[0], d.rev[1]));
+    d.t_keys += ms, keys_ms = ms;
+  }
+  d.t_replay += ms_since(t1) - keys_ms;
   return GN_OK;
 }
 
@@ -2078,6 +2110,12 @@ static void games_layout(const GamesCall &c, GameShard &sh) {
     sh.m = sh.games.empty() ? 0 : (size_t)sh.moff.back() + sh.games.size();
     sh.p0 = sh.games.empty() ? 0 : c.position_offsets[sh.games[0]];
     for (size_t j = 0; j < sh.games.size(); ++j) sh.starts.push_back((size_t)sh.moff[j] + j);
+    if (c.history) sh.hist.reserve(sh.m);
+    if (c.history)
+      for (size_t j = 0; j < sh.games.size(); ++j) {
+        const uint32_t first = (uint32_t)(sh.moff[j] + j);
+        for (uint32_t e = first; e < sh.moff[j + 1] + j + 1; ++e) sh.hist.push_back(gn_history{first, e});
+      }
     return;
   }
   for (size_t j = 0; j < sh.games.size(); ++j) {
@@ -2092,6 +2130,7 @@ static void games_layout(const GamesCall &c, GameShard &sh) {
       } else {
         sh.src.push_back((uint32_t)(sh.moff[j] + j + p));
         sh.where.push_back((uint32_t)at);
+        if (c.history) sh.hist.push_back(gn_history{(uint32_t)(sh.moff[j] + j), sh.src.back()});
       }
     }
   }
@@ -2113,6 +2152,13 @@ static int games_evaluate_or_count(const GamesCall &c, GameShard &sh, Dev &d) {
     d.t_upload += ms_since(t0);
     sh.res.resize(m);
     sh.lres.resize(m * (size_t)c.n_lines);
+  }
+  if (c.history) { // one gn_history per evaluated position, uploaded once per shard
+    const auto t0 = Clock::now();
+    HIP_TRY(d.hist.ensure(m));
+    HIP_TRY(hipMemcpyAsync(d.hist.p, sh.hist.data(), m * sizeof(gn_history), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    d.t_upload += ms_since(t0);
   }
   if (c.with_children) return count_shard(d, sh.parents_of(d), m, sh.off);
   const auto t1 = Clock::now();
@@ -2164,8 +2210,9 @@ static int games_child_offsets(GamesCall &c) {
 static int games_expand(const GamesCall &c, GameShard &sh, Dev &d) {
   gn_eval *const rec = sh.records_of(c.position_out);
   gn_line *const ln = sh.in_place ? c.lines + sh.p0 * (size_t)c.n_lines : sh.lres.data();
-  const ExpandOut o = c.n_lines ? ExpandOut{rec, nullptr, nullptr, c.n_lines, ln}
-                                : ExpandOut{rec, c.child_moves + sh.child_base, c.child_out + sh.child_base};
+  ExpandOut o = c.n_lines ? ExpandOut{rec, nullptr, nullptr, c.n_lines, ln}
+                          : ExpandOut{rec, c.child_moves + sh.child_base, c.child_out + sh.child_base};
+  if (c.history) o.history = d.hist.p, o.keys = d.rkeys.p, o.n_keys = d.n_rkeys;
   return expand_pipelined(c.ctx, d, sh.parents_of(d), sh.m, c.mode, sh.off,
                           chunk_plan(sh.m, sh.starts, c.ctx->chunk_parents), o);
 }
@@ -2240,7 +2287,7 @@ int gn_replay_game(const gn_game *game, gn_board *positions, uint8_t *skipped, u
 int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int with_children,
                       uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out, size_t position_cap,
                       uint32_t *child_offsets, uint16_t *child_moves, gn_child *child_out, size_t child_cap) {
-  return evaluate_games({ctx, games, n_games, mode, with_children, 0, position_offsets, child_offsets, game_status,
+  return evaluate_games({ctx, games, n_games, mode, with_children, 0, false, position_offsets, child_offsets, game_status,
                          position_out, position_cap, child_cap, child_moves, child_out, nullptr});
 }
 
@@ -2248,8 +2295,16 @@ int gn_evaluate_games_lines(gn_ctx *ctx, const gn_game *games, size_t n_games, i
                             uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                             size_t position_cap, gn_line *lines) {
   if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
-  return evaluate_games({ctx, games, n_games, mode, 1, n_lines, position_offsets, nullptr, game_status, position_out,
-                         position_cap, 0, nullptr, nullptr, lines});
+  return evaluate_games({ctx, games, n_games, mode, 1, n_lines, false, position_offsets, nullptr, game_status,
+                         position_out, position_cap, 0, nullptr, nullptr, lines});
+}
+
+int gn_evaluate_games_lines_history(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                    uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
+                                    size_t position_cap, gn_line *lines) {
+  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  return evaluate_games({ctx, games, n_games, mode, 1, n_lines, true, position_offsets, nullptr, game_status,
+                         position_out, position_cap, 0, nullptr, nullptr, lines});
 }
 
 int gn_partition(const uint32_t *weights, size_t n_items, int n_shards, size_t *bounds) {
@@ -2454,6 +2509,21 @@ int gn_boards_to_fens(const gn_board *boards, size_t n, char *buf, size_t stride
         Board B;
         char *o = buf + i * stride;
         if (!unpack(boards[i], B, host_tables()) || board_to_fen(B, o, stride) < 0) o[0] = '\0';
+      }
+    });
+  } catch (...) {
+    return fail(GN_E_NOMEM, "thread start failed");
+  }
+  return GN_OK;
+}
+
+int gn_position_keys(const gn_board *boards, size_t n, uint64_t *keys) {
+  if (n && (!boards || !keys)) return fail(GN_E_INVALID, "NULL argument");
+  try {
+    parallel_for(n, 4096, [&](size_t lo, size_t hi) {
+      for (size_t i = lo; i < hi; ++i) {
+        Board B;
+        keys[i] = unpack(boards[i], B, host_tables()) ? position_key(B) : 0;
       }
     });
   } catch (...) {
@@ -2686,6 +2756,33 @@ int gn_rank_children_device(gn_ctx *ctx, int device_slot, const gn_board *d_pare
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
   HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables, n_lines, d_lines, call.s));
+  return GN_OK;
+}
+
+int gn_position_keys_device(gn_ctx *ctx, int device_slot, const gn_board *d_boards, size_t n, uint64_t *d_keys,
+                            void *stream) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
+  if (n && (!d_boards || !d_keys)) return fail(GN_E_INVALID, "NULL buffer");
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_position_keys(d_boards, n, true, d->tables, d_keys, call.s));
+  return GN_OK;
+}
+
+int gn_rank_children_history_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                    const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out,
+                                    const uint64_t *d_keys, size_t n_keys, const gn_history *d_hist, int n_lines,
+                                    gn_line *d_lines, void *stream) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
+  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  if (n && (!d_parents || !d_offsets || !d_lines || !d_hist)) return fail(GN_E_INVALID, "NULL buffer");
+  if (n_keys && !d_keys) return fail(GN_E_INVALID, "d_keys is NULL");
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_rank_children_history(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables, n_lines, d_lines,
+                                       RankHistory{d_keys, n_keys, d_hist}, call.s));
   return GN_OK;
 }
 
@@ -3030,6 +3127,7 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
   case GN_STAT_HOST_DOWNLOAD_NS:
   case GN_STAT_RANK_NS:
   case GN_STAT_RANK2_NS:
+  case GN_STAT_KEYS_NS:
   case GN_STAT_HOST_TAIL_NS: { // the last host-buffer call, max over devices
     double m = 0;
     for (auto &dp : ctx->devs) {
@@ -3040,6 +3138,7 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
                       : option == GN_STAT_HOST_DOWNLOAD_NS ? d.t_download
                       : option == GN_STAT_RANK_NS          ? d.t_rank
                       : option == GN_STAT_RANK2_NS         ? d.t_rank2
+                      : option == GN_STAT_KEYS_NS          ? d.t_keys
                                                            : d.t_tail);
     }
     *value = (int64_t)(m * 1e6);

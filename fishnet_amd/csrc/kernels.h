@@ -260,6 +260,24 @@ hipError_t launch_rank_children(const Board *unpacked, size_t n, const uint64_t 
 hipError_t launch_rank_children(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
                                 const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
                                 gn_line *lines, hipStream_t s);
+// ... with the game-history draws (include/gpu_nnue.h at gn_history; rank_children_kernel with a RankHistory):
+// hist[i] names parent i's game so far in keys[0, n_keys) (position_key of each position)
+struct RankHistory {
+  const uint64_t *keys;
+  size_t n_keys;
+  const gn_history *hist;
+};
+hipError_t launch_rank_children_history(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
+                                        const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
+                                        gn_line *lines, const RankHistory &history, hipStream_t s);
+hipError_t launch_rank_children_history(const gn_board *parents, size_t n, const uint32_t *offsets,
+                                        const uint16_t *moves, const gn_eval *rec, const gn_eval_params &P,
+                                        const Tables *tables, int K, gn_line *lines, const RankHistory &history,
+                                        hipStream_t s);
+// keys[i] = position_key of boards[i], a lane per board.  gate: a caller's boards (unpack; a
+// rejected board's key is 0); else the library's own canonical boards (unpack_fields)
+hipError_t launch_position_keys(const gn_board *boards, size_t n, bool gate, const Tables *tables, uint64_t *keys,
+                                hipStream_t s);
 // Two-ply ranked lines (include/gpu_nnue.h gn_line2): lines[i * K + k] = line k + 1 of parent i, from
 // a depth-2 expansion's outputs: the children [offsets[i], offsets[i + 1]) (boards, records rec,
 // moves) and each child c's grandchildren [goffsets[c], goffsets[c + 1]) (gmoves, records grec).

@@ -1100,14 +1100,33 @@ __device__ __forceinline__ uint64_t top_k_rounds(uint64_t key, uint64_t top, int
 __device__ __forceinline__ bool rank_parent(const Board &src, Board &B, const Tables &) { B = src; return true; }
 __device__ __forceinline__ bool rank_parent(const gn_board &src, Board &B, const Tables &T) { return unpack(src, B, T); }
 
-template <class Parent, class Off>
-__global__ void __launch_bounds__(RANK_WG)
+// History variant (HIST; include/gpu_nnue.h at gn_history): where the lane holds its child C with
+// `none` and `check`, a child that has a legal move is drawn by rule when C.rule50 >= 100, or when
+// its position_key equals at least two keys of the parent's game so far, keys[first..=self] of the
+// parent's gn_history entry.  The walk tests only self + 1 - d for d = 4, 6, ... <=
+// min(C.rule50, self - first + 1): a pawn move or a capture lies between C and anything older,
+// and a position with the other side to move cannot equal C.  Its trip count differs per lane, so
+// it sits where any_legal sits: every shuffle stays outside it.  An entry with first > self or
+// self >= n_keys is no history (the fifty-move part still applies), so keys is never indexed at or
+// beyond n_keys.  The draw bit rides below the move with the other two flag bits, the value and
+// the move one bit higher: (value + 32768) << 19 | (0xFFFF - move) << 3 | draw << 2 |
+// no-moves << 1 | in-check.  The variant is chosen at compile time by an optional trailing kernel
+// argument (History: nothing, or one RankHistory), so the plain instantiations keep their
+// arguments and their code.  Left to itself the history variant takes 181 VGPRs, 2 waves per SIMD
+// where the plain kernel (162) runs 3, and that, not the key arithmetic or the walk's loads, was
+// its cost; asked for 3 waves it fits 168 without scratch.  (The plain variant
+// asks for 1, which is what no request means: its code is unchanged.)
+template <class Parent, class Off, class... History>
+__global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(sizeof...(History) ? 3 : 1)))
     rank_children_kernel(const Parent *__restrict__ parents, size_t n, const Off *__restrict__ offsets,
                          const uint16_t *__restrict__ moves, const gn_eval *__restrict__ rec, gn_eval_params P,
-                         const Tables *__restrict__ tables, int K, gn_line *__restrict__ lines) {
+                         const Tables *__restrict__ tables, int K, gn_line *__restrict__ lines, History... history) {
+  static_assert(sizeof...(History) <= 1, "nothing, or one RankHistory");
+  constexpr bool HIST = sizeof...(History) != 0;
   __shared__ Tables T;
   load_tables(T, tables);
   constexpr int W = GN_RANK_WIDTH;
+  constexpr int FB = HIST ? 3 : 2; // flag bits below the move
   const int lane = threadIdx.x & (W - 1);
   // a bounded grid striding over the parents (the 4 KiB table load once per workgroup)
   const size_t stride = (size_t)gridDim.x * (RANK_WG / W);
@@ -1118,6 +1137,14 @@ __global__ void __launch_bounds__(RANK_WG)
     // (a parent without children -- bad, mated, stalemated, or skipped by the caller -- is never
     // unpacked or read as a Board: its unpacked entry is not written)
     const bool ok = c1 > c0 && rank_parent(parents[p], B, T);
+    uint32_t hself = 0, hlen = 0; // HIST: the parent's key index, and its game's positions so far (0: no history)
+    if constexpr (HIST) {
+      if (ok) {
+        const gn_history h = (history.hist, ...)[p];
+        hself = h.self;
+        hlen = (h.first <= h.self && (size_t)h.self < (history.n_keys, ...)) ? h.self - h.first + 1 : 0u;
+      }
+    }
     for (uint64_t c = c0; ok && c < c1; c += W) {
       uint64_t key = 0;
       if (c + lane < c1) {
@@ -1126,8 +1153,43 @@ __global__ void __launch_bounds__(RANK_WG)
         const Board C = do_move(B, (uint16_t)mv, nullptr);
         const uint32_t check = (r.flags & GN_FLAG_IN_CHECK) ? 1u : 0u;
         const uint32_t none = any_legal(C, T) ? 0u : 1u;
-        const int32_t v = negate_ply(none ? (check ? -VALUE_MATE : 0) : r.final_v);
-        key = (uint64_t)(uint32_t)(v + 32768) << 18 | (uint64_t)(0xFFFFu - mv) << 2 | none << 1 | check;
+        if constexpr (HIST) {
+          uint32_t draw = 0;
+          if (!none) {
+            const uint32_t lim = C.rule50 < hlen ? (uint32_t)C.rule50 : hlen;
+            if (C.rule50 >= 100) {
+              draw = 1;
+            } else if (lim >= 4) {
+#ifdef GN_AB_HIST_NO_KEY // A/B only (wrong draws): the walk's loads without the key arithmetic
+              const uint64_t ck = C.byType[0];
+#else
+              const uint64_t ck = position_key(C);
+#endif
+              uint32_t seen = 0;
+#ifdef GN_AB_HIST_NO_WALK // A/B only (wrong draws): the key arithmetic without the walk's loads
+              seen = ck == 0x5EEDull ? 2u : 0u;
+#else
+              // four keys per trip, their loads independent of each other (a trip's tail re-reads
+              // d = 4, which lim >= 4 makes valid, and ignores it); the walk ends between trips
+              const uint64_t *const at = (history.keys, ...) + ((size_t)hself + 1);
+              for (uint32_t d = 4; d <= lim && seen < 2; d += 8) {
+#pragma unroll
+                for (uint32_t j = 0; j < 8; j += 2) {
+                  const bool in = d + j <= lim;
+                  const uint64_t k = *(at - (in ? d + j : 4u));
+                  seen += in && k == ck ? 1u : 0u;
+                }
+              }
+#endif
+              draw = seen >= 2 ? 1u : 0u;
+            }
+          }
+          const int32_t v = negate_ply(none ? (check ? -VALUE_MATE : 0) : draw ? 0 : r.final_v);
+          key = (uint64_t)(uint32_t)(v + 32768) << 19 | (uint64_t)(0xFFFFu - mv) << 3 | draw << 2 | none << 1 | check;
+        } else {
+          const int32_t v = negate_ply(none ? (check ? -VALUE_MATE : 0) : r.final_v);
+          key = (uint64_t)(uint32_t)(v + 32768) << 18 | (uint64_t)(0xFFFFu - mv) << 2 | none << 1 | check;
+        }
       }
       uint64_t next = 0;
       for (int k = 0; k < K; ++k) {
@@ -1144,8 +1206,9 @@ __global__ void __launch_bounds__(RANK_WG)
       gn_line l = {0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE};
       if (top) {
         uint32_t fl = ((top & 1) ? GN_FLAG_IN_CHECK : 0u) | ((top & 2) ? GN_FLAG_NO_MOVES : 0u);
-        l.value = (int32_t)(top >> 18) - 32768;
-        l.move = (uint16_t)(0xFFFFu - (uint32_t)((top >> 2) & 0xFFFFu));
+        if constexpr (HIST) fl |= (top & 4) ? GN_FLAG_DRAW : 0u;
+        l.value = (int32_t)(top >> (16 + FB)) - 32768;
+        l.move = (uint16_t)(0xFFFFu - (uint32_t)((top >> FB) & 0xFFFFu));
         l.score = rule_score(l.value, wdl_material(B, P), P, fl);
         l.flags = (uint16_t)fl;
       }
@@ -1154,15 +1217,20 @@ __global__ void __launch_bounds__(RANK_WG)
   }
 }
 
+// (history: keys / n_keys / hist of the history variant, or nullptr: the plain kernel)
 template <class Parent, class Off>
 static hipError_t rank_children_t(const Parent *parents, size_t n, const Off *offsets, const uint16_t *moves,
                                   const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                  gn_line *lines, hipStream_t s) {
+                                  gn_line *lines, hipStream_t s, const RankHistory *history = nullptr) {
   if (!n) return hipSuccess;
   constexpr size_t per_wg = RANK_WG / GN_RANK_WIDTH, max_blocks = 8192;
   const size_t blocks = std::min<size_t>((n + per_wg - 1) / per_wg, max_blocks);
-  hipLaunchKernelGGL((rank_children_kernel<Parent, Off>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets, moves,
-                     rec, P, tables, K, lines);
+  if (history)
+    hipLaunchKernelGGL((rank_children_kernel<Parent, Off, RankHistory>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n,
+                       offsets, moves, rec, P, tables, K, lines, *history);
+  else
+    hipLaunchKernelGGL((rank_children_kernel<Parent, Off>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets,
+                       moves, rec, P, tables, K, lines);
   return hipGetLastError();
 }
 hipError_t launch_rank_children(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
@@ -1174,6 +1242,43 @@ hipError_t launch_rank_children(const gn_board *parents, size_t n, const uint32_
                                 const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
                                 gn_line *lines, hipStream_t s) {
   return rank_children_t(parents, n, offsets, moves, rec, P, tables, K, lines, s);
+}
+hipError_t launch_rank_children_history(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
+                                        const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
+                                        gn_line *lines, const RankHistory &history, hipStream_t s) {
+  return rank_children_t(unpacked, n, offsets, moves, rec, P, tables, K, lines, s, &history);
+}
+hipError_t launch_rank_children_history(const gn_board *parents, size_t n, const uint32_t *offsets,
+                                        const uint16_t *moves, const gn_eval *rec, const gn_eval_params &P,
+                                        const Tables *tables, int K, gn_line *lines, const RankHistory &history,
+                                        hipStream_t s) {
+  return rank_children_t(parents, n, offsets, moves, rec, P, tables, K, lines, s, &history);
+}
+
+// Position keys (chess.h position_key), a lane per board.  GATE: a caller's boards through the
+// gate (unpack; a rejected board's key is 0); otherwise boards the library made itself (the
+// replay's, already canonical: unpack_fields, no tables).
+template <bool GATE>
+__global__ void position_keys_kernel(const gn_board *__restrict__ boards, size_t n, const Tables *__restrict__ tables,
+                                     uint64_t *__restrict__ keys) {
+  __shared__ Tables T;
+  if constexpr (GATE) load_tables(T, tables);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Board B;
+  bool ok;
+  if constexpr (GATE) ok = unpack(boards[i], B, T);
+  else ok = unpack_fields(boards[i], B);
+  keys[i] = ok ? position_key(B) : 0;
+}
+hipError_t launch_position_keys(const gn_board *boards, size_t n, bool gate, const Tables *tables, uint64_t *keys,
+                                hipStream_t s) {
+  if (!n) return hipSuccess;
+  if (gate)
+    hipLaunchKernelGGL(position_keys_kernel<true>, dim3(blocks_for(n, 256)), dim3(256), 0, s, boards, n, tables, keys);
+  else
+    hipLaunchKernelGGL(position_keys_kernel<false>, dim3(blocks_for(n, 256)), dim3(256), 0, s, boards, n, tables, keys);
+  return hipGetLastError();
 }
 
 // ---- two-ply ranked lines (include/gpu_nnue.h gn_line2) -----------------------------------

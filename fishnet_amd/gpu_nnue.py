@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("GPU_NNUE_LIB", os.path.join(HERE, "lib", "libgpu_nnue
 MODE_FULL, MODE_BIG, MODE_SMALL = 0, 1, 2
 FLAG_IN_CHECK, FLAG_SMALLNET, FLAG_BAD_FEN, FLAG_REEVAL, FLAG_SKIPPED = 1, 2, 4, 8, 16
 FLAG_MATE, FLAG_NO_SCORE, FLAG_SEARCHED, FLAG_NO_MOVES = 32, 64, 128, 256
+FLAG_DRAW = 512  # gn_line.flags of the history calls only: drawn by rule (gpu_nnue.h at gn_history)
 ERRORS = {-1: "INVALID", -2: "IO", -3: "FORMAT", -4: "HIP", -5: "NOMEM", -6: "CAPACITY",
           -7: "NODEVICE", -8: "NONET", -9: "ILLEGAL_MOVE"}
 E_INVALID, E_IO, E_FORMAT, E_HIP, E_NOMEM, E_CAPACITY, E_NODEVICE, E_NONET, E_ILLEGAL_MOVE = -1, -2, -3, -4, -5, -6, -7, -8, -9
@@ -38,6 +39,8 @@ CHILD_VIEW_DTYPE = np.dtype([("psqt", "<i4"), ("positional", "<i4"), ("final_cp"
 # gn_line: one ranked line of a position (MultiPV; gpu_nnue.h at gn_line), 12 bytes
 LINE_DTYPE = np.dtype([("value", "<i4"), ("score", "<i4"), ("move", "<u2"), ("flags", "<u2")])
 MAX_LINES = 8
+# gn_history: a parent's game so far in a key array, keys[first..=self] (gpu_nnue.h at gn_history)
+HISTORY_DTYPE = np.dtype([("first", "<u4"), ("self", "<u4")])
 # gn_line2: one ranked two-ply line (a two-move PV and its minimax value; gpu_nnue.h at gn_line2), 16 bytes
 LINE2_DTYPE = np.dtype([("value", "<i4"), ("score", "<i4"), ("move", "<u2"), ("reply", "<u2"), ("flags", "<u2"),
                         ("plies", "<u2")])
@@ -56,12 +59,13 @@ EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_
            "gn_net_sha256", "gn_partition", "gn_checksum_device",
            "gn_boards_to_fens", "gn_load_net_archive", "gn_archive_read", "gn_expand2_device",
            "gn_random_games_uci", "gn_rank_children_device", "gn_evaluate_games_lines",
-           "gn_rank_lines2_device", "gn_evaluate_lines2"]
+           "gn_rank_lines2_device", "gn_evaluate_lines2", "gn_position_keys", "gn_position_keys_device",
+           "gn_rank_children_history_device", "gn_evaluate_games_lines_history"]
 OPT_INCREMENTAL_CHILDREN, OPT_XCD_SWIZZLE, OPT_KING_SORT, OPT_CHAIN, OPT_KING_CACHE = 1, 2, 3, 4, 5
 OPT_CHUNK_PARENTS, OPT_COALESCE, OPT_STREAM_SLICES, OPT_FAST_BATCH, OPT_EXPAND_PIPELINE = 6, 7, 8, 9, 10
 STAT_PLAN_NS, STAT_STREAM_NS, STAT_SCRATCH_PADS, STAT_FINISH_NS = 101, 102, 103, 104
 STAT_BATCH_LAUNCHES, STAT_BATCH_CALLS, STAT_FAST_BATCHES, STAT_FAST_FALLBACKS = 117, 118, 119, 120
-STAT_RANK_NS, STAT_RANK2_NS = 121, 122
+STAT_RANK_NS, STAT_RANK2_NS, STAT_KEYS_NS = 121, 122, 123
 HOST_STAGES = {"parse": 110, "upload": 111, "replay": 112, "compute": 113, "download": 114, "tail": 115, "total": 116}
 EXPAND_STAGES = ["count_scan", "total_readback", "write_children", "classify", "small_net", "big_net", "finalize",
                  "score"]
@@ -180,6 +184,10 @@ def lib():
         "gn_evaluate_games_lines": [vp, vp, sz, i32, i32, vp, vp, vp, sz, vp],
         "gn_rank_lines2_device": [vp, i32, vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
         "gn_evaluate_lines2": [vp, vp, sz, i32, i32, vp, vp],
+        "gn_position_keys": [vp, sz, vp],
+        "gn_position_keys_device": [vp, i32, vp, sz, vp, vp],
+        "gn_rank_children_history_device": [vp, i32, vp, sz, vp, vp, vp, vp, sz, vp, i32, vp, vp],
+        "gn_evaluate_games_lines_history": [vp, vp, sz, i32, i32, vp, vp, vp, sz, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -233,6 +241,14 @@ def random_positions(seed: int, first: int, n: int, max_plies: int = 160):
     boards = np.zeros(n, dtype=BOARD_DTYPE)
     _check(lib().gn_random_positions(seed, first, n, max_plies, boards.ctypes.data))
     return boards
+
+
+def position_keys(boards) -> np.ndarray:
+    """gn_position_keys: the 64-bit repetition key of every board (0: a rejected board); host only."""
+    b = np.ascontiguousarray(np.asarray(boards, dtype=BOARD_DTYPE).reshape(-1))
+    keys = np.zeros(len(b), dtype=np.uint64)
+    _check(lib().gn_position_keys(b.ctypes.data, len(b), keys.ctypes.data))
+    return keys
 
 
 def replay_game(root_fen: str, moves, skip=()):
@@ -478,10 +494,12 @@ class GpuNnue:
             return offs, status, pos[:p], coffs[:p + 1], cmv[:t], cev[:t], (pcap, ccap)
         raise GnError(E_CAPACITY, "capacity retry failed")
 
-    def evaluate_games_lines(self, games, n_lines, mode=MODE_FULL, cap=None):
+    def evaluate_games_lines(self, games, n_lines, mode=MODE_FULL, cap=None, history=False):
         """gn_evaluate_games_lines over [(root_fen, moves, skip)]: (position_offsets, game_status,
         positions[EVAL_DTYPE], lines[positions, n_lines] as LINE_DTYPE).  cap: the position
-        capacity (None: sized by a first call, as the C caller's GN_E_CAPACITY retry)."""
+        capacity (None: sized by a first call, as the C caller's GN_E_CAPACITY retry).  history:
+        gn_evaluate_games_lines_history (draws by repetition and the fifty-move rule, FLAG_DRAW)."""
+        call = lib().gn_evaluate_games_lines_history if history else lib().gn_evaluate_games_lines
         ng = len(games)
         arr, _keep = _games_array(games)
         offs = np.zeros(ng + 1, dtype=np.uint32)
@@ -490,8 +508,8 @@ class GpuNnue:
         for _ in range(2):
             pos = np.zeros(max(pcap, 1), dtype=EVAL_DTYPE)
             lines = np.zeros((max(pcap, 1), max(n_lines, 1)), dtype=LINE_DTYPE)
-            rc = lib().gn_evaluate_games_lines(self.h, arr, ng, mode, n_lines, offs.ctypes.data, status.ctypes.data,
-                                               pos.ctypes.data, pcap, lines.ctypes.data)
+            rc = call(self.h, arr, ng, mode, n_lines, offs.ctypes.data, status.ctypes.data, pos.ctypes.data, pcap,
+                      lines.ctypes.data)
             if rc == E_CAPACITY and cap is None and int(offs[-1]) > pcap:
                 pcap = int(offs[-1])
                 continue
@@ -499,6 +517,10 @@ class GpuNnue:
             p = int(offs[-1])
             return offs, status, pos[:p], lines[:p]
         raise GnError(E_CAPACITY, "capacity retry failed")
+
+    def evaluate_games_lines_history(self, games, n_lines, mode=MODE_FULL, cap=None):
+        """gn_evaluate_games_lines_history: evaluate_games_lines with each game's history."""
+        return self.evaluate_games_lines(games, n_lines, mode, cap, history=True)
 
     def evaluate_lines2(self, fens, n_lines, mode=MODE_FULL):
         """gn_evaluate_lines2: (positions[EVAL_DTYPE], lines[positions, n_lines] as LINE2_DTYPE): the
@@ -585,6 +607,18 @@ class GpuNnue:
         offsets, moves and child records.  Asynchronous on the stream."""
         _check(lib().gn_rank_children_device(self.h, slot, d_parents.ptr, n, d_offsets.ptr, d_moves.ptr,
                                              d_child_out.ptr, n_lines, d_lines.ptr, stream))
+
+    def position_keys_device(self, d_boards, n, d_keys, stream=None, slot=0):
+        """gn_position_keys_device: d_keys[n] (uint64) of n device-resident boards.  Asynchronous."""
+        _check(lib().gn_position_keys_device(self.h, slot, d_boards.ptr, n, d_keys.ptr, stream))
+
+    def rank_children_history_device(self, d_parents, n, d_offsets, d_moves, d_child_out, d_keys, n_keys, d_hist,
+                                     n_lines, d_lines, stream=None, slot=0):
+        """gn_rank_children_history_device: rank_children_device with the game-history draws; d_hist[n]
+        (HISTORY_DTYPE) names each parent's game so far in d_keys[n_keys].  Asynchronous."""
+        _check(lib().gn_rank_children_history_device(self.h, slot, d_parents.ptr, n, d_offsets.ptr, d_moves.ptr,
+                                                     d_child_out.ptr, d_keys.ptr if d_keys else None, n_keys,
+                                                     d_hist.ptr, n_lines, d_lines.ptr, stream))
 
     def rank_lines2_device(self, d_parents, n, out, n_lines, d_lines, stream=None, slot=0):
         """gn_rank_lines2_device: d_lines[n * n_lines] (LINE2_DTYPE) from a preceding expand2_device's

@@ -173,8 +173,13 @@ extern "C" {
                                          computed (not overlapped)                        */
 #define GN_STAT_HOST_TOTAL_NS 116     /* the whole call                                    */
 #define GN_STAT_RANK_NS 121           /* rank_children_kernel in the last
-                                         gn_evaluate_games_lines, summed over its chunks
-                                         (0 after any other host-buffer call)              */
+                                         gn_evaluate_games_lines, or its history variant in
+                                         the last gn_evaluate_games_lines_history, summed
+                                         over its chunks (0 after any other host-buffer
+                                         call)                                             */
+#define GN_STAT_KEYS_NS 123           /* position_keys_kernel in the last
+                                         gn_evaluate_games_lines_history (the slowest
+                                         device; 0 after any other host-buffer call)       */
 #define GN_STAT_RANK2_NS 122          /* rank_lines2_kernel in the last gn_evaluate_lines2,
                                          summed over its chunks (the slowest device; 0 after
                                          any other host-buffer call)                       */
@@ -198,6 +203,8 @@ extern "C" {
 #define GN_FLAG_SEARCHED 128u /* score from the in-check rule over the legal replies
                                  (best_move set), not from the static evaluation   */
 #define GN_FLAG_NO_MOVES 256u /* no legal move: checkmate (with IN_CHECK) or stalemate */
+#define GN_FLAG_DRAW 512u /* gn_line.flags only: the move's child is drawn by rule (threefold
+                             repetition or fifty-move rule; gn_history below)          */
 
 /* One result.  psqt/positional are Network::evaluate's NetworkOutput (already
  * divided by OutputScale = 16) of the net that produced final_v; final_v is
@@ -277,8 +284,47 @@ typedef struct gn_line {
   uint16_t move;  /* Stockfish encoding, castling = king takes rook                      */
   uint16_t flags; /* GN_FLAG_MATE; GN_FLAG_IN_CHECK: the move gives check;
                      GN_FLAG_NO_MOVES: the move ends the game (mate or stalemate);
-                     GN_FLAG_NO_SCORE: an empty line                                     */
+                     GN_FLAG_NO_SCORE: an empty line; GN_FLAG_DRAW: the history calls
+                     only (gn_history below)                                             */
 } gn_line;
+
+/* Game-history draws in ranked lines (gn_rank_children_history_device,
+ * gn_evaluate_games_lines_history): what Stockfish, given `position fen ... moves ...`, scores
+ * as a draw at ply 1 of a search (Position::is_draw).
+ * Identity.  A position's identity is its piece placement, its side to move, the canonical
+ * castling rook squares and the canonical en-passant square: the first four fields of the FEN
+ * gn_board_to_fen writes for the canonical board.  rule50, fullmove and reserved are not part
+ * of it.
+ * Key.  gn_position_keys gives a 64-bit key that is a function of exactly the identity, never 0
+ * for a position that passes the gate (0: a rejected board).  With the board's bitboards
+ * (bit s = square s) w0..w5 = pawns, knights, bishops, rooks, queens, kings of both colours,
+ * w6 = white's pieces, w7 = stm | ep << 8 | rook[0] << 16 | rook[1] << 24 | rook[2] << 32 |
+ * rook[3] << 40 (stm 1 = black; ep and the castling rook squares [white O-O, white O-O-O, black
+ * O-O, black O-O-O] as squares, 64 = none):
+ *   h = 0x9E3779B97F4A7C15; for w0..w7: h = (h ^ w) * 0xBF58476D1CE4E5B9, h ^= h >> 29;
+ *   h = (h ^ h >> 27) * 0x94D049BB133111EB; h ^= h >> 31; key = h ? h : 1   (mod 2^64).
+ * Equality of keys stands for equality of identity: 64 bits, as Stockfish's own repetition
+ * test compares 64-bit keys.  The same value on the host and on the device.
+ * Rule.  For position k of a game (positions 0..=moves, skipped ones included; history starts
+ * at the root FEN, nothing before it is known) and a legal move m with child c: c is drawn by
+ * rule when c is not checkmated and either c.rule50 >= 100 (Stockfish: rule50 > 99 && (!checkers
+ * || a legal move exists)), or c's identity equals the identity of at least two of the game's
+ * positions 0..=k -- the third occurrence; a second occurrence is not a draw.
+ * Value, in this order of precedence: a checkmated child -VALUE_MATE and a child with no legal
+ * move and not in check 0 with GN_FLAG_NO_MOVES (both as gn_line above, without GN_FLAG_DRAW);
+ * a child drawn by rule V(c) = 0 with GN_FLAG_DRAW (and GN_FLAG_IN_CHECK if m gives check);
+ * otherwise the static final_v.  value = negate_ply(V), score = rule_score(value, ...), order by
+ * value descending, ties to the smaller move: all as gn_line.  A drawn line has value 0 and
+ * score 0 and ties with a static 0 by the move encoding.
+ * (The kernel tests only positions k + 1 - d for d = 4, 6, ... <= min(c.rule50, k + 1): a pawn
+ * move or a capture lies between c and anything older.  The result is that of the rule above.)
+ * A gn_history entry names a parent's game so far in a key array: keys[first..=self] are the
+ * keys of the game's positions up to and including the parent (self).  first > self, or self
+ * at or beyond the key count given with the array, means "no history": only the fifty-move part
+ * applies. */
+typedef struct gn_history {
+  uint32_t first, self;
+} gn_history;
 
 /* One ranked two-ply line of a position: a two-move principal variation (fishnet's
  * pvs[multipv][depth] is a Vec<UciMove>, not a single move) with its minimax value.
@@ -515,6 +561,17 @@ GN_API int gn_evaluate_games_lines(gn_ctx *ctx, const gn_game *games, size_t n_g
                                    uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                                    size_t position_cap, gn_line *lines);
 
+/* gn_evaluate_games_lines with the game-history draws (gn_history above): each game's positions
+ * 0..=k, skipped ones included, are position k's history.  Arguments, GN_E_CAPACITY behaviour,
+ * chunking, two-slot overlap and sharding as gn_evaluate_games_lines; position_offsets,
+ * game_status and position_out are byte-equal to its; the lines follow the rule at gn_history,
+ * and equal gn_evaluate_games_lines' wherever no legal move of the position is drawn by rule.
+ * The keys of every replayed position are made on the device once per shard
+ * (GN_STAT_KEYS_NS); GN_STAT_RANK_NS: the ranking's time. */
+GN_API int gn_evaluate_games_lines_history(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                           uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
+                                           size_t position_cap, gn_line *lines);
+
 /* Two-ply ranked lines from FENs: out[i] = position i's record (byte-equal to
  * gn_expand_and_evaluate's parent_out for the same FENs and mode), lines[i * n_lines + k] = line
  * k + 1 of position i (gn_line2).  The FENs are sharded equally over the context's devices; each
@@ -548,6 +605,9 @@ GN_API int gn_board_to_fen(const gn_board *board, char *buf, size_t buflen);
 /* n boards -> n NUL-terminated FENs at buf + i * stride (stride >= 100); an invalid
  * board gives "".  Host only, multithreaded. */
 GN_API int gn_boards_to_fens(const gn_board *boards, size_t n, char *buf, size_t stride);
+/* keys[i] = the position key of boards[i] (gn_history above); each board goes through the gate
+ * of a caller's board, a rejected board's key is 0.  Host only, needs no context. */
+GN_API int gn_position_keys(const gn_board *boards, size_t n, uint64_t *keys);
 /* Deterministic random-playout positions (xoshiro256**, seed + index): plays
  * k ~ U{0..max_plies} uniformly random legal plies from the start position
  * (stopping at mate/stalemate), resampling positions in check. Host only. */
@@ -594,6 +654,19 @@ GN_API int gn_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_pare
 GN_API int gn_rank_children_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
                                    const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out,
                                    int n_lines, gn_line *d_lines, void *stream);
+/* The same values as gn_position_keys for n device-resident boards, into d_keys[n]; one lane per
+ * board.  Asynchronous on `stream` (NULL = the context's own). */
+GN_API int gn_position_keys_device(gn_ctx *ctx, int device_slot, const gn_board *d_boards, size_t n,
+                                   uint64_t *d_keys, void *stream);
+/* gn_rank_children_device with the game-history draws (the rule at gn_history): d_hist[i] names
+ * parent i's game so far in d_keys[0, n_keys).  An entry with first > self or self >= n_keys is
+ * "no history" (the fifty-move part still applies); d_keys is never read at or beyond n_keys, and
+ * may be NULL when n_keys is 0.  Asynchronous, no read-back.  n_lines outside 1..GN_MAX_LINES:
+ * GN_E_INVALID. */
+GN_API int gn_rank_children_history_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                           const uint32_t *d_offsets, const uint16_t *d_moves,
+                                           const gn_eval *d_child_out, const uint64_t *d_keys, size_t n_keys,
+                                           const gn_history *d_hist, int n_lines, gn_line *d_lines, void *stream);
 /* Depth 2 (grandchildren): gn_expand_device, then every child's legal children
  * evaluated incrementally from the child's accumulator (a sibling block refreshes each
  * child from its predecessor through the king cache).  d_goffsets: total + 1 offsets of

@@ -56,6 +56,7 @@ pub const GN_STAT_FAST_BATCHES: c_int = 119;
 pub const GN_STAT_FAST_FALLBACKS: c_int = 120;
 pub const GN_STAT_RANK_NS: c_int = 121;
 pub const GN_STAT_RANK2_NS: c_int = 122;
+pub const GN_STAT_KEYS_NS: c_int = 123;
 
 // per-position flags
 pub const GN_FLAG_IN_CHECK: u16 = 1;
@@ -67,6 +68,7 @@ pub const GN_FLAG_MATE: u16 = 32;
 pub const GN_FLAG_NO_SCORE: u16 = 64;
 pub const GN_FLAG_SEARCHED: u16 = 128;
 pub const GN_FLAG_NO_MOVES: u16 = 256;
+pub const GN_FLAG_DRAW: u16 = 512;
 
 /// One result: NetworkOutput (psqt, positional) of the net that produced final_v,
 /// Eval::evaluate (internal units), UCIEngine::to_cp, and the score fishnet posts for the
@@ -119,6 +121,16 @@ pub struct gn_line {
     pub score: i32,
     pub r#move: u16,
     pub flags: u16,
+}
+
+/// A parent's game so far in a key array (gn_position_keys): keys[first..=self] are the keys of
+/// the game's positions up to and including the parent; first > self means "no history".  See
+/// the header at gn_history for the draw rule the history calls apply (GN_FLAG_DRAW lines).
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct gn_history {
+    pub first: u32,
+    pub r#self: u32,
 }
 
 /// One ranked two-ply line of a position (16 bytes): a two-move principal variation (`move`, then
@@ -222,6 +234,10 @@ extern "C" {
     pub fn gn_evaluate_games_lines(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
                                    n_lines: c_int, position_offsets: *mut u32, game_status: *mut i32,
                                    position_out: *mut gn_eval, position_cap: usize, lines: *mut gn_line) -> c_int;
+    pub fn gn_evaluate_games_lines_history(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
+                                           n_lines: c_int, position_offsets: *mut u32, game_status: *mut i32,
+                                           position_out: *mut gn_eval, position_cap: usize, lines: *mut gn_line)
+                                           -> c_int;
     pub fn gn_evaluate_lines2(ctx: *mut gn_ctx, fens: *const *const c_char, n: usize, mode: c_int, n_lines: c_int,
                               out: *mut gn_eval, lines: *mut gn_line2) -> c_int;
     pub fn gn_partition(weights: *const u32, n_items: usize, n_shards: c_int, bounds: *mut usize) -> c_int;
@@ -229,6 +245,7 @@ extern "C" {
     pub fn gn_pack_fens(fens: *const *const c_char, n: usize, out: *mut gn_board, ok: *mut u8) -> c_int;
     pub fn gn_board_to_fen(board: *const gn_board, buf: *mut c_char, buflen: usize) -> c_int;
     pub fn gn_boards_to_fens(boards: *const gn_board, n: usize, buf: *mut c_char, stride: usize) -> c_int;
+    pub fn gn_position_keys(boards: *const gn_board, n: usize, keys: *mut u64) -> c_int;
     pub fn gn_random_positions(seed: u64, first_index: usize, n: usize, max_plies: c_int, out: *mut gn_board)
                                -> c_int;
     // device-resident entry points (pointers are device memory of device_slot; stream: a
@@ -244,6 +261,12 @@ extern "C" {
     pub fn gn_rank_children_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
                                    d_offsets: *const u32, d_moves: *const u16, d_child_out: *const gn_eval,
                                    n_lines: c_int, d_lines: *mut gn_line, stream: *mut c_void) -> c_int;
+    pub fn gn_position_keys_device(ctx: *mut gn_ctx, device_slot: c_int, d_boards: *const gn_board, n: usize,
+                                   d_keys: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn gn_rank_children_history_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                                           d_offsets: *const u32, d_moves: *const u16, d_child_out: *const gn_eval,
+                                           d_keys: *const u64, n_keys: usize, d_hist: *const gn_history,
+                                           n_lines: c_int, d_lines: *mut gn_line, stream: *mut c_void) -> c_int;
     pub fn gn_rank_lines2_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
                                  d_offsets: *const u32, d_children: *const gn_board, d_child_out: *const gn_eval,
                                  d_moves: *const u16, d_goffsets: *const u32, d_gmoves: *const u16,
