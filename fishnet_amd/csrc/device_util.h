@@ -298,8 +298,8 @@ __device__ __forceinline__ int32_t wave_sum_dpp(int32_t v) {
   return __builtin_amdgcn_readlane((int)scan_add((uint32_t)v), 63);
 }
 
-// ---- the column-sliced stream's finishing step for one position (slice_finish_kernel, and
-// finalize_kernel when it takes the big net's outputs from the partial sums itself): the NPART
+// ---- the column-sliced stream's finishing step for one position (finalize_kernel, which
+// takes the big net's outputs from the partial sums itself): the NPART
 // slices' fc_0 sums (part[t * npos + q][16]) + bias, the activations, fc_1, fc_2 -- the
 // whole-row kernel's finishing step in scalar integer arithmetic (exact: every sum is an
 // integer sum, the wrapping adds as there).  info = pinfo[q] (PSQT value, bucket >= 0).
@@ -356,13 +356,6 @@ __device__ __forceinline__ int2 slice_finish_from(const NetDevice &net, const in
   }
   const int32_t positional = wadd(wadd(net.b2[b], sum), fwd);
   return make_int2(info.x / 16, positional / 16);
-}
-template <int NPART>
-__device__ __forceinline__ int2 slice_finish_one(const NetDevice &net, const int4v *w1s, const int32_t *__restrict__ part,
-                                                 uint64_t npos, uint64_t q, int2 info) {
-  int4v sums[4];
-  slice_sums<NPART>(part, npos, q, sums);
-  return slice_finish_from(net, w1s, sums, info);
 }
 
 } // namespace gn

@@ -662,25 +662,11 @@ static int create(const uint8_t *big, size_t big_len, const uint8_t *small, size
     HIP_TRY(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&d.done, hipEventDisableTiming));
     HIP_TRY(hipStreamCreateWithFlags(&d.copy, hipStreamNonBlocking));
-#ifdef GN_AB_FRONT_PRIORITY // A/B: the pipeline's front stream at the device's highest priority
-    {
-      int least = 0, greatest = 0;
-      HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-      HIP_TRY(hipStreamCreateWithPriority(&d.front, hipStreamNonBlocking, greatest));
-    }
-#else
     HIP_TRY(hipStreamCreateWithFlags(&d.front, hipStreamNonBlocking));
-#endif
     HIP_TRY(hipEventCreateWithFlags(&d.ev_streamed, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&d.ev_planned, hipEventDisableTiming));
     for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&d.cev[i], hipEventDisableTiming));
     for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&d.rev[i]));
-#ifdef GN_AB_AUX_STREAMS // A/B only: two extra streams, as the removed range pipeline had
-    {
-      hipStream_t x[2];
-      for (int i = 0; i < 2; ++i) HIP_TRY(hipStreamCreateWithFlags(&x[i], hipStreamNonBlocking));
-    }
-#endif
     HIP_TRY(hipMalloc(&d.tables, sizeof(Tables)));
     for (ExpSet *x : {&d.cur, &d.alt}) { // the planned expansion's error word and pad count
       HIP_TRY(x->perr.ensure(1));
@@ -1055,18 +1041,16 @@ static int expand_evaluate(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t 
   }
   if (!(phases & EXP_BACK)) return GN_OK;
   // ---- the back half: the big net's row stream, finalize
-  bool fused = false; // the sliced stream's finish runs inside finalize
+  // (the sliced stream's finish runs inside finalize)
+  const bool sliced = mode != GN_MODE_SMALL && x.planned && x.slices > 1;
   if (mode != GN_MODE_SMALL) {
     if (x.planned) {
       HIP_TRY(hipMemsetAsync(d.pool.p, 0, 88 * sizeof(uint32_t), s)); // per stream launch (<= 3)
-#ifndef GN_AB_FINISH_SEPARATE // A/B (round 4): slice_finish_kernel, then finalize
-      fused = x.slices > 1;
-#endif
       if (ev && (phases & EXP_FRONT) == 0) HIP_TRY(hipEventRecord(ev[7], s)); // (the pipeline: the stream's start)
       PlanStreamArgs a = plan_args();
       a.swz = (ctx->swizzle >> 2) & 1 ? 1 : (ctx->swizzle >> 3) & 1 ? 2 : 0;
       a.order = ordered ? x.border.p : nullptr;
-      a.fin = ev ? ev[6] : nullptr, a.streamed = o.streamed, a.finish = !fused;
+      a.fin = ev ? ev[6] : nullptr, a.streamed = o.streamed;
       HIP_TRY(launch_plan_stream(d.net[BIG], a, STREAM_PHASE, s));
     } else { // a 128-wide net loaded as the big net
       HIP_TRY(launch_expand_net(d.net[BIG], parents, n, off, children, dl, f ? x.p_nbg.p : nullptr,
@@ -1074,7 +1058,7 @@ static int expand_evaluate(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t 
     }
   }
   HIP_TRY(mark(2));
-  int rc = finalize_all(ctx, d, parents, children, mode, parent_out, child_out, n, total, s, o.score_parents, fused);
+  int rc = finalize_all(ctx, d, parents, children, mode, parent_out, child_out, n, total, s, o.score_parents, sliced);
   if (rc) return rc;
   HIP_TRY(mark(3));
   return GN_OK;
@@ -1245,13 +1229,8 @@ static int fast_build(gn_ctx *ctx, Dev &d, FastBatch &f, size_t nb, int mode) {
     HIP_TRY(launch_reply_level(f.r1, f.c1, d.tables, f.off1.p, f.c2, f.r2, f.m2.p, flag, 0, s));
     int rc = evaluate_on(ctx, d, f.all.p, na, mode, f.out, s, nullptr, nullptr, 1, nullptr, &f.eb, false);
     if (rc) return rc;
-#ifndef GN_AB_FAST_TWO_REDUCES // A/B: the two reductions as two launches
     HIP_TRY(launch_score_reduce2(f.r1, f.c1, f.off1.p, f.m2.p, f.e2, f.sv2.p, f.e1, f.sv1.p, f.in, nb, f.off0.p, f.m1.p,
                                  ctx->P, f.out, s));
-#else
-    HIP_TRY(launch_score_reduce(f.r1, f.c1, nullptr, f.off1.p, f.m2.p, f.e2, f.sv2.p, ctx->P, f.e1, f.sv1.p, s));
-    HIP_TRY(launch_score_reduce(f.in, nb, nullptr, f.off0.p, f.m1.p, f.e1, f.sv1.p, ctx->P, f.out, nullptr, s));
-#endif
     HIP_TRY(hipMemcpyAsync(f.h_out, f.rec.p, (nb + 1) * sizeof(gn_eval), hipMemcpyDeviceToHost, s));
     return GN_OK;
   };

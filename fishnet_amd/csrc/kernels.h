@@ -46,7 +46,7 @@ static_assert(GN_FRONT_WG == 64 || GN_FRONT_WG == 128 || GN_FRONT_WG == 256, "fr
 constexpr unsigned ENT_SPARE = 32;
 
 // The column-sliced stream's fc_0 partial sums: one array per slice (default), which
-// slice_finish_kernel adds; or, with -DGN_PART_INPLACE (A/B only), one array that each slice
+// finalize_kernel adds; or, with -DGN_PART_INPLACE (A/B only), one array that each slice
 // s > 0 adds its sums to in place, reading slice s - 1's at the tile's start.  In place measured
 // slower (round 5: finish 5.44 -> 2.75 ms, but each later stream launch +2.1 ms: the prefetch
 // misses to HBM and, vector-memory completion being in order, holds up the ring's next loads).
@@ -111,8 +111,8 @@ static_assert(sizeof(TileDesc) == 192, "TileDesc is 192 bytes");
 // of them), entries at ent + eoff[pbeg] + ENT_SPARE * block (list 0 upward, list 1 downward from
 // the region's end, eoff = exclusive scan of write_children's per-parent entry bounds).
 // One call plans and / or evaluates every block of the n parents.
-// phases: PLAN_PHASE (the pinfo reset and plan_kernel) and / or STREAM_PHASE (the stream launches
-// and the finish), so that an expansion's plan can run on another stream than its row stream (the
+// phases: PLAN_PHASE (the pinfo reset and plan_kernel) and / or STREAM_PHASE (the stream
+// launches), so that an expansion's plan can run on another stream than its row stream (the
 // expansion pipeline, gpu_nnue.hip): the two calls take the same PlanStreamArgs, and differ in
 // phases, swz and the events.
 constexpr int PLAN_PHASE = 1, STREAM_PHASE = 2;
@@ -140,19 +140,17 @@ struct PlanStreamArgs {
   unsigned long long *pads_out = nullptr; // (optional) += no-op entries the plan inserted to keep GN_SCR_GAP
   const uint32_t *order = nullptr;        // block order of the stream (block_order) or NULL
   // slices == 3 (L1 3072; part, pinfo non-null): the stream runs as three launches over 1,024
-  // columns each (stream_eval_kernel<3072, 3>) and slice_finish_kernel; part = GN_PART_SLICES x npos
-  // x 16 int32 fc_0 partial sums, pinfo = npos (PSQT value, bucket) pairs (written by the plan),
-  // npos = n + the children; otherwise one launch over whole rows
+  // columns each (stream_eval_kernel<3072, 3>); part = GN_PART_SLICES x npos x 16 int32 fc_0
+  // partial sums, pinfo = npos (PSQT value, bucket) pairs (written by the plan), npos = n + the
+  // children; out_parent / out_child stay unwritten: the caller's launch_finalize takes the big
+  // net's outputs from part and pinfo itself (SlicedOut).  Otherwise one launch over whole rows
   int slices = 1;
   int32_t *part = nullptr;
   size_t npos = 0;
   int2 *pinfo = nullptr;
-  // finish false (sliced stream): no slice_finish_kernel, out_parent / out_child stay unwritten:
-  // the caller's launch_finalize takes the big net's outputs from part and pinfo itself
-  bool finish = true;
   int swz = 0;
   hipEvent_t mid = nullptr;                     // (optional) recorded between the kernels
-  hipEvent_t fin = nullptr, streamed = nullptr; // (optional) recorded after the stream launches (before the finish)
+  hipEvent_t fin = nullptr, streamed = nullptr; // (optional) recorded after the stream launches
 };
 hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int phases, hipStream_t s);
 // GN_MODE_FULL preparation: need_small = valid && |simple_eval| > threshold,
@@ -169,7 +167,7 @@ hipError_t launch_reeval(const int2 *out_small, const uint8_t *need_small, size_
 // owner / moves / unpacked (optional, children only): board i is unpacked[owner[i]] after
 // moves[i] (the parents write_children unpacked), instead of unpacking boards[i].
 // sliced (optional): the column-sliced stream's partial sums of the big net; position i's big-net
-// output is then slice_finish_one of pinfo[qoff + i] (out_big[i] where pinfo.y < 0)
+// output is then slice_finish_from its slice_sums and pinfo[qoff + i] (out_big[i] where pinfo.y < 0)
 struct SlicedOut {
   const NetDevice *net;
   const int32_t *part;

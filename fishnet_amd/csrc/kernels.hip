@@ -738,13 +738,8 @@ hipError_t launch_eval_net(const NetDevice &net, const gn_board *boards, const u
   // <= 1,024 positions, the drop-in's one game per call with its reply levels: p50 0.176 -> 0.169
   // ms, r06s)
   unsigned tn = 16;
-#ifndef GN_TN_MIN
-#define GN_TN_MIN (n <= 1024 ? 1u : 2u)
-#endif
-#ifndef GN_AB_TN16 // A/B: 16 positions per workgroup at every batch size
   if (net.L1 != 128)
-    while (tn > (GN_TN_MIN) && (n + tn - 1) / tn < 2048) tn >>= 1;
-#endif
+    while (tn > (n <= 1024 ? 1u : 2u) && (n + tn - 1) / tn < 2048) tn >>= 1;
   const unsigned tiles = (unsigned)((n + tn - 1) / tn);
   const unsigned grid = swz ? 8 * ((tiles + 7) / 8) : tiles;
   if (net.L1 == 3072) {
@@ -805,8 +800,9 @@ __global__ void finalize_kernel(const gn_board *__restrict__ boards, size_t n, i
                                 NetDevice bnet, const int32_t *__restrict__ part, const int2 *__restrict__ pinfo,
                                 uint64_t npos, uint64_t qoff) {
   __shared__ Tables T;
-  // (part: the big net's outputs from the sliced stream's partial sums, slice_finish_one --
-  // its reads then overlap this kernel's arithmetic instead of running as a kernel of their own)
+  // (part: the big net's outputs from the sliced stream's partial sums, slice_sums and
+  // slice_finish_from -- their reads overlap this kernel's arithmetic instead of running as a
+  // kernel of their own)
   __shared__ int4v w1s[8 * 32 * 2];
   if (part) stage_fc1(w1s, bnet);
   load_tables(T, tables);
@@ -814,17 +810,6 @@ __global__ void finalize_kernel(const gn_board *__restrict__ boards, size_t n, i
   // per workgroup and many positions, not once per 256 (480 k workgroups per expansion)
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-#ifdef GN_AB_FIN_LATE_SUMS // A/B: the sums loaded where the output is needed (after the board)
-    auto big_out = [&](size_t j) -> int2 {
-      if (part) {
-        const int2 info = pinfo[qoff + j];
-        if (info.y >= 0) return slice_finish_one<GN_PART_SLICES>(bnet, w1s, part, npos, qoff + j, info);
-      }
-      return out_big[j];
-    };
-    const uint32_t ow = CHILD ? owner[i] : 0u;
-    const uint16_t mv = CHILD ? moves[i] : (uint16_t)0;
-#else
     // the owner and move, then (part) the position's slice sums, all loaded before anything waits:
     // the sums' HBM round trip runs beside the owner -> parent board chain instead of after the
     // board work (owner, parent, pinfo, sums were three round trips in a row)
@@ -841,7 +826,6 @@ __global__ void finalize_kernel(const gn_board *__restrict__ boards, size_t n, i
     auto big_out = [&](size_t j) -> int2 {
       return part && info.y >= 0 ? slice_finish_from(bnet, w1s, sums, info) : out_big[j];
     };
-#endif
     Board B;
     gn_eval e = {0, 0, 0, 0, 0, 0, 0};
     if constexpr (CHILD) {
@@ -1160,15 +1144,8 @@ __global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(si
             if (C.rule50 >= 100) {
               draw = 1;
             } else if (lim >= 4) {
-#ifdef GN_AB_HIST_NO_KEY // A/B only (wrong draws): the walk's loads without the key arithmetic
-              const uint64_t ck = C.byType[0];
-#else
               const uint64_t ck = position_key(C);
-#endif
               uint32_t seen = 0;
-#ifdef GN_AB_HIST_NO_WALK // A/B only (wrong draws): the key arithmetic without the walk's loads
-              seen = ck == 0x5EEDull ? 2u : 0u;
-#else
               // four keys per trip, their loads independent of each other (a trip's tail re-reads
               // d = 4, which lim >= 4 makes valid, and ignores it); the walk ends between trips
               const uint64_t *const at = (history.keys, ...) + ((size_t)hself + 1);
@@ -1180,7 +1157,6 @@ __global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(si
                   seen += in && k == ck ? 1u : 0u;
                 }
               }
-#endif
               draw = seen >= 2 ? 1u : 0u;
             }
           }

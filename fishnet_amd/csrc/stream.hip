@@ -64,14 +64,9 @@
 #endif                 // bound (130 unbounded, i.e. 3 per SIMD).  (Round 4: with the finish in the last slice,
                        // 125 + 8 AGPRs, 3 per SIMD 157.1 ms, forced to 4 160.4 ms)
 #define GN_PART_N GN_PART_SLICES
-#ifndef GN_WCACHE // the sliced stream's per-wave fc_0 weight cache (0: weights loaded at each layer stack)
-#define GN_WCACHE 1
-#endif
 #ifndef GN_EXPAND_WPE
 #define GN_EXPAND_WPE (GN_RING == 4 ? 5 : 4)
 #endif
-#define GN_STR2(x) #x
-#define GN_STR(x) GN_STR2(x)
 
 #ifdef GN_STREAM_PROF
 // diagnostics build only: per-phase s_memtime cycles summed over waves, and list balance
@@ -127,11 +122,8 @@ __device__ __forceinline__ uint32_t hs(int slot, int side, uint32_t xu, uint32_t
 constexpr bool lds_field16(int XS, int LC) {
   return XS % 16 == 0 && (LC / 2) % 16 == 0 && 15 * (XS / 16) + LC / 32 < 1024;
 }
-#ifndef GN_SLICE_XPAD // A/B: LDS bytes added per tile row of the sliced stream (fewer workgroups per CU)
-#define GN_SLICE_XPAD 0
-#endif
 // the stream's LDS tile row (bytes) for L1 / SL columns, and the plan's (xu, hu) for it
-constexpr int tile_xs(int L1, int SL) { return L1 / SL + 16 + (SL > 1 ? GN_SLICE_XPAD : 0); }
+constexpr int tile_xs(int L1, int SL) { return L1 / SL + 16; }
 constexpr uint32_t field_xu(int L1, int SL) {
   return lds_field16(tile_xs(L1, SL), L1 / SL) ? (uint32_t)tile_xs(L1, SL) / 16 : 2u;
 }
@@ -166,9 +158,6 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
   const __amdgpu_buffer_rsrc_t pst = __builtin_amdgcn_make_buffer_rsrc(
       (void *)net.psqt, 0, (int)((size_t)PSQT_BUCKETS * FT_ROWS * 4), 0x00020000);
   auto psqt = [&](uint32_t row, int bucket) -> int32_t { // bucket-major copy (L2-resident)
-#ifdef GN_AB_PLAN_NOPSQT // timing diagnostics only (wrong PSQT): the plan without its PSQT loads
-    return (int32_t)(row + bucket);
-#endif
     return (int32_t)__builtin_amdgcn_raw_buffer_load_b32(pst, (bucket * (uint32_t)FT_ROWS + row) * 4, 0, 0);
   };
   const uint32_t pbeg = blk * K, pend = pbeg + K < np ? pbeg + K : np;
@@ -776,7 +765,7 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
 // whole 3072-wide rows of one bucket pair, 8.6 MB, exceed its 4 MB).  A slice's fc_0 sums are
 // partial: every slice stores them (part[slice][position][16], position = the output index:
 // parent P, or np + child) and slice 0 the position's PSQT value and layer-stack bucket
-// (pinfo[position]); slice_finish_kernel adds the SL sums (wrapping int32 adds, as the LDS
+// (pinfo[position]); finalize_kernel adds the SL sums (wrapping int32 adds, as the LDS
 // atomics: the sum is the whole-row kernel's exactly) and runs the rest of the layer stack.
 // (The last slice finishing in its own launch, one of its two waves per bucket, took 59.6 ms
 // against 49 for the others.)
@@ -976,23 +965,15 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
   const uint32_t scr_off = (scr - (uint32_t)FT_ROWS) * RS - L_SCR;
   auto offset = [&](uint32_t lo, uint32_t h) -> uint32_t {
     (void)h;
-#ifdef GN_ABLATE_ROWS
-    (void)lo, (void)h;
-    return (uint32_t)FT_BIAS_ROW * RS; // timing diagnostics build only: every row from L1 / L2
-#else
     return lo + ((uint32_t)((int32_t)lo >> 31) & scr_off);
-#endif
   };
   auto issue = [&](int r, uint32_t lo, uint32_t h) {
     eh[r] = h;
     // the ring's loads are invisible to the compiler's wait insertion (which, merging the
     // paths of the entry kinds at the loop head, waits for far more of the ring than an entry
     // needs); consume() waits for exactly its own row: see ring_wait
-#ifndef GN_ROW_POLICY
-#define GN_ROW_POLICY "" // A/B: cache-policy modifiers of the row loads (e.g. " nt")
-#endif
-    asm volatile("buffer_load_dwordx4 %0, %2, %3, %4 offen" GN_ROW_POLICY "\n\t"
-                 "buffer_load_dwordx4 %1, %2, %3, %4 offen offset:%5" GN_ROW_POLICY
+    asm volatile("buffer_load_dwordx4 %0, %2, %3, %4 offen\n\t"
+                 "buffer_load_dwordx4 %1, %2, %3, %4 offen offset:%5"
                  : "=&v"(rlo[r]), "=&v"(rhi[r])
                  : "v"(j16), "s"(rsq), "s"(offset(lo, h)), "n"(L1));
   };
@@ -1011,20 +992,6 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
   auto consume = [&](int r) {
     ring_wait(r);
     const uint32_t h = eh[r];
-#ifdef GN_AB_SALU_PLUS // timing diagnostics only: N extra independent scalar ALU instructions per entry
-    {
-      uint32_t d0, d1;
-      asm volatile(".rept " GN_STR(GN_AB_SALU_PLUS) " / 2\n\ts_add_u32 %0, %2, 1\n\ts_add_u32 %1, %2, 2\n\t.endr"
-                   : "=&s"(d0), "=&s"(d1) : "s"(h));
-    }
-#endif
-#ifdef GN_AB_VALU_PLUS // timing diagnostics only: N extra independent vector ALU instructions per entry
-    {
-      uint32_t d0, d1;
-      asm volatile(".rept " GN_STR(GN_AB_VALU_PLUS) " / 2\n\tv_mov_b32 %0, %2\n\tv_mov_b32 %1, %2\n\t.endr"
-                   : "=&v"(d0), "=&v"(d1) : "v"(j16));
-    }
-#endif
     // every entry is one 16-bit multiply-add per dword, acc = src + sg * row, its multiplier
     // sg (1, 0xFFFF = -1, 0) the low half of h as the instruction's scalar operand; src is
     // the accumulator, or (an init) 0 / the parent / the sibling base at a slot's first entry
@@ -1032,34 +999,6 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
     // test per branch, each kind with its own multiply-adds (the compiler's version of this tree
     // copied the source registers on every path and spilled): a plain entry costs two scalar
     // instructions, an init five to seven.
-#ifdef GN_AB_WHOLE_CDECODE // diagnostics: the whole-row stream with the compiler's decode (round 5's)
-    if constexpr (SL == 1) {
-      const unsigned short sg = (unsigned short)h;
-      const uint32_t init = (h >> 16) & 3u;
-      ushort8 lo = __builtin_bit_cast(ushort8, make_uint4(A[0], A[1], A[2], A[3]));
-      ushort8 hi = __builtin_bit_cast(ushort8, make_uint4(A[4], A[5], A[6], A[7]));
-      if (init) {
-        asm volatile("");
-        if (init == 2) {
-          lo = __builtin_bit_cast(ushort8, make_uint4(PA[0], PA[1], PA[2], PA[3]));
-          hi = __builtin_bit_cast(ushort8, make_uint4(PA[4], PA[5], PA[6], PA[7]));
-        } else if (init == 3) {
-          lo = __builtin_bit_cast(ushort8, make_uint4(BA[0], BA[1], BA[2], BA[3]));
-          hi = __builtin_bit_cast(ushort8, make_uint4(BA[4], BA[5], BA[6], BA[7]));
-        } else {
-          lo = ushort8{}, hi = ushort8{};
-        }
-      }
-      lo = rlo[r] * sg + lo, hi = rhi[r] * sg + hi;
-      const uint4 l4 = __builtin_bit_cast(uint4, lo), h4 = __builtin_bit_cast(uint4, hi);
-      A[0] = l4.x, A[1] = l4.y, A[2] = l4.z, A[3] = l4.w, A[4] = h4.x, A[5] = h4.y, A[6] = h4.z, A[7] = h4.w;
-      if (init == 2) {
-        asm volatile("");
-#pragma unroll
-        for (int i = 0; i < 8; ++i) BA[i] = A[i];
-      }
-    } else
-#endif
     {
       const uint4 rl = __builtin_bit_cast(uint4, rlo[r]), rh = __builtin_bit_cast(uint4, rhi[r]);
       uint32_t t;
@@ -1126,11 +1065,7 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
       constexpr bool FIELD16 = lds_field16(XS, LC);
       const uint32_t la = FIELD16 ? (h >> H_LDS_SH) << 4
                                   : (h >> (H_LDS_SH + 1)) * (uint32_t)XS + ((h >> H_LDS_SH) & 1) * (uint32_t)(LC / 2);
-#ifdef GN_AB_NO_TRANSFORM // timing diagnostics only (wrong results): the accumulator's low bytes, untransformed
-      *reinterpret_cast<uint2 *>(xt + la + 8 * jt) = make_uint2(lo[0] | (uint32_t)hi[0] << 16, lo[1]);
-#else
       *reinterpret_cast<uint2 *>(xt + la + 8 * jt) = transform8(lo, hi);
-#endif
       if (h & H_X) {
       if (h & (H_PAR_E & ~H_X)) {
         asm volatile("");
@@ -1140,12 +1075,9 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
       if (h & (H_KST & ~H_X)) { // the accumulator to its king-cache row
         asm volatile("");
         const uint32_t so = (scr + (h & 0xFFFFu)) * RS;
-#ifndef GN_KC_ASM_POLICY
-// cache policy of the king-cache stores: "" = default.  The same-address store -> load order
-// the reload relies on is pinned for default-policy stores only (kernels.h); non-temporal
-// (" nt") measured 205.5 -> 205.0 ms, within noise, so it stays an A/B build option
-#define GN_KC_ASM_POLICY ""
-#endif
+        // cache policy of the king-cache stores: default.  The same-address store -> load order
+        // the reload relies on is pinned for default-policy stores only (kernels.h); non-temporal
+        // (" nt") measured 205.5 -> 205.0 ms, within noise
         // Both halves in one asm block: the high half at the instruction's immediate offset, and a
         // wait state after the pair before any VALU may overwrite their data registers.  (As two
         // builtins, the whole-row kernel at its 96-VGPR cap computed the second address into a data
@@ -1154,8 +1086,8 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
         // then held wrong values now and then, round 6, test_stream_column_slices_equal_whole_rows.
         // A VALU write to the data VGPRs of a > 64-bit store needs one wait state on this family.)
         static_assert(L1 < 4096, "the high half's offset fits the 12-bit immediate");
-        asm volatile("buffer_store_dwordx4 %0, %2, %3, %4 offen" GN_KC_ASM_POLICY "\n\t"
-                     "buffer_store_dwordx4 %1, %2, %3, %4 offen offset:%5" GN_KC_ASM_POLICY "\n\t"
+        asm volatile("buffer_store_dwordx4 %0, %2, %3, %4 offen\n\t"
+                     "buffer_store_dwordx4 %1, %2, %3, %4 offen offset:%5\n\t"
                      "s_nop 0"
                      :
                      : "v"(__builtin_bit_cast(int4v, lo)), "v"(__builtin_bit_cast(int4v, hi)), "v"(j16), "s"(rsq),
@@ -1218,12 +1150,9 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
       if (m & 1) bm |= 1u << ((m >> 1) & 7);
       if (m & 16) pm |= 1u << sl;
     }
-#ifdef GN_AB_NO_LS // timing diagnostics only (no outputs): the stream without its layer stack
-    bm = 0;
-#endif
     bool wpend = false; // (SL > 1) the cache was loaded at this tile's start
     const uint32_t pos0 = pos;
-    if constexpr (SL > 1 && GN_WCACHE) {
+    if constexpr (SL > 1) {
       if (bm && !((bm >> cb) & 1)) {
         cb = __builtin_ctz(bm);
         wc_load(cb);
@@ -1249,11 +1178,7 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
     // revolution starts at a multiple of 4: it waits for its prefetched group of entries,
     // whose rows it issues, and prefetches the next); the steps of a partial revolution are
     // guarded by uniform tests, whole revolutions run unguarded (sliced stream)
-#ifdef GN_AB_GUARDED // A/B (round 4): every entry behind its own guard
-    constexpr bool REV = false;
-#else
     constexpr bool REV = SL > 1; // (the whole-row stream, at its 96-VGPR cap, spills with it)
-#endif
     // the tile's first partial revolution (guarded), then whole revolutions without per-entry
     // guards (each took 7 scalar instructions and a branch), then the last partial one (guarded)
     if constexpr (REV) {
@@ -1305,9 +1230,7 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
     }
     asm volatile("" ::: "memory");
     const unsigned long long t1 = SP_T();
-#ifndef GN_AB_NO_BARRIER // timing diagnostics only (racy, wrong results): the layer stack without barriers
     __syncthreads();
-#endif
     const unsigned long long t2 = SP_T();
     sp_s += t1 - t0, sp_w += t2 - t1;
     // ---- layer stack: per bucket of the tile, fc_0 by all waves (int8 MFMA over this wave's
@@ -1321,7 +1244,7 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
       // copy the registers before the wait)
       if ((wpend || (GN_PART_N == 1 && slice > 0)) && pos - pos0 < (uint32_t)RD)
         __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
-      if constexpr (GN_WCACHE) GN_WC_WAIT(RWAIT_PV);
+      GN_WC_WAIT(RWAIT_PV);
       if constexpr (GN_PART_N == 1) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(pv) : "n"(RWAIT_PV));
     }
     // (SL > 1: the cached bucket first, as bit 8 of mm; the others load the cache when they come)
@@ -1335,7 +1258,7 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
       int tl = tid;
       asm volatile("" : "+v"(tl));
       const int ln = tl & 63, row = ln & 15, kg = ln >> 4;
-      if constexpr (SL > 1 && GN_WCACHE) {
+      if constexpr (SL > 1) {
         if (b != cb) { // a tile's second bucket: the cache's fill now, behind the ring's loads
           cb = b;
           wc_load(b);
@@ -1359,16 +1282,7 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
       } else {
         const uint8_t *xa = xt + row * XS + kg * 16 + 64 * KPW * wave;
         // (w0f: the k-step's 64 lanes x 16 B are one contiguous 1 KiB)
-        // (SL > 1: wave w of perspective h covers the net's k-steps of its slice of that side)
-        constexpr int WH = NW / 2;
-        const int wsl = SL > 1 ? (wave / WH) * WH * SL + slice * WH + wave % WH : wave;
-#ifdef GN_AB_W0_FIXED // timing diagnostics only (wrong results): every k-step's weights from one 1-KiB block
-        const int8_t *wb = net.w0f + (size_t)ln * 16;
-        constexpr int WSTEP = 0;
-#else
-        const int8_t *wb = net.w0f + (((size_t)b * KSF + KPW * wsl) * 64 + ln) * 16;
-        constexpr int WSTEP = 1024;
-#endif
+        const int8_t *wb = net.w0f + (((size_t)b * KSF + KPW * wave) * 64 + ln) * 16;
         int4v acc = {0, 0, 0, 0};
         // (batches of FB k-steps: the next tile's rows stay in flight in registers meanwhile)
         // (`stop`, always 0, is opaque to the compiler: without a runtime exit test it schedules the
@@ -1381,7 +1295,7 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
         for (int k0 = 0; k0 < KPW && !stop; k0 += FB) {
           int4v wv[FB], av[FB];
 #pragma unroll
-          for (int j = 0; j < FB; ++j) wv[j] = *reinterpret_cast<const int4v *>(wb + WSTEP * (k0 + j));
+          for (int j = 0; j < FB; ++j) wv[j] = *reinterpret_cast<const int4v *>(wb + 1024 * (k0 + j));
 #pragma unroll
           for (int j = 0; j < FB; ++j) av[j] = *reinterpret_cast<const int4v *>(xa + 64 * (k0 + j));
 #pragma unroll
@@ -1390,9 +1304,7 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
 #pragma unroll
         for (int i = 0; i < 4; ++i) atomicAdd(&acc0[buf][(4 * kg + i) * AS + row], acc[i]);
       }
-#ifndef GN_AB_NO_BARRIER
       __syncthreads();
-#endif
       // a position's output index (parent P, or np + its child index) and whether it is evaluated
       // in bucket b
       auto present = [&](int pos) -> bool {
@@ -1525,24 +1437,6 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
 #endif
 }
 
-// The column-sliced stream's finish when finalize does not take it over (a thread per position,
-// slice_finish_one).  pinfo.y < 0: a position the big net does not evaluate (left as it is).
-template <int SL>
-__global__ void __launch_bounds__(256) slice_finish_kernel(NetDevice net, const int32_t *__restrict__ part,
-                                                           const int2 *__restrict__ pinfo, uint64_t npos, uint32_t np,
-                                                           int2 *__restrict__ out_parent, int2 *__restrict__ out_child) {
-  __shared__ int4v w1s[8 * 32 * 2];
-  stage_fc1(w1s, net);
-  __syncthreads();
-  const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= npos) return;
-  const int2 info = pinfo[q];
-  if (info.y < 0) return;
-  const int2 val = slice_finish_one<GN_PART_N>(net, w1s, part, npos, q, info);
-  if (q < np) out_parent[q] = val;
-  else out_child[q - np] = val;
-}
-
 hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int phases, hipStream_t s) {
   const size_t n = a.n;
   if (!n) return hipSuccess;
@@ -1572,16 +1466,13 @@ hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int
       if (a.mid) (void)hipEventRecord(a.mid, s);
     }
     if (!do_stream) {
-    } else if (sliced) { // three launches over 1,024 columns each (claim counters pool[64 + 8 slice ..]),
-      // then the finish
+    } else if (sliced) { // three launches over 1,024 columns each (claim counters pool[64 + 8 slice ..]);
+      // the caller's finalize takes the outputs from part itself
       for (int sl = 0; sl < 3; ++sl)
         hipLaunchKernelGGL((stream_eval_kernel<3072, 3>), dim3(g), dim3(128), 0, s, net, a.offsets, (uint32_t)n, K, B0,
                            B1, a.swz, a.eoff, a.ent, a.tiles, a.btiles, a.order, a.out_parent, a.out_child, a.pool, scr,
                            a.err, a.pool + 64 + 8 * sl, sl, a.part, (uint64_t)a.npos, a.pinfo);
       stream_done();
-      if (a.finish) // (otherwise the caller's finalize takes the outputs from part itself)
-        hipLaunchKernelGGL((slice_finish_kernel<3>), dim3((unsigned)((a.npos + 255) / 256)), dim3(256), 0, s, net,
-                           a.part, a.pinfo, (uint64_t)a.npos, (uint32_t)n, a.out_parent, a.out_child);
     } else {
       hipLaunchKernelGGL((stream_eval_kernel<3072>), dim3(g), dim3(384), 0, s, net, a.offsets, (uint32_t)n, K, B0, B1,
                          a.swz, a.eoff, a.ent, a.tiles, a.btiles, a.order, a.out_parent, a.out_child, a.pool, scr, a.err,

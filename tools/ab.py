@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """A/B driver for the GPU box: runs bench.py once per variant and prints one line each.
 
-A variant is a library build (fishnet_amd/lib/<name>.so, built beforehand on the CPU with
-`python -m fishnet_amd.build -DNAME=VALUE --out=<name>.so`) and/or environment settings
-(GN_ABLATE, GN_STREAM=old, GN_BLOCK_SORT=0, ...), plus bench.py arguments shared by all.
+A variant is a library build (fishnet_amd/lib/<name>.so, built beforehand on the CPU, e.g.
+`python -m fishnet_amd.build -DGN_SCR_GAP=7 --out=libgpu_nnue_gap7.so`), plus bench.py arguments
+shared by all.  The library reads no environment setting; the only one the Python side reads is
+GPU_NNUE_LIB, which this script sets per variant (--env adds settings for the bench process
+itself, e.g. the HIP runtime's).
 
-    python tools/ab.py --variants libgpu_nnue.so libgpu_nnue_gap7.so \
-        --env "" "GN_BLOCK_SORT=0" -- --positions 16384 --steps 3
+    python tools/ab.py --variants libgpu_nnue.so libgpu_nnue_gap7.so -- --positions 16384 --steps 3
 
 runs every (library x env) pair; each run gets its own time limit and the script stops at the
 first failing run (no retries on the GPU).  Output: gpurun_out/ab/<tag>.json per run and a
