@@ -1928,7 +1928,8 @@ static std::string move_token(const gn_game &g, size_t k) {
 }
 
 // ---- gn_evaluate_games, and (n_lines > 0) gn_evaluate_games_lines: the expansion with children,
-// whose chunks are ranked on the device instead of downloaded (no child array, no child capacity).
+// whose chunks are ranked on the device instead of downloaded (no child array, no child capacity);
+// and (lines2) gn_evaluate_games_lines2: the same front, then the two-ply lines' chunk loop.
 
 // One device's share of a games call.  In place (the common case): every game of the device
 // replayed and none has a skipped position, so its evaluated positions are the replay's boards as
@@ -1946,7 +1947,8 @@ struct GameShard {
   std::vector<uint32_t> src, where; // gathered: each one's board in rboards / index in position_out
   std::vector<size_t> starts;       // first evaluated position of each game (the chunks' cuts)
   std::vector<gn_eval> res;         // gathered: the evaluated positions' records ...
-  std::vector<gn_line> lres;        // ... and lines
+  std::vector<gn_line> lres;        // ... and lines ...
+  std::vector<gn_line2> l2res;      // ... or two-ply lines
   std::vector<gn_history> hist;     // history call: each evaluated position's game so far, in rboards' indices
   std::vector<uint64_t> off;        // child offsets from pass 1 (m + 1, relative)
   uint64_t child_base = 0;          // the shard's first child in the caller's arrays
@@ -1961,7 +1963,7 @@ struct GamesCall {
   const gn_game *games;
   size_t n_games;
   int mode, with_children, n_lines;
-  bool history; // gn_evaluate_games_lines_history: the lines with the game-history draws
+  bool history; // gn_evaluate_games_lines_history / _lines2_history: the lines with the game-history draws
   uint32_t *position_offsets, *child_offsets;
   int32_t *game_status;
   gn_eval *position_out;
@@ -1969,6 +1971,7 @@ struct GamesCall {
   uint16_t *child_moves;
   gn_child *child_out;
   gn_line *lines;
+  gn_line2 *lines2;              // gn_evaluate_games_lines2: two-ply lines instead (lines NULL, no children)
   std::vector<GamePrep> prep;
   std::vector<size_t> bounds;    // the devices' game ranges
   std::vector<GameShard> shards; // one per device
@@ -2072,7 +2075,7 @@ static int games_offsets(GamesCall &c) {
   if (c.total > c.position_cap)
     return fail(GN_E_CAPACITY, "%zu positions exceed capacity %zu", (size_t)c.total, c.position_cap);
   if (c.total && !c.position_out) return fail(GN_E_INVALID, "position_out is NULL");
-  if (c.total && c.n_lines && !c.lines) return fail(GN_E_INVALID, "lines is NULL");
+  if (c.total && c.n_lines && !c.lines && !c.lines2) return fail(GN_E_INVALID, "lines is NULL");
   return GN_OK;
 }
 
@@ -2116,9 +2119,9 @@ static void games_layout(const GamesCall &c, GameShard &sh) {
   sh.m = sh.src.size();
 }
 
-// phase B: (gathered) the evaluated positions gathered into contiguous parents; evaluated (no
-// children) or counted (pass 1 of the expansion)
-static int games_evaluate_or_count(const GamesCall &c, GameShard &sh, Dev &d) {
+// phase B's front: (gathered) the evaluated positions gathered into contiguous parents; (history)
+// their gn_history entries uploaded
+static int games_gather(const GamesCall &c, GameShard &sh, Dev &d) {
   const size_t m = sh.m;
   hipStream_t s = d.stream;
   if (!sh.in_place) {
@@ -2130,7 +2133,8 @@ static int games_evaluate_or_count(const GamesCall &c, GameShard &sh, Dev &d) {
     HIP_TRY(hipStreamSynchronize(s));
     d.t_upload += ms_since(t0);
     sh.res.resize(m);
-    sh.lres.resize(m * (size_t)c.n_lines);
+    if (c.lines2) sh.l2res.resize(m * (size_t)c.n_lines);
+    else sh.lres.resize(m * (size_t)c.n_lines);
   }
   if (c.history) { // one gn_history per evaluated position, uploaded once per shard
     const auto t0 = Clock::now();
@@ -2139,6 +2143,15 @@ static int games_evaluate_or_count(const GamesCall &c, GameShard &sh, Dev &d) {
     HIP_TRY(hipStreamSynchronize(s));
     d.t_upload += ms_since(t0);
   }
+  return GN_OK;
+}
+
+// phase B: the gather; then evaluated (no children) or counted (pass 1 of the expansion)
+static int games_evaluate_or_count(const GamesCall &c, GameShard &sh, Dev &d) {
+  const int rc = games_gather(c, sh, d);
+  if (rc) return rc;
+  const size_t m = sh.m;
+  hipStream_t s = d.stream;
   if (c.with_children) return count_shard(d, sh.parents_of(d), m, sh.off);
   const auto t1 = Clock::now();
   HIP_TRY(d.io_out.ensure(m));
@@ -2196,22 +2209,33 @@ static int games_expand(const GamesCall &c, GameShard &sh, Dev &d) {
                           chunk_plan(sh.m, sh.starts, c.ctx->chunk_parents), o);
 }
 
-// host: the gathered shards' records and lines to their places in the caller's arrays; the
-// skipped positions' lines are empty
-static void games_scatter(const GamesCall &c) {
+// host: the gathered shards' lines (the shard's vector `res`) to their places in the caller's
+// array; the skipped positions' lines are `empty`
+template <class Line>
+static void games_scatter_lines(const GamesCall &c, Line *lines, std::vector<Line> GameShard::*res, const Line &empty) {
   const size_t K = (size_t)c.n_lines;
-  for (const GameShard &sh : c.shards)
-    for (size_t e = 0; e < sh.where.size(); ++e) c.position_out[sh.where[e]] = sh.res[e];
-  if (!K) return;
   if (!c.all_in_place)
     for (size_t g = 0; g < c.n_games; ++g)
       for (size_t at = c.position_offsets[g]; at < c.position_offsets[g + 1]; ++at)
         if (c.position_out[at].flags & GN_FLAG_SKIPPED)
-          for (size_t j = 0; j < K; ++j) c.lines[at * K + j] = gn_line{0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE};
+          for (size_t j = 0; j < K; ++j) lines[at * K + j] = empty;
   for (const GameShard &sh : c.shards)
     for (size_t e = 0; e < sh.where.size(); ++e)
-      std::copy(sh.lres.begin() + e * K, sh.lres.begin() + (e + 1) * K, c.lines + (size_t)sh.where[e] * K);
+      std::copy((sh.*res).begin() + e * K, (sh.*res).begin() + (e + 1) * K, lines + (size_t)sh.where[e] * K);
 }
+
+// host: the gathered shards' records and lines to their places in the caller's arrays
+static void games_scatter(const GamesCall &c) {
+  for (const GameShard &sh : c.shards)
+    for (size_t e = 0; e < sh.where.size(); ++e) c.position_out[sh.where[e]] = sh.res[e];
+  if (!c.n_lines) return;
+  if (c.lines2) games_scatter_lines(c, c.lines2, &GameShard::l2res, gn_line2{0, 0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE, 0});
+  else games_scatter_lines(c, c.lines, &GameShard::lres, gn_line{0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE});
+}
+
+// phase B of gn_evaluate_games_lines2: the gather, then the two-ply lines' chunk loop (below, with
+// gn_evaluate_lines2)
+static int games_lines2(const GamesCall &c, GameShard &sh, Dev &d);
 
 static int evaluate_games(GamesCall c) {
   if (!slot(c.ctx, 0)) return fail(GN_E_INVALID, "bad context");
@@ -2230,7 +2254,9 @@ static int evaluate_games(GamesCall c) {
     if (rc || (rc = games_offsets(c)) != GN_OK) return rc;
     for (GameShard &sh : c.shards) games_layout(c, sh), c.all_in_place = c.all_in_place && sh.in_place;
     auto has = [&](size_t k) { return c.shards[k].has(); };
-    rc = run_devices(ctx, has, [&](size_t k, Dev &d) -> int { return games_evaluate_or_count(c, c.shards[k], d); });
+    rc = run_devices(ctx, has, [&](size_t k, Dev &d) -> int {
+      return c.lines2 ? games_lines2(c, c.shards[k], d) : games_evaluate_or_count(c, c.shards[k], d);
+    });
     if (rc) return rc;
     if (c.with_children) {
       if ((rc = games_child_offsets(c)) != GN_OK) return rc;
@@ -2284,6 +2310,28 @@ int gn_evaluate_games_lines_history(gn_ctx *ctx, const gn_game *games, size_t n_
   if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
   return evaluate_games({ctx, games, n_games, mode, 1, n_lines, true, position_offsets, nullptr, game_status,
                          position_out, position_cap, 0, nullptr, nullptr, lines});
+}
+
+static int evaluate_games_lines2(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines, bool history,
+                                 uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
+                                 size_t position_cap, gn_line2 *lines) {
+  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  return evaluate_games({ctx, games, n_games, mode, 0, n_lines, history, position_offsets, nullptr, game_status,
+                         position_out, position_cap, 0, nullptr, nullptr, nullptr, lines});
+}
+
+int gn_evaluate_games_lines2(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                             uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
+                             size_t position_cap, gn_line2 *lines) {
+  return evaluate_games_lines2(ctx, games, n_games, mode, n_lines, false, position_offsets, game_status, position_out,
+                               position_cap, lines);
+}
+
+int gn_evaluate_games_lines2_history(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                     uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
+                                     size_t position_cap, gn_line2 *lines) {
+  return evaluate_games_lines2(ctx, games, n_games, mode, n_lines, true, position_offsets, game_status, position_out,
+                               position_cap, lines);
 }
 
 int gn_partition(const uint32_t *weights, size_t n_items, int n_shards, size_t *bounds) {
@@ -2877,6 +2925,24 @@ int gn_rank_lines2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parent
   return GN_OK;
 }
 
+int gn_rank_lines2_history_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                  const uint32_t *d_offsets, const gn_board *d_children, const gn_eval *d_child_out,
+                                  const uint16_t *d_moves, const uint32_t *d_goffsets, const uint16_t *d_gmoves,
+                                  const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
+                                  const gn_history *d_hist, int n_lines, gn_line2 *d_lines, void *stream) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
+  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  if (n && (!d_parents || !d_offsets || !d_lines || !d_hist)) return fail(GN_E_INVALID, "NULL buffer");
+  if (n_keys && !d_keys) return fail(GN_E_INVALID, "d_keys is NULL");
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_rank_lines2_history(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves,
+                                     d_grand_out, ctx->P, d->tables, n_lines, d_lines,
+                                     RankHistory{d_keys, n_keys, d_hist}, call.s));
+  return GN_OK;
+}
+
 int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, int mode, int iters,
                           float *ms_total, size_t *total, float *stage_ms, uint64_t *ft_rows, gn_eval *d_parent_out,
                           uint32_t *d_offsets, uint16_t *d_moves, gn_eval *d_child_out, size_t cap) {
@@ -3156,64 +3222,90 @@ int gn_expand_and_evaluate(gn_ctx *ctx, const char *const *parent_fens, size_t n
   });
 }
 
-// Two-ply ranked lines from host boards (gn_evaluate_lines2): each device's shard in chunks of
-// chunk parents; per chunk the depth-2 expansion into the device's Lines2 buffers (expand2_on),
-// rank_lines2_kernel, and one download of the chunk's parent records and lines.
+// A shard's two-ply lines (gn_evaluate_lines2, gn_evaluate_games_lines2): its m device-resident
+// parents in chunks of chunk parents; per chunk the depth-2 expansion into the device's Lines2
+// buffers (expand2_on), rank_lines2_kernel -- its history variant when history names the shard's
+// keys and its parents' gn_history entries -- and one download of the chunk's parent records and
+// lines into out / lines (the shard's first parent's).  The chunks need no cut at game starts: the
+// keys are the whole shard's.
+static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m, int mode, int K, gn_eval *out,
+                         gn_line2 *lines, const RankHistory *history) {
+  hipStream_t s = d.stream;
+  Dev::Lines2 &x = d.l2;
+  // 1,024 parents are ~1 M grandchildren: a few hundred MB of records, boards and partial sums
+  const size_t chunk = ctx->chunk_parents > 0 ? (size_t)ctx->chunk_parents : 1024;
+  const std::function<int(size_t, size_t, Expand2Grand &)> size_grand = [&](size_t t, size_t g, Expand2Grand &gr) -> int {
+    HIP_TRY(x.goff.ensure(t + 1));
+    HIP_TRY(x.gmv.ensure(std::max<size_t>(g, 1)));
+    HIP_TRY(x.gco.ensure(std::max<size_t>(g, 1)));
+    gr = Expand2Grand{x.goff.p, x.gmv.p, x.gco.p, std::max<size_t>(g, 1)};
+    return GN_OK;
+  };
+  for (size_t a = 0; a < m; a += chunk) {
+    const size_t mp = std::min(chunk, m - a);
+    const gn_board *par = parents + a;
+    auto t0 = Clock::now();
+    size_t t = 0, g = 0;
+    HIP_TRY(count_children(d, par, mp, s, &t));
+    const size_t cap = std::max<size_t>(t, 1);
+    HIP_TRY(x.po.ensure(mp));
+    HIP_TRY(x.off.ensure(mp + 1));
+    HIP_TRY(x.ch.ensure(cap));
+    HIP_TRY(x.mv.ensure(cap));
+    HIP_TRY(x.co.ensure(cap));
+    HIP_TRY(x.ln.ensure(mp * (size_t)K));
+    int rc = expand2_on(ctx, &d, par, mp, mode, x.po.p, x.off.p, x.ch.p, x.mv.p, x.co.p, cap, Expand2Grand{}, &t, &g, s,
+                        &size_grand);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(d.rev[0], s));
+    if (history)
+      HIP_TRY(launch_rank_lines2_history(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P,
+                                         d.tables, K, x.ln.p, RankHistory{history->keys, history->n_keys, history->hist + a},
+                                         s));
+    else
+      HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables, K,
+                                 x.ln.p, s));
+    HIP_TRY(hipEventRecord(d.rev[1], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, d.rev[0], d.rev[1]));
+    d.t_rank2 += ms;
+    d.t_compute += ms_since(t0), t0 = Clock::now();
+    HIP_TRY(hipMemcpyAsync(out + a, x.po.p, mp * sizeof(gn_eval), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(lines + a * (size_t)K, x.ln.p, mp * (size_t)K * sizeof(gn_line2), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    d.t_download += ms_since(t0);
+  }
+  return GN_OK;
+}
+
+// gn_evaluate_lines2: the boards sharded equally over the devices, each shard uploaded and run
+// through lines2_chunks
 static int lines2_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int mode, int K, gn_eval *out,
                               gn_line2 *lines) {
   const size_t nd = ctx->devs.size();
   std::vector<size_t> b(nd + 1);
   partition(nullptr, n, (int)nd, b.data());
   const auto locks = lock_devices(ctx);
-  // 1,024 parents are ~1 M grandchildren: a few hundred MB of records, boards and partial sums
-  const size_t chunk = ctx->chunk_parents > 0 ? (size_t)ctx->chunk_parents : 1024;
   return run_shards(ctx, b, [&](size_t, Dev &d, size_t lo, size_t hi) -> int {
-    hipStream_t s = d.stream;
-    Dev::Lines2 &x = d.l2;
-    auto t0 = Clock::now();
+    const auto t0 = Clock::now();
     HIP_TRY(d.par.ensure(hi - lo));
-    HIP_TRY(hipMemcpyAsync(d.par.p, boards + lo, (hi - lo) * sizeof(gn_board), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(d.par.p, boards + lo, (hi - lo) * sizeof(gn_board), hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
     d.t_upload += ms_since(t0);
-    const std::function<int(size_t, size_t, Expand2Grand &)> size_grand = [&](size_t t, size_t g, Expand2Grand &gr) -> int {
-      HIP_TRY(x.goff.ensure(t + 1));
-      HIP_TRY(x.gmv.ensure(std::max<size_t>(g, 1)));
-      HIP_TRY(x.gco.ensure(std::max<size_t>(g, 1)));
-      gr = Expand2Grand{x.goff.p, x.gmv.p, x.gco.p, std::max<size_t>(g, 1)};
-      return GN_OK;
-    };
-    for (size_t a = lo; a < hi; a += chunk) {
-      const size_t mp = std::min(chunk, hi - a);
-      const gn_board *par = d.par.p + (a - lo);
-      t0 = Clock::now();
-      size_t t = 0, g = 0;
-      HIP_TRY(count_children(d, par, mp, s, &t));
-      const size_t cap = std::max<size_t>(t, 1);
-      HIP_TRY(x.po.ensure(mp));
-      HIP_TRY(x.off.ensure(mp + 1));
-      HIP_TRY(x.ch.ensure(cap));
-      HIP_TRY(x.mv.ensure(cap));
-      HIP_TRY(x.co.ensure(cap));
-      HIP_TRY(x.ln.ensure(mp * (size_t)K));
-      int rc = expand2_on(ctx, &d, par, mp, mode, x.po.p, x.off.p, x.ch.p, x.mv.p, x.co.p, cap, Expand2Grand{}, &t, &g, s,
-                          &size_grand);
-      if (rc) return rc;
-      HIP_TRY(hipEventRecord(d.rev[0], s));
-      HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables, K,
-                                 x.ln.p, s));
-      HIP_TRY(hipEventRecord(d.rev[1], s));
-      HIP_TRY(hipStreamSynchronize(s));
-      float ms = 0;
-      HIP_TRY(hipEventElapsedTime(&ms, d.rev[0], d.rev[1]));
-      d.t_rank2 += ms;
-      d.t_compute += ms_since(t0), t0 = Clock::now();
-      HIP_TRY(hipMemcpyAsync(out + a, x.po.p, mp * sizeof(gn_eval), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipMemcpyAsync(lines + a * (size_t)K, x.ln.p, mp * (size_t)K * sizeof(gn_line2), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      d.t_download += ms_since(t0);
-    }
-    return GN_OK;
+    return lines2_chunks(ctx, d, d.par.p, hi - lo, mode, K, out + lo, lines + lo * (size_t)K, nullptr);
   });
+}
+
+// (declared with the games phases above) the shard's lines go into the caller's arrays when it is
+// in place, or into its vectors to be scattered
+static int games_lines2(const GamesCall &c, GameShard &sh, Dev &d) {
+  const int rc = games_gather(c, sh, d);
+  if (rc) return rc;
+  const RankHistory h{d.rkeys.p, d.n_rkeys, d.hist.p};
+  gn_line2 *const ln = sh.in_place ? c.lines2 + sh.p0 * (size_t)c.n_lines : sh.l2res.data();
+  return lines2_chunks(c.ctx, d, sh.parents_of(d), sh.m, c.mode, c.n_lines, sh.records_of(c.position_out), ln,
+                       c.history ? &h : nullptr);
 }
 
 int gn_evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,

@@ -287,6 +287,13 @@ hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t 
                               const gn_eval *rec, const uint16_t *moves, const uint32_t *goffsets,
                               const uint16_t *gmoves, const gn_eval *grec, const gn_eval_params &P,
                               const Tables *tables, int K, gn_line2 *lines, hipStream_t s);
+// ... with the game-history draws at both levels (include/gpu_nnue.h at gn_line2 and gn_history;
+// rank_lines2_kernel with a RankHistory): hist[i] names parent i's game so far, as above
+hipError_t launch_rank_lines2_history(const gn_board *parents, size_t n, const uint32_t *offsets,
+                                      const gn_board *children, const gn_eval *rec, const uint16_t *moves,
+                                      const uint32_t *goffsets, const uint16_t *gmoves, const gn_eval *grec,
+                                      const gn_eval_params &P, const Tables *tables, int K, gn_line2 *lines,
+                                      const RankHistory &history, hipStream_t s);
 // narrowing copy of offsets for the C-ABI
 hipError_t launch_offsets_u32(const uint64_t *in, size_t n, uint32_t *out, hipStream_t s);
 // exclusive scan of n + 1 counts (counts[n] must be 0); temp grows on demand

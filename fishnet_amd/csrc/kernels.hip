@@ -1064,6 +1064,12 @@ __device__ __forceinline__ uint64_t group_max_w(uint64_t v) {
   return v;
 }
 __device__ __forceinline__ uint64_t group_max(uint64_t v) { return group_max_w<GN_RANK_WIDTH>(v); }
+template <int W>
+__device__ __forceinline__ uint32_t group_sum_w(uint32_t v) {
+#pragma unroll
+  for (int o = W / 2; o; o >>= 1) v += __shfl_xor(v, o, W);
+  return v;
+}
 
 // K rounds of the cross-lane maximum over the lanes' keys and the running top K (lane k's `top`):
 // the new top K, round k's winner to lane k, the winner retiring.  Keys are distinct or 0.
@@ -1277,13 +1283,35 @@ hipError_t launch_position_keys(const gn_board *boards, size_t n, bool gate, con
 // are uniform in the workgroup (both barriers are reached by every lane or by none); the loop
 // over a child's grandchildren runs until no lane of the wave has one left (__any), so both
 // groups of a wave reach every shuffle together.
-template <class Parent, class Off>
+//
+// History variant (HIST; include/gpu_nnue.h at gn_line2 and gn_history), chosen like
+// rank_children_kernel's by an optional trailing RankHistory, so the plain instantiation keeps its
+// arguments and its code.  The parent's gn_history entry is read once per parent.  A child with a
+// grandchild is tested by its group, which holds nothing else: lane j tests the keys at
+// self + 1 - d for d = 4 + 2j (+ 64 ...) <= min(C.rule50, self - first + 1), and a sum over the
+// group counts the matches, so the outcome is uniform in the group and the sum's shuffles are
+// reached by every lane of the wave, drawn or not, child or none.  A drawn child's grandchildren
+// are not consulted: its group's loop bound becomes g0, like a child without any, and the __any
+// still keeps the wave's other group company.  A grandchild G that has a legal move is tested by
+// its lane, where any_legal sits and no shuffle does: G.rule50 >= 100, or two matches among
+// self + 2 - d for d = 4, 6, ... <= min(G.rule50, self - first + 2), four independent loads per
+// trip as in rank_children_kernel.  (The child has the other side to move and can never equal G;
+// d = 2 would be the parent, which two plies cannot restore.)  No history (first > self or
+// self >= n_keys) leaves only the fifty-move part at both levels, and keys is never indexed at or
+// beyond n_keys.  The draw bit rides in the reply key below the reply, (V + 32768) << 17 |
+// (0xFFFF - reply) << 1 | draw, and in the child key below the other two flag bits, the other
+// fields one bit higher: (value + 32768) << 35 | (0xFFFF - move) << 19 | reply << 3 |
+// no-moves << 2 | in-check << 1 | draw.  A drawn child has reply 0: plies is reply ? 2 : 1.
+template <class Parent, class Off, class... History>
 __global__ void __launch_bounds__(RANK_WG)
     rank_lines2_kernel(const Parent *__restrict__ parents, size_t n, const Off *__restrict__ offsets,
                        const gn_board *__restrict__ children, const gn_eval *__restrict__ rec,
                        const uint16_t *__restrict__ moves, const Off *__restrict__ goffsets,
                        const uint16_t *__restrict__ gmoves, const gn_eval *__restrict__ grec, gn_eval_params P,
-                       const Tables *__restrict__ tables, int K, gn_line2 *__restrict__ lines) {
+                       const Tables *__restrict__ tables, int K, gn_line2 *__restrict__ lines, History... history) {
+  static_assert(sizeof...(History) <= 1, "nothing, or one RankHistory");
+  constexpr bool HIST = sizeof...(History) != 0;
+  constexpr int FB = HIST ? 3 : 2; // flag bits below the reply
   __shared__ Tables T;
   __shared__ uint64_t merge[RANK_WG / 32 * GN_MAX_LINES]; // each group's top 8
   load_tables(T, tables);
@@ -1296,6 +1324,12 @@ __global__ void __launch_bounds__(RANK_WG)
       continue;
     }
     uint64_t top = 0; // lane k: this group's k-th best child key so far (0: none)
+    uint32_t hself = 0, hlen = 0; // HIST: the parent's key index, and its game's positions so far (0: no history)
+    if constexpr (HIST) {
+      const gn_history h = (history.hist, ...)[p];
+      hself = h.self;
+      hlen = (h.first <= h.self && (size_t)h.self < (history.n_keys, ...)) ? h.self - h.first + 1 : 0u;
+    }
     for (uint64_t cb = c0; cb < c1; cb += GROUPS) {
       const uint64_t c = cb + q;
       const bool have = c < c1;
@@ -1308,27 +1342,88 @@ __global__ void __launch_bounds__(RANK_WG)
       }
       const uint32_t none = g0 == g1 ? 1u : 0u;
       uint64_t best = 0; // the lane's best reply key
-      if (__any(g0 < g1)) {
+      uint64_t key = 0;
+      if constexpr (HIST) {
         Board C;
-        if (!none) unpack_fields(children[c], C);
-        for (uint64_t g = g0; __any(g < g1); g += W) {
-          if (g + lane < g1) {
+        uint32_t seen = 0; // the lane's share of the child's earlier occurrences
+        if (!none) {
+          unpack_fields(children[c], C);
+          const uint32_t lim = C.rule50 < hlen ? (uint32_t)C.rule50 : hlen;
+          if (C.rule50 >= 100) {
+            seen = 2;
+          } else if (lim >= 4) {
+            const uint64_t ck = position_key(C);
+            const uint64_t *const at = (history.keys, ...) + ((size_t)hself + 1);
+            for (uint32_t d = 4 + 2 * (uint32_t)lane; d <= lim; d += 2 * W) seen += *(at - d) == ck ? 1u : 0u;
+          }
+        }
+        const uint32_t cdraw = group_sum_w<W>(seen) >= 2 ? 1u : 0u;
+        const uint64_t ge = cdraw ? g0 : g1; // a drawn child's replies are not consulted
+        const uint32_t glen = hlen ? hlen + 1 : 0u;
+        for (uint64_t g = g0; __any(g < ge); g += W) {
+          if (g + lane < ge) {
             const uint32_t gm = gmoves[g + lane];
             const gn_eval r = grec[g + lane];
             const Board G = do_move(C, (uint16_t)gm, nullptr);
-            const int32_t v1 = any_legal(G, T) ? r.final_v : (r.flags & GN_FLAG_IN_CHECK) ? -VALUE_MATE : 0;
-            const uint64_t k = (uint64_t)(uint32_t)(negate_ply(v1) + 32768) << 16 | (0xFFFFu - gm);
+            int32_t v1 = (r.flags & GN_FLAG_IN_CHECK) ? -VALUE_MATE : 0;
+            uint32_t draw = 0;
+            if (any_legal(G, T)) {
+              const uint32_t lim = G.rule50 < glen ? (uint32_t)G.rule50 : glen;
+              if (G.rule50 >= 100) {
+                draw = 1;
+              } else if (lim >= 4) {
+                const uint64_t gk = position_key(G);
+                uint32_t n2 = 0;
+                // four keys per trip, their loads independent of each other (a trip's tail re-reads
+                // d = 4, which lim >= 4 makes valid, and ignores it); the walk ends between trips
+                const uint64_t *const at = (history.keys, ...) + ((size_t)hself + 2);
+                for (uint32_t d = 4; d <= lim && n2 < 2; d += 8) {
+#pragma unroll
+                  for (uint32_t j = 0; j < 8; j += 2) {
+                    const bool in = d + j <= lim;
+                    const uint64_t k = *(at - (in ? d + j : 4u));
+                    n2 += in && k == gk ? 1u : 0u;
+                  }
+                }
+                draw = n2 >= 2 ? 1u : 0u;
+              }
+              v1 = draw ? 0 : r.final_v;
+            }
+            const uint64_t k = (uint64_t)(uint32_t)(negate_ply(v1) + 32768) << 17 | (uint64_t)(0xFFFFu - gm) << 1 | draw;
             best = k > best ? k : best;
           }
         }
-      }
-      best = group_max_w<W>(best);
-      uint64_t key = 0;
-      if (have) {
-        const int32_t R = none ? (check ? -VALUE_MATE : 0) : (int32_t)(best >> 16) - 32768;
-        const uint32_t reply = none ? 0u : 0xFFFFu - (uint32_t)(best & 0xFFFFu);
-        key = (uint64_t)(uint32_t)(negate_ply(R) + 32768) << 34 | (uint64_t)(0xFFFFu - mv) << 18 |
-              (uint64_t)reply << 2 | none << 1 | check;
+        best = group_max_w<W>(best);
+        if (have) {
+          const bool leaf = none || cdraw; // the line ends at the child
+          const int32_t R = none ? (check ? -VALUE_MATE : 0) : cdraw ? 0 : (int32_t)(best >> 17) - 32768;
+          const uint32_t reply = leaf ? 0u : 0xFFFFu - (uint32_t)((best >> 1) & 0xFFFFu);
+          const uint32_t draw = none ? 0u : cdraw ? 1u : (uint32_t)(best & 1);
+          key = (uint64_t)(uint32_t)(negate_ply(R) + 32768) << 35 | (uint64_t)(0xFFFFu - mv) << 19 |
+                (uint64_t)reply << 3 | none << 2 | check << 1 | draw;
+        }
+      } else {
+        if (__any(g0 < g1)) {
+          Board C;
+          if (!none) unpack_fields(children[c], C);
+          for (uint64_t g = g0; __any(g < g1); g += W) {
+            if (g + lane < g1) {
+              const uint32_t gm = gmoves[g + lane];
+              const gn_eval r = grec[g + lane];
+              const Board G = do_move(C, (uint16_t)gm, nullptr);
+              const int32_t v1 = any_legal(G, T) ? r.final_v : (r.flags & GN_FLAG_IN_CHECK) ? -VALUE_MATE : 0;
+              const uint64_t k = (uint64_t)(uint32_t)(negate_ply(v1) + 32768) << 16 | (0xFFFFu - gm);
+              best = k > best ? k : best;
+            }
+          }
+        }
+        best = group_max_w<W>(best);
+        if (have) {
+          const int32_t R = none ? (check ? -VALUE_MATE : 0) : (int32_t)(best >> 16) - 32768;
+          const uint32_t reply = none ? 0u : 0xFFFFu - (uint32_t)(best & 0xFFFFu);
+          key = (uint64_t)(uint32_t)(negate_ply(R) + 32768) << 34 | (uint64_t)(0xFFFFu - mv) << 18 |
+                (uint64_t)reply << 2 | none << 1 | check;
+        }
       }
       // sorted insert: lane k takes the key if it beats top[k] but not top[k - 1], the neighbour's
       // old value if it beats both
@@ -1345,13 +1440,18 @@ __global__ void __launch_bounds__(RANK_WG)
         rank_parent(parents[p], B, T); // (it has children: it passed the gate)
         gn_line2 l = {0, 0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE, 0};
         if (t2) {
-          uint32_t fl = ((t2 & 1) ? GN_FLAG_IN_CHECK : 0u) | ((t2 & 2) ? GN_FLAG_NO_MOVES : 0u);
-          l.value = (int32_t)(t2 >> 34) - 32768;
-          l.move = (uint16_t)(0xFFFFu - (uint32_t)((t2 >> 18) & 0xFFFFu));
-          l.reply = (uint16_t)((t2 >> 2) & 0xFFFFu);
+          uint32_t fl;
+          if constexpr (HIST)
+            fl = ((t2 & 2) ? GN_FLAG_IN_CHECK : 0u) | ((t2 & 4) ? GN_FLAG_NO_MOVES : 0u) | ((t2 & 1) ? GN_FLAG_DRAW : 0u);
+          else
+            fl = ((t2 & 1) ? GN_FLAG_IN_CHECK : 0u) | ((t2 & 2) ? GN_FLAG_NO_MOVES : 0u);
+          l.value = (int32_t)(t2 >> (32 + FB)) - 32768;
+          l.move = (uint16_t)(0xFFFFu - (uint32_t)((t2 >> (16 + FB)) & 0xFFFFu));
+          l.reply = (uint16_t)((t2 >> FB) & 0xFFFFu);
           l.score = rule_score(l.value, wdl_material(B, P), P, fl);
           l.flags = (uint16_t)fl;
-          l.plies = (t2 & 2) ? 1 : 2;
+          if constexpr (HIST) l.plies = l.reply ? 2 : 1;
+          else l.plies = (t2 & 2) ? 1 : 2;
         }
         lines[p * (size_t)K + threadIdx.x] = l;
       }
@@ -1360,15 +1460,20 @@ __global__ void __launch_bounds__(RANK_WG)
   }
 }
 
+// (history: keys / n_keys / hist of the history variant, or nullptr: the plain kernel)
 template <class Parent, class Off>
 static hipError_t rank_lines2_t(const Parent *parents, size_t n, const Off *offsets, const gn_board *children,
                                 const gn_eval *rec, const uint16_t *moves, const Off *goffsets, const uint16_t *gmoves,
                                 const gn_eval *grec, const gn_eval_params &P, const Tables *tables, int K,
-                                gn_line2 *lines, hipStream_t s) {
+                                gn_line2 *lines, hipStream_t s, const RankHistory *history = nullptr) {
   if (!n) return hipSuccess;
   const size_t blocks = std::min<size_t>(n, 8192);
-  hipLaunchKernelGGL((rank_lines2_kernel<Parent, Off>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets, children,
-                     rec, moves, goffsets, gmoves, grec, P, tables, K, lines);
+  if (history)
+    hipLaunchKernelGGL((rank_lines2_kernel<Parent, Off, RankHistory>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n,
+                       offsets, children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines, *history);
+  else
+    hipLaunchKernelGGL((rank_lines2_kernel<Parent, Off>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets,
+                       children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines);
   return hipGetLastError();
 }
 hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t *offsets, const gn_board *children,
@@ -1376,6 +1481,14 @@ hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t 
                               const uint16_t *gmoves, const gn_eval *grec, const gn_eval_params &P,
                               const Tables *tables, int K, gn_line2 *lines, hipStream_t s) {
   return rank_lines2_t(parents, n, offsets, children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines, s);
+}
+hipError_t launch_rank_lines2_history(const gn_board *parents, size_t n, const uint32_t *offsets,
+                                      const gn_board *children, const gn_eval *rec, const uint16_t *moves,
+                                      const uint32_t *goffsets, const uint16_t *gmoves, const gn_eval *grec,
+                                      const gn_eval_params &P, const Tables *tables, int K, gn_line2 *lines,
+                                      const RankHistory &history, hipStream_t s) {
+  return rank_lines2_t(parents, n, offsets, children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines, s,
+                       &history);
 }
 
 hipError_t launch_classify(const gn_board *boards, size_t n, const gn_eval_params &P, uint8_t *need_small,

@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("GPU_NNUE_LIB", os.path.join(HERE, "lib", "libgpu_nnue
 MODE_FULL, MODE_BIG, MODE_SMALL = 0, 1, 2
 FLAG_IN_CHECK, FLAG_SMALLNET, FLAG_BAD_FEN, FLAG_REEVAL, FLAG_SKIPPED = 1, 2, 4, 8, 16
 FLAG_MATE, FLAG_NO_SCORE, FLAG_SEARCHED, FLAG_NO_MOVES = 32, 64, 128, 256
-FLAG_DRAW = 512  # gn_line.flags of the history calls only: drawn by rule (gpu_nnue.h at gn_history)
+FLAG_DRAW = 512  # gn_line.flags / gn_line2.flags of the history calls only: drawn by rule (gpu_nnue.h at gn_history)
 ERRORS = {-1: "INVALID", -2: "IO", -3: "FORMAT", -4: "HIP", -5: "NOMEM", -6: "CAPACITY",
           -7: "NODEVICE", -8: "NONET", -9: "ILLEGAL_MOVE"}
 E_INVALID, E_IO, E_FORMAT, E_HIP, E_NOMEM, E_CAPACITY, E_NODEVICE, E_NONET, E_ILLEGAL_MOVE = -1, -2, -3, -4, -5, -6, -7, -8, -9
@@ -60,7 +60,8 @@ EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_
            "gn_boards_to_fens", "gn_load_net_archive", "gn_archive_read", "gn_expand2_device",
            "gn_random_games_uci", "gn_rank_children_device", "gn_evaluate_games_lines",
            "gn_rank_lines2_device", "gn_evaluate_lines2", "gn_position_keys", "gn_position_keys_device",
-           "gn_rank_children_history_device", "gn_evaluate_games_lines_history"]
+           "gn_rank_children_history_device", "gn_evaluate_games_lines_history",
+           "gn_rank_lines2_history_device", "gn_evaluate_games_lines2", "gn_evaluate_games_lines2_history"]
 OPT_INCREMENTAL_CHILDREN, OPT_XCD_SWIZZLE, OPT_KING_SORT, OPT_CHAIN, OPT_KING_CACHE = 1, 2, 3, 4, 5
 OPT_CHUNK_PARENTS, OPT_COALESCE, OPT_STREAM_SLICES, OPT_FAST_BATCH, OPT_EXPAND_PIPELINE = 6, 7, 8, 9, 10
 STAT_PLAN_NS, STAT_STREAM_NS, STAT_SCRATCH_PADS, STAT_FINISH_NS = 101, 102, 103, 104
@@ -188,6 +189,9 @@ def lib():
         "gn_position_keys_device": [vp, i32, vp, sz, vp, vp],
         "gn_rank_children_history_device": [vp, i32, vp, sz, vp, vp, vp, vp, sz, vp, i32, vp, vp],
         "gn_evaluate_games_lines_history": [vp, vp, sz, i32, i32, vp, vp, vp, sz, vp],
+        "gn_rank_lines2_history_device": [vp, i32, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, i32, vp, vp],
+        "gn_evaluate_games_lines2": [vp, vp, sz, i32, i32, vp, vp, vp, sz, vp],
+        "gn_evaluate_games_lines2_history": [vp, vp, sz, i32, i32, vp, vp, vp, sz, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -500,6 +504,20 @@ class GpuNnue:
         capacity (None: sized by a first call, as the C caller's GN_E_CAPACITY retry).  history:
         gn_evaluate_games_lines_history (draws by repetition and the fifty-move rule, FLAG_DRAW)."""
         call = lib().gn_evaluate_games_lines_history if history else lib().gn_evaluate_games_lines
+        return self._games_lines(call, LINE_DTYPE, games, n_lines, mode, cap)
+
+    def evaluate_games_lines2(self, games, n_lines, mode=MODE_FULL, cap=None, history=False):
+        """gn_evaluate_games_lines2: evaluate_games_lines with two-ply lines (LINE2_DTYPE: move, best
+        reply, minimax value).  history: gn_evaluate_games_lines2_history (draws by repetition and
+        the fifty-move rule at the child and at the reply, FLAG_DRAW; plies tells them apart)."""
+        call = lib().gn_evaluate_games_lines2_history if history else lib().gn_evaluate_games_lines2
+        return self._games_lines(call, LINE2_DTYPE, games, n_lines, mode, cap)
+
+    def evaluate_games_lines2_history(self, games, n_lines, mode=MODE_FULL, cap=None):
+        """gn_evaluate_games_lines2_history: evaluate_games_lines2 with each game's history."""
+        return self.evaluate_games_lines2(games, n_lines, mode, cap, history=True)
+
+    def _games_lines(self, call, line_dtype, games, n_lines, mode, cap):
         ng = len(games)
         arr, _keep = _games_array(games)
         offs = np.zeros(ng + 1, dtype=np.uint32)
@@ -507,7 +525,7 @@ class GpuNnue:
         pcap = 0 if cap is None else cap
         for _ in range(2):
             pos = np.zeros(max(pcap, 1), dtype=EVAL_DTYPE)
-            lines = np.zeros((max(pcap, 1), max(n_lines, 1)), dtype=LINE_DTYPE)
+            lines = np.zeros((max(pcap, 1), max(n_lines, 1)), dtype=line_dtype)
             rc = call(self.h, arr, ng, mode, n_lines, offs.ctypes.data, status.ctypes.data, pos.ctypes.data, pcap,
                       lines.ctypes.data)
             if rc == E_CAPACITY and cap is None and int(offs[-1]) > pcap:
@@ -627,6 +645,15 @@ class GpuNnue:
         p = lambda k: out[k].ptr if out.get(k) is not None else None
         _check(lib().gn_rank_lines2_device(self.h, slot, d_parents.ptr, n, p("off"), p("ch"), p("co"), p("mv"),
                                            p("goff"), p("gmv"), p("gco"), n_lines, d_lines.ptr, stream))
+
+    def rank_lines2_history_device(self, d_parents, n, out, d_keys, n_keys, d_hist, n_lines, d_lines, stream=None,
+                                   slot=0):
+        """gn_rank_lines2_history_device: rank_lines2_device with the game-history draws; d_hist[n]
+        (HISTORY_DTYPE) names each parent's game so far in d_keys[n_keys].  Asynchronous."""
+        p = lambda k: out[k].ptr if out.get(k) is not None else None
+        _check(lib().gn_rank_lines2_history_device(self.h, slot, d_parents.ptr, n, p("off"), p("ch"), p("co"), p("mv"),
+                                                   p("goff"), p("gmv"), p("gco"), d_keys.ptr if d_keys else None,
+                                                   n_keys, d_hist.ptr, n_lines, d_lines.ptr, stream))
 
     def expand2_device(self, d_parents, n, mode, out, stream=None, slot=0):
         """Depth 2 (gn_expand2_device).  out: DeviceBuffers po, off, ch (child boards), mv, co,

@@ -161,7 +161,9 @@ extern "C" {
                                          after the store, from the same lanes)            */
 /* stage times of the last gn_evaluate_games / gn_expand_and_evaluate (nanoseconds; per-device
  * stages: the slowest device).  The expansion runs in chunks of whole games; a drain thread
- * downloads chunk c's records on a copy stream while chunk c + 1 computes.               */
+ * downloads chunk c's records on a copy stream while chunk c + 1 computes.  The two-ply lines
+ * calls (gn_evaluate_lines2, gn_evaluate_games_lines2 and its history form) fill them too:
+ * their chunks run one after the other, compute then download, and leave no tail.         */
 #define GN_STAT_HOST_PARSE_NS 110     /* host: root FENs / FENs parsed, UCI moves tokenized */
 #define GN_STAT_HOST_UPLOAD_NS 111    /* host -> device copies of the inputs               */
 #define GN_STAT_HOST_REPLAY_NS 112    /* the GPU replay of the games' moves (games only)   */
@@ -177,11 +179,14 @@ extern "C" {
                                          over its chunks (0 after any other host-buffer
                                          call)                                             */
 #define GN_STAT_KEYS_NS 123           /* position_keys_kernel in the last
-                                         gn_evaluate_games_lines_history (the slowest
+                                         gn_evaluate_games_lines_history or
+                                         gn_evaluate_games_lines2_history (the slowest
                                          device; 0 after any other host-buffer call)       */
-#define GN_STAT_RANK2_NS 122          /* rank_lines2_kernel in the last gn_evaluate_lines2,
-                                         summed over its chunks (the slowest device; 0 after
-                                         any other host-buffer call)                       */
+#define GN_STAT_RANK2_NS 122          /* rank_lines2_kernel in the last gn_evaluate_lines2 or
+                                         gn_evaluate_games_lines2, or its history variant in
+                                         the last gn_evaluate_games_lines2_history, summed
+                                         over its chunks (the slowest device; 0 after any
+                                         other host-buffer call)                           */
 #define GN_STAT_BATCH_LAUNCHES 117    /* merged gn_evaluate_batch launches since load ...   */
 #define GN_STAT_BATCH_CALLS 118       /* ... and the calls they served (GN_OPT_COALESCE)    */
 #define GN_STAT_FAST_BATCHES 119      /* evaluations run by the captured small-batch graphs
@@ -202,8 +207,9 @@ extern "C" {
 #define GN_FLAG_SEARCHED 128u /* score from the in-check rule over the legal replies
                                  (best_move set), not from the static evaluation   */
 #define GN_FLAG_NO_MOVES 256u /* no legal move: checkmate (with IN_CHECK) or stalemate */
-#define GN_FLAG_DRAW 512u /* gn_line.flags only: the move's child is drawn by rule (threefold
-                             repetition or fifty-move rule; gn_history below)          */
+#define GN_FLAG_DRAW 512u /* gn_line.flags and gn_line2.flags of the history calls only: the
+                             line ends in a position drawn by rule (threefold repetition or
+                             fifty-move rule; gn_history and gn_line2 below)            */
 
 /* One result.  psqt/positional are Network::evaluate's NetworkOutput (already
  * divided by OutputScale = 16) of the net that produced final_v; final_v is
@@ -320,7 +326,11 @@ typedef struct gn_line {
  * A gn_history entry names a parent's game so far in a key array: keys[first..=self] are the
  * keys of the game's positions up to and including the parent (self).  first > self, or self
  * at or beyond the key count given with the array, means "no history": only the fifty-move part
- * applies. */
+ * applies.
+ * Two plies deep (gn_rank_lines2_history_device, gn_evaluate_games_lines2_history) the same test,
+ * against the same positions 0..=k, applies to the child and to each grandchild: the rule at
+ * gn_line2 below.  For a grandchild g the kernel tests positions k + 2 - d for d = 4, 6, ... <=
+ * min(g.rule50, k + 2). */
 typedef struct gn_history {
   uint32_t first, self;
 } gn_history;
@@ -350,7 +360,30 @@ typedef struct gn_history {
  * child c with a legal move, (R(c), reply) is exactly line 1's (value, move) from
  * gn_rank_children_device.
  * Relation to gn_eval.score: none is claimed.  The score rule searches only positions that are in
- * check (and then only replies that give check); these lines search two plies everywhere. */
+ * check (and then only replies that give check); these lines search two plies everywhere.
+ * With the game-history draws (gn_rank_lines2_history_device, gn_evaluate_games_lines2_history;
+ * GN_FLAG_DRAW is valid on gn_line2.flags for these calls only).  Position k of a game has the
+ * history of gn_history above: positions 0..=k, skipped ones included.  For a legal move m with
+ * child c, in this order of precedence:
+ *   1. c has no legal move: nothing changes.  R(c) = -VALUE_MATE when c is in check, else 0;
+ *      reply = 0, plies = 1, GN_FLAG_NO_MOVES, no GN_FLAG_DRAW.
+ *   2. c has a legal move and is drawn by rule -- c.rule50 >= 100, or c's identity equals that of
+ *      at least two of positions 0..=k (the gn_history rule): R(c) = 0, reply = 0, plies = 1,
+ *      GN_FLAG_DRAW, no GN_FLAG_NO_MOVES, GN_FLAG_IN_CHECK if m gives check.  c's grandchildren are
+ *      not consulted: Stockfish returns the draw at that node without searching it.
+ *   3. otherwise, for each reply r with grandchild g: g has no legal move: V1(g) = -VALUE_MATE when
+ *      g is in check, else 0, as above; else g drawn by rule -- g.rule50 >= 100, or g's identity
+ *      equals that of at least two of positions 0..=k (c has the other side to move and can never
+ *      equal g): V1(g) = 0; else V1(g) = g's static final_v.  R(c) = max negate_ply(V1(g)), ties to
+ *      the smaller reply encoding, plies = 2, and GN_FLAG_DRAW exactly when the chosen reply's
+ *      grandchild is drawn by rule.  A drawn reply ties with a static 0 by the reply encoding alone.
+ * value = negate_ply(R(c)), score, the order, the tie rule and the empty lines are unchanged.  A
+ * drawn line has value 0 and score 0; plies tells the two kinds apart (1: the move's child is the
+ * draw; 2: the best reply reaches it).
+ * Why "third occurrence" is the whole rule at ply 2 as well: Stockfish's is_draw(ply) also draws a
+ * single repetition that lies strictly after the root.  Two positions with the same side to move
+ * and equal identity are at least 4 plies apart, so at ply 1 or 2 the earlier occurrence always
+ * lies at or before the root, and the threefold test is all there is. */
 typedef struct gn_line2 { /* 16 bytes */
   int32_t value;  /* minimax value after two plies, p's side-to-move POV, Stockfish units  */
   int32_t score;  /* rule_score(value, p's win-rate material): cp, or the mate distance with
@@ -358,9 +391,10 @@ typedef struct gn_line2 { /* 16 bytes */
   uint16_t move;  /* p's move (Stockfish encoding, castling = king takes rook)             */
   uint16_t reply; /* the opponent's best reply to it; 0 when the move ends the game        */
   uint16_t flags; /* GN_FLAG_MATE; GN_FLAG_IN_CHECK: the move gives check; GN_FLAG_NO_MOVES:
-                     the move ends the game; GN_FLAG_NO_SCORE: an empty line               */
-  uint16_t plies; /* moves in the PV: 2, or 1 when the move ends the game, 0 for an empty
-                     line                                                                  */
+                     the move ends the game; GN_FLAG_NO_SCORE: an empty line; GN_FLAG_DRAW:
+                     the history calls only                                                */
+  uint16_t plies; /* moves in the PV: 2, or 1 when the move ends the game (or, in the history
+                     calls, reaches a position drawn by rule), 0 for an empty line         */
 } gn_line2;
 
 /* Packed position, 32 bytes, the device input format.
@@ -571,6 +605,28 @@ GN_API int gn_evaluate_games_lines_history(gn_ctx *ctx, const gn_game *games, si
                                            uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                                            size_t position_cap, gn_line *lines);
 
+/* gn_evaluate_games_lines with two-ply lines (gn_line2) instead: the same front (the games
+ * prepared, replayed on the device, sharded by game; position_offsets, game_status, position_out
+ * and GN_E_CAPACITY for the positions exactly as gn_evaluate_games), then each shard's evaluated
+ * positions through gn_evaluate_lines2's chunk loop: chunks of exactly GN_OPT_CHUNK_PARENTS
+ * parents (0: 1,024), one download per chunk.  lines[position * n_lines + k] = line k + 1 of each
+ * position, equal to gn_evaluate_lines2's for the position's FEN; a skipped position has only
+ * empty lines, a failed game no positions.  n_lines outside 1..GN_MAX_LINES: GN_E_INVALID.
+ * GN_STAT_HOST_* and GN_STAT_RANK2_NS: the call's stage times. */
+GN_API int gn_evaluate_games_lines2(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                    uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
+                                    size_t position_cap, gn_line2 *lines);
+
+/* gn_evaluate_games_lines2 with the game-history draws at both levels (the rule at gn_line2): each
+ * game's positions 0..=k, skipped ones included, are position k's history.  position_offsets,
+ * game_status and position_out are byte-equal to gn_evaluate_games_lines2's, and so are the lines
+ * wherever the rule draws nothing at either level.  The keys of every replayed position are made
+ * on the device once per shard (GN_STAT_KEYS_NS), so the chunks need no cut at game starts;
+ * GN_STAT_RANK2_NS: the ranking's time. */
+GN_API int gn_evaluate_games_lines2_history(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                            uint32_t *position_offsets, int32_t *game_status,
+                                            gn_eval *position_out, size_t position_cap, gn_line2 *lines);
+
 /* Two-ply ranked lines from FENs: out[i] = position i's record (byte-equal to
  * gn_expand_and_evaluate's parent_out for the same FENs and mode), lines[i * n_lines + k] = line
  * k + 1 of position i (gn_line2).  The FENs are sharded equally over the context's devices; each
@@ -685,6 +741,18 @@ GN_API int gn_rank_lines2_device(gn_ctx *ctx, int device_slot, const gn_board *d
                                  const uint32_t *d_offsets, const gn_board *d_children, const gn_eval *d_child_out,
                                  const uint16_t *d_moves, const uint32_t *d_goffsets, const uint16_t *d_gmoves,
                                  const gn_eval *d_grand_out, int n_lines, gn_line2 *d_lines, void *stream);
+/* gn_rank_lines2_device with the game-history draws at both levels (the rule at gn_line2):
+ * d_hist[i] names parent i's game so far in d_keys[0, n_keys), as for
+ * gn_rank_children_history_device.  An entry with first > self or self >= n_keys is "no history"
+ * (the fifty-move part still applies, at both levels); d_keys is never read at or beyond n_keys,
+ * and may be NULL when n_keys is 0.  Asynchronous, no read-back.  n_lines outside
+ * 1..GN_MAX_LINES: GN_E_INVALID. */
+GN_API int gn_rank_lines2_history_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                         const uint32_t *d_offsets, const gn_board *d_children,
+                                         const gn_eval *d_child_out, const uint16_t *d_moves,
+                                         const uint32_t *d_goffsets, const uint16_t *d_gmoves,
+                                         const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
+                                         const gn_history *d_hist, int n_lines, gn_line2 *d_lines, void *stream);
 GN_API int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, int mode,
                                  int iters, float *ms_total, size_t *total, float *stage_ms, uint64_t *ft_rows,
                                  gn_eval *d_parent_out, uint32_t *d_offsets, uint16_t *d_moves,

@@ -178,6 +178,44 @@ impl GpuNnue {
         Ok((offsets, status, evals, lines))
     }
 
+    /// evaluate_games_lines with two-ply lines: per position `n_lines` lines of a move, the
+    /// opponent's best reply and the minimax value after both, with the game's history taken into
+    /// account at the child and at the reply (gn_evaluate_games_lines2_history; include/gpu_nnue.h
+    /// at gn_line2).  A line that ends in a position drawn by rule is valued 0 and carries
+    /// GN_FLAG_DRAW; `plies` is 1 when the move itself reaches the draw, 2 when the best reply does.
+    /// Returns (position_offsets per game, game_status per game, records,
+    /// lines[position * n_lines + k]); a game that fails has no positions.
+    #[allow(clippy::type_complexity)]
+    pub fn evaluate_games_lines2(&self, games: &[(CString, CString, Vec<u32>)], n_lines: usize)
+                                 -> Result<(Vec<u32>, Vec<i32>, Vec<GpuEval>, Vec<GpuLine2>), GpuError> {
+        let gs: Vec<sys::gn_game> = games
+            .iter()
+            .map(|(root, moves, skip)| sys::gn_game {
+                root_fen: root.as_ptr(),
+                uci_moves: moves.as_ptr(),
+                skip_positions: if skip.is_empty() { ptr::null() } else { skip.as_ptr() },
+                n_skip: skip.len(),
+            })
+            .collect();
+        let mut offsets = vec![0u32; games.len() + 1];
+        let mut status = vec![0i32; games.len()];
+        // a game has at most one position per move token and one for the root
+        let cap: usize = games.iter().map(|(_, m, _)| m.as_bytes().split(|&b| b == b' ').filter(|t| !t.is_empty()).count() + 1).sum();
+        let mut evals = vec![GpuEval::default(); cap];
+        let mut lines = vec![GpuLine2::default(); cap * n_lines];
+        // SAFETY: offsets / status have games.len() (+ 1) elements, evals `cap` and lines
+        // cap * n_lines; the call checks n_lines and the capacity before it writes.
+        check(unsafe {
+            sys::gn_evaluate_games_lines2_history(self.0, gs.as_ptr(), gs.len(), sys::GN_MODE_FULL, n_lines as i32,
+                                                  offsets.as_mut_ptr(), status.as_mut_ptr(), evals.as_mut_ptr(), cap,
+                                                  lines.as_mut_ptr())
+        })?;
+        let total = offsets[games.len()] as usize;
+        evals.truncate(total);
+        lines.truncate(total * n_lines);
+        Ok((offsets, status, evals, lines))
+    }
+
     /// The best `n_lines` two-ply lines of every position (1..=8): the records as evaluate_batch
     /// returns them and, per position, `n_lines` lines of a move, the opponent's best reply and the
     /// minimax value after both (lines[i * n_lines + k] = line k + 1 of position i; `plies` is the

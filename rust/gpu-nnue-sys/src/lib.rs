@@ -238,6 +238,13 @@ extern "C" {
                                            n_lines: c_int, position_offsets: *mut u32, game_status: *mut i32,
                                            position_out: *mut gn_eval, position_cap: usize, lines: *mut gn_line)
                                            -> c_int;
+    pub fn gn_evaluate_games_lines2(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
+                                    n_lines: c_int, position_offsets: *mut u32, game_status: *mut i32,
+                                    position_out: *mut gn_eval, position_cap: usize, lines: *mut gn_line2) -> c_int;
+    pub fn gn_evaluate_games_lines2_history(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
+                                            n_lines: c_int, position_offsets: *mut u32, game_status: *mut i32,
+                                            position_out: *mut gn_eval, position_cap: usize, lines: *mut gn_line2)
+                                            -> c_int;
     pub fn gn_evaluate_lines2(ctx: *mut gn_ctx, fens: *const *const c_char, n: usize, mode: c_int, n_lines: c_int,
                               out: *mut gn_eval, lines: *mut gn_line2) -> c_int;
     pub fn gn_partition(weights: *const u32, n_items: usize, n_shards: c_int, bounds: *mut usize) -> c_int;
@@ -272,6 +279,12 @@ extern "C" {
                                  d_moves: *const u16, d_goffsets: *const u32, d_gmoves: *const u16,
                                  d_grand_out: *const gn_eval, n_lines: c_int, d_lines: *mut gn_line2,
                                  stream: *mut c_void) -> c_int;
+    pub fn gn_rank_lines2_history_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                                         d_offsets: *const u32, d_children: *const gn_board,
+                                         d_child_out: *const gn_eval, d_moves: *const u16, d_goffsets: *const u32,
+                                         d_gmoves: *const u16, d_grand_out: *const gn_eval, d_keys: *const u64,
+                                         n_keys: usize, d_hist: *const gn_history, n_lines: c_int,
+                                         d_lines: *mut gn_line2, stream: *mut c_void) -> c_int;
     pub fn gn_expand2_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize, mode: c_int,
                              d_parent_out: *mut gn_eval, d_offsets: *mut u32, d_children: *mut gn_board,
                              d_moves: *mut u16, d_child_out: *mut gn_eval, cap: usize, d_goffsets: *mut u32,
