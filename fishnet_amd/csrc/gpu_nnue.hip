@@ -767,6 +767,11 @@ static Dev *slot(gn_ctx *ctx, int s) {
   if (!ctx || s < 0 || s >= (int)ctx->devs.size()) return nullptr;
   return ctx->devs[s].get();
 }
+// the lines calls' K
+static int check_n_lines(int n_lines) {
+  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  return GN_OK;
+}
 
 template <class F>
 static void parallel_for(size_t n, size_t grain, F &&f) {
@@ -1635,6 +1640,7 @@ static int run_expansions(gn_ctx *ctx, Dev &d, int mode, size_t count, size_t la
 // (optional) and child_moves / child_out[0, off[m]); or, n_lines > 0 (gn_evaluate_games_lines), no
 // child reaches the host: each chunk's children are ranked on the device and lines[0, m * n_lines)
 // receives n_lines lines per parent.
+constexpr RankHistory NO_HISTORY = {nullptr, 0, nullptr}; // (hist NULL: the plain ranking)
 struct ExpandOut {
   gn_eval *parent_out = nullptr;
   uint16_t *child_moves = nullptr;
@@ -1642,10 +1648,8 @@ struct ExpandOut {
   int n_lines = 0;
   gn_line *lines = nullptr;
   // gn_evaluate_games_lines_history: the shard's keys (device, n_keys of them) and one gn_history per
-  // parent of the shard (device; chunk c's at history + chunks[c]); NULL: the plain ranking
-  const gn_history *history = nullptr;
-  const uint64_t *keys = nullptr;
-  size_t n_keys = 0;
+  // parent of the shard (device; chunk c's at hist + chunks[c]); hist NULL: the plain ranking
+  RankHistory history = NO_HISTORY;
 };
 // Pass 2 of a shard (see above).  off: the shard's child offsets from pass 1.
 static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m, int mode,
@@ -1725,14 +1729,10 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
         if (n_lines) {
           // (d.cur's offsets and unpacked parents are this chunk's: the front that overwrites the
           // set is queued after the synchronisation below)
+          const RankHistory h = {o.history.keys, o.history.n_keys, o.history.hist ? o.history.hist + pa : nullptr};
           HIP_TRY(hipEventRecord(d.rev[0], s));
-          if (o.history)
-            HIP_TRY(launch_rank_children_history(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P,
-                                                 d.tables, n_lines, d.ln2[k].p,
-                                                 RankHistory{o.keys, o.n_keys, o.history + pa}, s));
-          else
-            HIP_TRY(launch_rank_children(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P, d.tables,
-                                         n_lines, d.ln2[k].p, s));
+          HIP_TRY(launch_rank_children(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P, d.tables,
+                                       n_lines, d.ln2[k].p, h.hist ? &h : nullptr, s));
           HIP_TRY(hipEventRecord(d.rev[1], s));
         } else {
           HIP_TRY(launch_pack_children(d.co2[k].p, t, d.cc2[k].p, s));
@@ -2204,7 +2204,7 @@ static int games_expand(const GamesCall &c, GameShard &sh, Dev &d) {
   gn_line *const ln = sh.in_place ? c.lines + sh.p0 * (size_t)c.n_lines : sh.lres.data();
   ExpandOut o = c.n_lines ? ExpandOut{rec, nullptr, nullptr, c.n_lines, ln}
                           : ExpandOut{rec, c.child_moves + sh.child_base, c.child_out + sh.child_base};
-  if (c.history) o.history = d.hist.p, o.keys = d.rkeys.p, o.n_keys = d.n_rkeys;
+  if (c.history) o.history = RankHistory{d.rkeys.p, d.n_rkeys, d.hist.p};
   return expand_pipelined(c.ctx, d, sh.parents_of(d), sh.m, c.mode, sh.off,
                           chunk_plan(sh.m, sh.starts, c.ctx->chunk_parents), o);
 }
@@ -2299,7 +2299,7 @@ int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mod
 int gn_evaluate_games_lines(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                             uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                             size_t position_cap, gn_line *lines) {
-  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  if (int rc = check_n_lines(n_lines)) return rc;
   return evaluate_games({ctx, games, n_games, mode, 1, n_lines, false, position_offsets, nullptr, game_status,
                          position_out, position_cap, 0, nullptr, nullptr, lines});
 }
@@ -2307,7 +2307,7 @@ int gn_evaluate_games_lines(gn_ctx *ctx, const gn_game *games, size_t n_games, i
 int gn_evaluate_games_lines_history(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                                     uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                                     size_t position_cap, gn_line *lines) {
-  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  if (int rc = check_n_lines(n_lines)) return rc;
   return evaluate_games({ctx, games, n_games, mode, 1, n_lines, true, position_offsets, nullptr, game_status,
                          position_out, position_cap, 0, nullptr, nullptr, lines});
 }
@@ -2315,7 +2315,7 @@ int gn_evaluate_games_lines_history(gn_ctx *ctx, const gn_game *games, size_t n_
 static int evaluate_games_lines2(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines, bool history,
                                  uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                                  size_t position_cap, gn_line2 *lines) {
-  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  if (int rc = check_n_lines(n_lines)) return rc;
   return evaluate_games({ctx, games, n_games, mode, 0, n_lines, history, position_offsets, nullptr, game_status,
                          position_out, position_cap, 0, nullptr, nullptr, nullptr, lines});
 }
@@ -2765,24 +2765,29 @@ int gn_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, si
   return check_plan(*d, s);
 }
 
-// Depth 2 (SURVEY.md §8f row 4): the children of gn_expand_device's children.  Level 2 is
-// the same machinery with the children as parents: they arrive in sibling order, so a
-// block of consecutive siblings refreshes each from its predecessor's king-cache row
-// (plan_kernel: cache row + the placement difference, a few rows instead of ~30) and
-// every grandchild is incremental from its parent's accumulator.  The children are
-// evaluated again at level 2 (as parents); those results must equal level 1's and are
-// compared on the device (GN_E_HIP if not: an internal consistency check).
+// What the four gn_rank_*_device calls check before they take the device, in this order: the slot,
+// n_lines, the buffers every parent needs (the child and grandchild buffers may be NULL when no
+// parent has a child: they are then never read) and, for the history forms (h), the entries and
+// the keys.  d: the slot's device.
+static int rank_call_args(gn_ctx *ctx, int device_slot, size_t n, const gn_board *d_parents, const uint32_t *d_offsets,
+                          int n_lines, const void *d_lines, const RankHistory *h, Dev *&d) {
+  d = slot(ctx, device_slot);
+  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
+  if (int rc = check_n_lines(n_lines)) return rc;
+  if (n && (!d_parents || !d_offsets || !d_lines || (h && !h->hist))) return fail(GN_E_INVALID, "NULL buffer");
+  if (h && h->n_keys && !h->keys) return fail(GN_E_INVALID, "d_keys is NULL");
+  return GN_OK;
+}
+
 int gn_rank_children_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
                             const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out, int n_lines,
                             gn_line *d_lines, void *stream) {
-  Dev *d = slot(ctx, device_slot);
-  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
-  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
-  // (d_moves / d_child_out may be NULL when no parent has a child: they are then never read)
-  if (n && (!d_parents || !d_offsets || !d_lines)) return fail(GN_E_INVALID, "NULL buffer");
+  Dev *d;
+  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, nullptr, d)) return rc;
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
-  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables, n_lines, d_lines, call.s));
+  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables, n_lines, d_lines, nullptr,
+                               call.s));
   return GN_OK;
 }
 
@@ -2801,18 +2806,24 @@ int gn_rank_children_history_device(gn_ctx *ctx, int device_slot, const gn_board
                                     const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out,
                                     const uint64_t *d_keys, size_t n_keys, const gn_history *d_hist, int n_lines,
                                     gn_line *d_lines, void *stream) {
-  Dev *d = slot(ctx, device_slot);
-  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
-  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
-  if (n && (!d_parents || !d_offsets || !d_lines || !d_hist)) return fail(GN_E_INVALID, "NULL buffer");
-  if (n_keys && !d_keys) return fail(GN_E_INVALID, "d_keys is NULL");
+  const RankHistory h = {d_keys, n_keys, d_hist};
+  Dev *d;
+  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, &h, d)) return rc;
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
-  HIP_TRY(launch_rank_children_history(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables, n_lines, d_lines,
-                                       RankHistory{d_keys, n_keys, d_hist}, call.s));
+  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables, n_lines, d_lines, &h,
+                               call.s));
   return GN_OK;
 }
 
+// Depth 2 (SURVEY.md §8f row 4): the children of gn_expand_device's children.  Level 2 is
+// the same machinery with the children as parents: they arrive in sibling order, so a
+// block of consecutive siblings refreshes each from its predecessor's king-cache row
+// (plan_kernel: cache row + the placement difference, a few rows instead of ~30) and
+// every grandchild is incremental from its parent's accumulator.  The children are
+// evaluated again at level 2 (as parents); those results must equal level 1's and are
+// compared on the device (GN_E_HIP if not: an internal consistency check).
+//
 // gn_expand2_device's work on stream s (d.mu held, the launch sequence begun).  size_grand
 // (optional, gn_evaluate_lines2): called with the grandchild count once level 1 is done, it
 // provides the level-2 buffers (d_goffsets: total + 1, d_gmoves / d_grand_out / gcap: the count)
@@ -2913,15 +2924,12 @@ int gn_rank_lines2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parent
                           const gn_board *d_children, const gn_eval *d_child_out, const uint16_t *d_moves,
                           const uint32_t *d_goffsets, const uint16_t *d_gmoves, const gn_eval *d_grand_out, int n_lines,
                           gn_line2 *d_lines, void *stream) {
-  Dev *d = slot(ctx, device_slot);
-  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
-  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
-  // (the child and grandchild buffers may be NULL when no parent has a child: they are then never read)
-  if (n && (!d_parents || !d_offsets || !d_lines)) return fail(GN_E_INVALID, "NULL buffer");
+  Dev *d;
+  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, nullptr, d)) return rc;
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
   HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
-                             ctx->P, d->tables, n_lines, d_lines, call.s));
+                             ctx->P, d->tables, n_lines, d_lines, nullptr, call.s));
   return GN_OK;
 }
 
@@ -2930,16 +2938,13 @@ int gn_rank_lines2_history_device(gn_ctx *ctx, int device_slot, const gn_board *
                                   const uint16_t *d_moves, const uint32_t *d_goffsets, const uint16_t *d_gmoves,
                                   const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
                                   const gn_history *d_hist, int n_lines, gn_line2 *d_lines, void *stream) {
-  Dev *d = slot(ctx, device_slot);
-  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
-  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
-  if (n && (!d_parents || !d_offsets || !d_lines || !d_hist)) return fail(GN_E_INVALID, "NULL buffer");
-  if (n_keys && !d_keys) return fail(GN_E_INVALID, "d_keys is NULL");
+  const RankHistory h = {d_keys, n_keys, d_hist};
+  Dev *d;
+  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, &h, d)) return rc;
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
-  HIP_TRY(launch_rank_lines2_history(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves,
-                                     d_grand_out, ctx->P, d->tables, n_lines, d_lines,
-                                     RankHistory{d_keys, n_keys, d_hist}, call.s));
+  HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
+                             ctx->P, d->tables, n_lines, d_lines, &h, call.s));
   return GN_OK;
 }
 
@@ -3225,11 +3230,11 @@ int gn_expand_and_evaluate(gn_ctx *ctx, const char *const *parent_fens, size_t n
 // A shard's two-ply lines (gn_evaluate_lines2, gn_evaluate_games_lines2): its m device-resident
 // parents in chunks of chunk parents; per chunk the depth-2 expansion into the device's Lines2
 // buffers (expand2_on), rank_lines2_kernel -- its history variant when history names the shard's
-// keys and its parents' gn_history entries -- and one download of the chunk's parent records and
+// keys and its parents' gn_history entries (hist NULL: the plain one) -- and one download of the chunk's parent records and
 // lines into out / lines (the shard's first parent's).  The chunks need no cut at game starts: the
 // keys are the whole shard's.
 static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m, int mode, int K, gn_eval *out,
-                         gn_line2 *lines, const RankHistory *history) {
+                         gn_line2 *lines, const RankHistory &history) {
   hipStream_t s = d.stream;
   Dev::Lines2 &x = d.l2;
   // 1,024 parents are ~1 M grandchildren: a few hundred MB of records, boards and partial sums
@@ -3257,14 +3262,10 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
     int rc = expand2_on(ctx, &d, par, mp, mode, x.po.p, x.off.p, x.ch.p, x.mv.p, x.co.p, cap, Expand2Grand{}, &t, &g, s,
                         &size_grand);
     if (rc) return rc;
+    const RankHistory h = {history.keys, history.n_keys, history.hist ? history.hist + a : nullptr};
     HIP_TRY(hipEventRecord(d.rev[0], s));
-    if (history)
-      HIP_TRY(launch_rank_lines2_history(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P,
-                                         d.tables, K, x.ln.p, RankHistory{history->keys, history->n_keys, history->hist + a},
-                                         s));
-    else
-      HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables, K,
-                                 x.ln.p, s));
+    HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables, K,
+                               x.ln.p, h.hist ? &h : nullptr, s));
     HIP_TRY(hipEventRecord(d.rev[1], s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0;
@@ -3293,7 +3294,7 @@ static int lines2_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int
     HIP_TRY(hipMemcpyAsync(d.par.p, boards + lo, (hi - lo) * sizeof(gn_board), hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipStreamSynchronize(d.stream));
     d.t_upload += ms_since(t0);
-    return lines2_chunks(ctx, d, d.par.p, hi - lo, mode, K, out + lo, lines + lo * (size_t)K, nullptr);
+    return lines2_chunks(ctx, d, d.par.p, hi - lo, mode, K, out + lo, lines + lo * (size_t)K, NO_HISTORY);
   });
 }
 
@@ -3302,16 +3303,15 @@ static int lines2_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int
 static int games_lines2(const GamesCall &c, GameShard &sh, Dev &d) {
   const int rc = games_gather(c, sh, d);
   if (rc) return rc;
-  const RankHistory h{d.rkeys.p, d.n_rkeys, d.hist.p};
   gn_line2 *const ln = sh.in_place ? c.lines2 + sh.p0 * (size_t)c.n_lines : sh.l2res.data();
   return lines2_chunks(c.ctx, d, sh.parents_of(d), sh.m, c.mode, c.n_lines, sh.records_of(c.position_out), ln,
-                       c.history ? &h : nullptr);
+                       c.history ? RankHistory{d.rkeys.p, d.n_rkeys, d.hist.p} : NO_HISTORY);
 }
 
 int gn_evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,
                        gn_line2 *lines) {
   if (!slot(ctx, 0)) return fail(GN_E_INVALID, "bad context");
-  if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  if (int rc = check_n_lines(n_lines)) return rc;
   if (n && (!fens || !out || !lines)) return fail(GN_E_INVALID, "NULL argument");
   if (!n) return GN_OK;
   return on_packed_fens(ctx, fens, n, [&](const gn_board *boards) -> int {

@@ -252,26 +252,19 @@ hipError_t launch_pack_children(const gn_eval *in, size_t n, gn_child *out, hipS
 // children [offsets[i], offsets[i + 1]) (moves, records rec of one expansion), 1 <= K <= GN_MAX_LINES.
 // The parents as write_children unpacked them with the pipeline's 64-bit offsets (an entry is
 // read only where the parent has children), or packed with the C-ABI's 32-bit offsets.
-hipError_t launch_rank_children(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
-                                const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                gn_line *lines, hipStream_t s);
-hipError_t launch_rank_children(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
-                                const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                gn_line *lines, hipStream_t s);
-// ... with the game-history draws (include/gpu_nnue.h at gn_history; rank_children_kernel with a RankHistory):
-// hist[i] names parent i's game so far in keys[0, n_keys) (position_key of each position)
+// With history (include/gpu_nnue.h at gn_history) the game-history draws are applied: hist[i] names
+// parent i's game so far in keys[0, n_keys) (position_key of each position).  NULL: the plain ranking.
 struct RankHistory {
   const uint64_t *keys;
   size_t n_keys;
   const gn_history *hist;
 };
-hipError_t launch_rank_children_history(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
-                                        const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                        gn_line *lines, const RankHistory &history, hipStream_t s);
-hipError_t launch_rank_children_history(const gn_board *parents, size_t n, const uint32_t *offsets,
-                                        const uint16_t *moves, const gn_eval *rec, const gn_eval_params &P,
-                                        const Tables *tables, int K, gn_line *lines, const RankHistory &history,
-                                        hipStream_t s);
+hipError_t launch_rank_children(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
+                                const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
+                                gn_line *lines, const RankHistory *history, hipStream_t s);
+hipError_t launch_rank_children(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
+                                const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
+                                gn_line *lines, const RankHistory *history, hipStream_t s);
 // keys[i] = position_key of boards[i], a lane per board.  gate: a caller's boards (unpack; a
 // rejected board's key is 0); else the library's own canonical boards (unpack_fields)
 hipError_t launch_position_keys(const gn_board *boards, size_t n, bool gate, const Tables *tables, uint64_t *keys,
@@ -283,17 +276,13 @@ hipError_t launch_position_keys(const gn_board *boards, size_t n, bool gate, con
 // child.  (The kernel is templated on the parent form and offset type like rank_children_kernel;
 // the host path feeds it the same packed parents and 32-bit offsets as the C-ABI: level 2 of the
 // expansion has overwritten the buffer set's unpacked parents and 64-bit offsets by then.)
+// history: the game-history draws at both levels (include/gpu_nnue.h at gn_line2 and gn_history),
+// hist[i] naming parent i's game so far as above; NULL: the plain ranking.
 hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t *offsets, const gn_board *children,
                               const gn_eval *rec, const uint16_t *moves, const uint32_t *goffsets,
                               const uint16_t *gmoves, const gn_eval *grec, const gn_eval_params &P,
-                              const Tables *tables, int K, gn_line2 *lines, hipStream_t s);
-// ... with the game-history draws at both levels (include/gpu_nnue.h at gn_line2 and gn_history;
-// rank_lines2_kernel with a RankHistory): hist[i] names parent i's game so far, as above
-hipError_t launch_rank_lines2_history(const gn_board *parents, size_t n, const uint32_t *offsets,
-                                      const gn_board *children, const gn_eval *rec, const uint16_t *moves,
-                                      const uint32_t *goffsets, const uint16_t *gmoves, const gn_eval *grec,
-                                      const gn_eval_params &P, const Tables *tables, int K, gn_line2 *lines,
-                                      const RankHistory &history, hipStream_t s);
+                              const Tables *tables, int K, gn_line2 *lines, const RankHistory *history,
+                              hipStream_t s);
 // narrowing copy of offsets for the C-ABI
 hipError_t launch_offsets_u32(const uint64_t *in, size_t n, uint32_t *out, hipStream_t s);
 // exclusive scan of n + 1 counts (counts[n] must be 0); temp grows on demand

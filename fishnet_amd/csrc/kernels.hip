@@ -1041,9 +1041,9 @@ hipError_t launch_pack_children(const gn_eval *in, size_t n, gn_child *out, hipS
 // child, the group looping over a segment longer than itself.  Each lane makes its child
 // (do_move from the parent the group holds) and asks any_legal, which stops at the first legal
 // move: needed for every child, a stalemating move not being a check.  The lane's line is one
-// sortable key, (value + 32768) << 18 | (0xFFFF - move) << 2 | no-moves << 1 | in-check: larger
-// value first, then the smaller move; the two flag bits ride below the move, where they cannot
-// change the order (a parent's moves are distinct).  0 is no line: value >= -32000.
+// sortable key (LineKey below), (value + 32768) << 18 | (0xFFFF - move) << 2 | no-moves << 1 |
+// in-check: larger value first, then the smaller move; the flag bits ride below the move, where
+// they cannot change the order (a parent's moves are distinct).  0 is no line: value >= -32000.
 // K rounds of a cross-lane maximum (xor butterfly) over the lanes' keys and the running top K
 // (lane k's `top`, from the segment's earlier iterations) give the new top K, round k's winner
 // to lane k, the winner retiring; lanes 0..K-1 then write the parent's K lines, 12 B each, as
@@ -1063,7 +1063,6 @@ __device__ __forceinline__ uint64_t group_max_w(uint64_t v) {
   }
   return v;
 }
-__device__ __forceinline__ uint64_t group_max(uint64_t v) { return group_max_w<GN_RANK_WIDTH>(v); }
 template <int W>
 __device__ __forceinline__ uint32_t group_sum_w(uint32_t v) {
 #pragma unroll
@@ -1090,22 +1089,78 @@ __device__ __forceinline__ uint64_t top_k_rounds(uint64_t key, uint64_t top, int
 __device__ __forceinline__ bool rank_parent(const Board &src, Board &B, const Tables &) { B = src; return true; }
 __device__ __forceinline__ bool rank_parent(const gn_board &src, Board &B, const Tables &T) { return unpack(src, B, T); }
 
-// History variant (HIST; include/gpu_nnue.h at gn_history): where the lane holds its child C with
-// `none` and `check`, a child that has a legal move is drawn by rule when C.rule50 >= 100, or when
-// its position_key equals at least two keys of the parent's game so far, keys[first..=self] of the
-// parent's gn_history entry.  The walk tests only self + 1 - d for d = 4, 6, ... <=
-// min(C.rule50, self - first + 1): a pawn move or a capture lies between C and anything older,
-// and a position with the other side to move cannot equal C.  Its trip count differs per lane, so
-// it sits where any_legal sits: every shuffle stays outside it.  An entry with first > self or
-// self >= n_keys is no history (the fifty-move part still applies), so keys is never indexed at or
-// beyond n_keys.  The draw bit rides below the move with the other two flag bits, the value and
-// the move one bit higher: (value + 32768) << 19 | (0xFFFF - move) << 3 | draw << 2 |
-// no-moves << 1 | in-check.  The variant is chosen at compile time by an optional trailing kernel
-// argument (History: nothing, or one RankHistory), so the plain instantiations keep their
-// arguments and their code.  Left to itself the history variant takes 181 VGPRs, 2 waves per SIMD
-// where the plain kernel (162) runs 3, and that, not the key arithmetic or the walk's loads, was
-// its cost; asked for 3 waves it fits 168 without scratch.  (The plain variant
-// asks for 1, which is what no request means: its code is unchanged.)
+// The ranking kernels' sort keys: (value + 32768) << (PAYLOAD + FLAGS) | payload << FLAGS | flags.
+// The payload breaks ties between equal values and is distinct among the keys that meet, so the
+// flags below it never change an order.  0 is no key: value >= -32000.
+template <int PAYLOAD, int FLAGS>
+struct SortKey {
+  static __device__ __forceinline__ uint64_t pack(int32_t value, uint64_t payload, uint32_t flags) {
+    return (uint64_t)(uint32_t)(value + 32768) << (PAYLOAD + FLAGS) | payload << FLAGS | flags;
+  }
+  static __device__ __forceinline__ int32_t value(uint64_t k) { return (int32_t)(k >> (PAYLOAD + FLAGS)) - 32768; }
+  static __device__ __forceinline__ uint32_t payload(uint64_t k) { return (uint32_t)(k >> FLAGS & ((1ull << PAYLOAD) - 1)); }
+  static __device__ __forceinline__ uint32_t flags(uint64_t k) { return (uint32_t)(k & ((1u << FLAGS) - 1)); }
+};
+// The flags, in one order everywhere; the draw bit exists in the history variants' keys only.
+constexpr uint32_t KEY_CHECK = 1, KEY_NO_MOVES = 2, KEY_DRAW = 4;
+// a line of rank_children_kernel: payload 0xFFFF - move (the smaller move first)
+template <bool HIST> using LineKey = SortKey<16, HIST ? 3 : 2>;
+// a grandchild of rank_lines2_kernel: payload 0xFFFF - reply; its one flag is the draw bit (1: drawn)
+template <bool HIST> using ReplyKey = SortKey<16, HIST ? 1 : 0>;
+// a child of rank_lines2_kernel: payload (0xFFFF - move) << 16 | reply (moves are distinct; the reply rides along)
+template <bool HIST> using ChildKey = SortKey<32, HIST ? 3 : 2>;
+__device__ __forceinline__ uint32_t line_flags(uint32_t kf) {
+  return ((kf & KEY_CHECK) ? GN_FLAG_IN_CHECK : 0u) | ((kf & KEY_NO_MOVES) ? GN_FLAG_NO_MOVES : 0u) |
+         ((kf & KEY_DRAW) ? GN_FLAG_DRAW : 0u);
+}
+
+// Game-history draws (include/gpu_nnue.h at gn_history), shared by the history variants of both
+// ranking kernels.  A parent's game so far is keys[first..=self] of its gn_history entry: `len`
+// positions, the newest at keys[self].  An entry with first > self or self >= n_keys is no history
+// (len 0; the fifty-move part of the rule still applies), and since every reader indexes below
+// self + 1 and not below first, keys is never indexed at or beyond n_keys.
+struct HistWindow {
+  uint32_t self, len;
+};
+__device__ __forceinline__ HistWindow hist_window(const RankHistory &h, size_t p) {
+  const gn_history e = h.hist[p];
+  return {e.self, (e.first <= e.self && (size_t)e.self < h.n_keys) ? e.self - e.first + 1 : 0u};
+}
+// A position X that has a legal move is drawn by rule when X.rule50 >= 100, or when its
+// position_key equals at least two of the `len` keys that end just below newest_plus_1.  X is d
+// plies after newest_plus_1[-d]; the walk tests only d = 4, 6, ... <= min(X.rule50, len): a pawn
+// move or a capture lies between X and anything older, a position with the other side to move
+// cannot equal X, and two plies cannot restore a position (d = 2).  The trip count differs per
+// lane, so a caller puts the test where any_legal sits: outside every shuffle.
+__device__ __forceinline__ uint32_t drawn_by_rule(const Board &X, const uint64_t *newest_plus_1, uint32_t len) {
+  const uint32_t lim = X.rule50 < len ? (uint32_t)X.rule50 : len;
+  if (X.rule50 >= 100) return 1;
+  if (lim < 4) return 0;
+  const uint64_t xk = position_key(X);
+  uint32_t seen = 0;
+  // four keys per trip, their loads independent of each other (a trip's tail re-reads d = 4,
+  // which lim >= 4 makes valid, and ignores it); the walk ends between trips
+  for (uint32_t d = 4; d <= lim && seen < 2; d += 8) {
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j += 2) {
+      const bool in = d + j <= lim;
+      const uint64_t k = *(newest_plus_1 - (in ? d + j : 4u));
+      seen += in && k == xk ? 1u : 0u;
+    }
+  }
+  return seen >= 2 ? 1u : 0u;
+}
+
+// History variant (HIST): where the lane holds its child C with `none` and `check`, a child that
+// has a legal move is tested by drawn_by_rule against the parent's window, C being one ply after
+// keys[self].  The draw bit rides below the move with the other two flag bits, the value and the
+// move one bit higher: (value + 32768) << 19 | (0xFFFF - move) << 3 | draw << 2 | no-moves << 1 |
+// in-check.  The variant is chosen at compile time by an optional trailing kernel argument
+// (History: nothing, or one RankHistory), so the plain instantiations keep their arguments.
+// Left to itself the history variant takes 181 VGPRs, 2 waves per SIMD where the
+// plain kernel (162) runs 3, and that, not the key arithmetic or the walk's loads, was its cost
+// (DESIGN.md §1.5); asked for 3 waves it fits 168 without scratch.  (The plain variant asks for 1,
+// which is what no request means.)
 template <class Parent, class Off, class... History>
 __global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(sizeof...(History) ? 3 : 1)))
     rank_children_kernel(const Parent *__restrict__ parents, size_t n, const Off *__restrict__ offsets,
@@ -1116,7 +1171,7 @@ __global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(si
   __shared__ Tables T;
   load_tables(T, tables);
   constexpr int W = GN_RANK_WIDTH;
-  constexpr int FB = HIST ? 3 : 2; // flag bits below the move
+  using Key = LineKey<HIST>;
   const int lane = threadIdx.x & (W - 1);
   // a bounded grid striding over the parents (the 4 KiB table load once per workgroup)
   const size_t stride = (size_t)gridDim.x * (RANK_WG / W);
@@ -1127,13 +1182,9 @@ __global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(si
     // (a parent without children -- bad, mated, stalemated, or skipped by the caller -- is never
     // unpacked or read as a Board: its unpacked entry is not written)
     const bool ok = c1 > c0 && rank_parent(parents[p], B, T);
-    uint32_t hself = 0, hlen = 0; // HIST: the parent's key index, and its game's positions so far (0: no history)
+    HistWindow hw = {0, 0}; // HIST: the parent's game so far (len 0: no history)
     if constexpr (HIST) {
-      if (ok) {
-        const gn_history h = (history.hist, ...)[p];
-        hself = h.self;
-        hlen = (h.first <= h.self && (size_t)h.self < (history.n_keys, ...)) ? h.self - h.first + 1 : 0u;
-      }
+      if (ok) hw = hist_window((history, ...), p);
     }
     for (uint64_t c = c0; ok && c < c1; c += W) {
       uint64_t key = 0;
@@ -1141,56 +1192,23 @@ __global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(si
         const uint32_t mv = moves[c + lane];
         const gn_eval r = rec[c + lane];
         const Board C = do_move(B, (uint16_t)mv, nullptr);
-        const uint32_t check = (r.flags & GN_FLAG_IN_CHECK) ? 1u : 0u;
-        const uint32_t none = any_legal(C, T) ? 0u : 1u;
+        const uint32_t check = (r.flags & GN_FLAG_IN_CHECK) ? KEY_CHECK : 0u;
+        const uint32_t none = any_legal(C, T) ? 0u : KEY_NO_MOVES;
+        uint32_t draw = 0;
         if constexpr (HIST) {
-          uint32_t draw = 0;
-          if (!none) {
-            const uint32_t lim = C.rule50 < hlen ? (uint32_t)C.rule50 : hlen;
-            if (C.rule50 >= 100) {
-              draw = 1;
-            } else if (lim >= 4) {
-              const uint64_t ck = position_key(C);
-              uint32_t seen = 0;
-              // four keys per trip, their loads independent of each other (a trip's tail re-reads
-              // d = 4, which lim >= 4 makes valid, and ignores it); the walk ends between trips
-              const uint64_t *const at = (history.keys, ...) + ((size_t)hself + 1);
-              for (uint32_t d = 4; d <= lim && seen < 2; d += 8) {
-#pragma unroll
-                for (uint32_t j = 0; j < 8; j += 2) {
-                  const bool in = d + j <= lim;
-                  const uint64_t k = *(at - (in ? d + j : 4u));
-                  seen += in && k == ck ? 1u : 0u;
-                }
-              }
-              draw = seen >= 2 ? 1u : 0u;
-            }
-          }
-          const int32_t v = negate_ply(none ? (check ? -VALUE_MATE : 0) : draw ? 0 : r.final_v);
-          key = (uint64_t)(uint32_t)(v + 32768) << 19 | (uint64_t)(0xFFFFu - mv) << 3 | draw << 2 | none << 1 | check;
-        } else {
-          const int32_t v = negate_ply(none ? (check ? -VALUE_MATE : 0) : r.final_v);
-          key = (uint64_t)(uint32_t)(v + 32768) << 18 | (uint64_t)(0xFFFFu - mv) << 2 | none << 1 | check;
+          if (!none && drawn_by_rule(C, (history.keys, ...) + ((size_t)hw.self + 1), hw.len)) draw = KEY_DRAW;
         }
+        const int32_t v = negate_ply(none ? (check ? -VALUE_MATE : 0) : draw ? 0 : r.final_v);
+        key = Key::pack(v, 0xFFFFu - mv, draw | none | check);
       }
-      uint64_t next = 0;
-      for (int k = 0; k < K; ++k) {
-        const uint64_t mine = key > top ? key : top;
-        const uint64_t m = group_max(mine);
-        if (!m) break; // (uniform in the group) fewer than K lines so far
-        if (key == m) key = 0;
-        if (top == m) top = 0;
-        if (lane == k) next = m;
-      }
-      top = next;
+      top = top_k_rounds<W>(key, top, lane, K);
     }
     if (lane < K) {
       gn_line l = {0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE};
       if (top) {
-        uint32_t fl = ((top & 1) ? GN_FLAG_IN_CHECK : 0u) | ((top & 2) ? GN_FLAG_NO_MOVES : 0u);
-        if constexpr (HIST) fl |= (top & 4) ? GN_FLAG_DRAW : 0u;
-        l.value = (int32_t)(top >> (16 + FB)) - 32768;
-        l.move = (uint16_t)(0xFFFFu - (uint32_t)((top >> FB) & 0xFFFFu));
+        uint32_t fl = line_flags(Key::flags(top));
+        l.value = Key::value(top);
+        l.move = (uint16_t)(0xFFFFu - Key::payload(top));
         l.score = rule_score(l.value, wdl_material(B, P), P, fl);
         l.flags = (uint16_t)fl;
       }
@@ -1203,7 +1221,7 @@ __global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(si
 template <class Parent, class Off>
 static hipError_t rank_children_t(const Parent *parents, size_t n, const Off *offsets, const uint16_t *moves,
                                   const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                  gn_line *lines, hipStream_t s, const RankHistory *history = nullptr) {
+                                  gn_line *lines, const RankHistory *history, hipStream_t s) {
   if (!n) return hipSuccess;
   constexpr size_t per_wg = RANK_WG / GN_RANK_WIDTH, max_blocks = 8192;
   const size_t blocks = std::min<size_t>((n + per_wg - 1) / per_wg, max_blocks);
@@ -1217,24 +1235,13 @@ static hipError_t rank_children_t(const Parent *parents, size_t n, const Off *of
 }
 hipError_t launch_rank_children(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
                                 const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                gn_line *lines, hipStream_t s) {
-  return rank_children_t(unpacked, n, offsets, moves, rec, P, tables, K, lines, s);
+                                gn_line *lines, const RankHistory *history, hipStream_t s) {
+  return rank_children_t(unpacked, n, offsets, moves, rec, P, tables, K, lines, history, s);
 }
 hipError_t launch_rank_children(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
                                 const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                gn_line *lines, hipStream_t s) {
-  return rank_children_t(parents, n, offsets, moves, rec, P, tables, K, lines, s);
-}
-hipError_t launch_rank_children_history(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
-                                        const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                        gn_line *lines, const RankHistory &history, hipStream_t s) {
-  return rank_children_t(unpacked, n, offsets, moves, rec, P, tables, K, lines, s, &history);
-}
-hipError_t launch_rank_children_history(const gn_board *parents, size_t n, const uint32_t *offsets,
-                                        const uint16_t *moves, const gn_eval *rec, const gn_eval_params &P,
-                                        const Tables *tables, int K, gn_line *lines, const RankHistory &history,
-                                        hipStream_t s) {
-  return rank_children_t(parents, n, offsets, moves, rec, P, tables, K, lines, s, &history);
+                                gn_line *lines, const RankHistory *history, hipStream_t s) {
+  return rank_children_t(parents, n, offsets, moves, rec, P, tables, K, lines, history, s);
 }
 
 // Position keys (chess.h position_key), a lane per board.  GATE: a caller's boards through the
@@ -1269,12 +1276,12 @@ hipError_t launch_position_keys(const gn_board *boards, size_t n, bool gate, con
 // workgroup takes one parent at a time; its eight 32-lane groups take the parent's children
 // round-robin (group q: children q, q + 8, ...).  A group unpacks its child (the library's own
 // board: unpack_fields, no gate, as level 2 of the expansion reads it), a lane takes a grandchild
-// (do_move from the child, any_legal, its key (V + 32768) << 16 | 0xFFFF - reply with
+// (do_move from the child, any_legal, its key (ReplyKey) (V + 32768) << 16 | 0xFFFF - reply with
 // V = negate_ply(V1(g))), keeps a running maximum over segments longer than 32, and one butterfly
 // per child gives R(c) and the reply.  A child without grandchildren needs no board: mated or
-// stalemated by its record's check bit.  The child's key is rank_children_kernel's packing with
-// the reply below the move: (value + 32768) << 34 | (0xFFFF - move) << 18 | reply << 2 |
-// no-moves << 1 | in-check, value = negate_ply(R(c)); 0 is no line.  Each group keeps its own
+// stalemated by its record's check bit.  The child's key (ChildKey) is rank_children_kernel's
+// packing with the reply below the move: (value + 32768) << 34 | (0xFFFF - move) << 18 |
+// reply << 2 | no-moves << 1 | in-check, value = negate_ply(R(c)); 0 is no line.  Each group keeps its own
 // top list sorted in its lanes (lane k: the group's k-th best so far) and inserts a child's key
 // with one __shfl_up: any number of children, no staging array.  The eight groups' top 8 then
 // meet in LDS (64 keys) and wave 0 merges them by the K-round maximum over two 32-key passes;
@@ -1282,26 +1289,26 @@ hipError_t launch_position_keys(const gn_board *boards, size_t n, bool gate, con
 // Control flow: the loop over a parent's children and the branch on a parent without children
 // are uniform in the workgroup (both barriers are reached by every lane or by none); the loop
 // over a child's grandchildren runs until no lane of the wave has one left (__any), so both
-// groups of a wave reach every shuffle together.
+// groups of a wave reach every shuffle together.  (The plain kernel skips a wave's child unpack
+// and loop when neither of its groups has a grandchild: the same __any.)
 //
 // History variant (HIST; include/gpu_nnue.h at gn_line2 and gn_history), chosen like
 // rank_children_kernel's by an optional trailing RankHistory, so the plain instantiation keeps its
-// arguments and its code.  The parent's gn_history entry is read once per parent.  A child with a
-// grandchild is tested by its group, which holds nothing else: lane j tests the keys at
-// self + 1 - d for d = 4 + 2j (+ 64 ...) <= min(C.rule50, self - first + 1), and a sum over the
-// group counts the matches, so the outcome is uniform in the group and the sum's shuffles are
-// reached by every lane of the wave, drawn or not, child or none.  A drawn child's grandchildren
-// are not consulted: its group's loop bound becomes g0, like a child without any, and the __any
-// still keeps the wave's other group company.  A grandchild G that has a legal move is tested by
-// its lane, where any_legal sits and no shuffle does: G.rule50 >= 100, or two matches among
-// self + 2 - d for d = 4, 6, ... <= min(G.rule50, self - first + 2), four independent loads per
-// trip as in rank_children_kernel.  (The child has the other side to move and can never equal G;
-// d = 2 would be the parent, which two plies cannot restore.)  No history (first > self or
-// self >= n_keys) leaves only the fifty-move part at both levels, and keys is never indexed at or
-// beyond n_keys.  The draw bit rides in the reply key below the reply, (V + 32768) << 17 |
-// (0xFFFF - reply) << 1 | draw, and in the child key below the other two flag bits, the other
-// fields one bit higher: (value + 32768) << 35 | (0xFFFF - move) << 19 | reply << 3 |
-// no-moves << 2 | in-check << 1 | draw.  A drawn child has reply 0: plies is reply ? 2 : 1.
+// arguments; the two share one body, which differs at the draw tests and in the keys' flag bits.
+// The parent's window (hist_window) is read once per parent.  A child with a grandchild is tested
+// by its group, which holds nothing else: lane j tests the keys at self + 1 - d for
+// d = 4 + 2j (+ 64 ...) <= min(C.rule50, len), and a sum over the group counts the matches, so the
+// outcome is uniform in the group and the sum's shuffles are reached by every lane of the wave,
+// drawn or not, child or none.  A drawn child's grandchildren are not consulted: its group's loop
+// bound becomes g0, like a child without any, and the __any still keeps the wave's other group
+// company.  A grandchild G that has a legal move is tested by its lane, where any_legal sits and
+// no shuffle does: drawn_by_rule with the window one longer, G being two plies after keys[self].
+// (The child has the other side to move and can never equal G.)  No history leaves only the
+// fifty-move part at both levels.  The draw bit rides in the reply key below the reply,
+// (V + 32768) << 17 | (0xFFFF - reply) << 1 | draw, and in the child key with the other two flag
+// bits, the other fields one bit higher: (value + 32768) << 35 | (0xFFFF - move) << 19 |
+// reply << 3 | draw << 2 | no-moves << 1 | in-check.  A child without a reply to show (none, or
+// drawn) has reply 0, a legal reply's encoding is never 0: plies is reply ? 2 : 1.
 template <class Parent, class Off, class... History>
 __global__ void __launch_bounds__(RANK_WG)
     rank_lines2_kernel(const Parent *__restrict__ parents, size_t n, const Off *__restrict__ offsets,
@@ -1311,7 +1318,8 @@ __global__ void __launch_bounds__(RANK_WG)
                        const Tables *__restrict__ tables, int K, gn_line2 *__restrict__ lines, History... history) {
   static_assert(sizeof...(History) <= 1, "nothing, or one RankHistory");
   constexpr bool HIST = sizeof...(History) != 0;
-  constexpr int FB = HIST ? 3 : 2; // flag bits below the reply
+  using Reply = ReplyKey<HIST>;
+  using Child = ChildKey<HIST>;
   __shared__ Tables T;
   __shared__ uint64_t merge[RANK_WG / 32 * GN_MAX_LINES]; // each group's top 8
   load_tables(T, tables);
@@ -1324,12 +1332,9 @@ __global__ void __launch_bounds__(RANK_WG)
       continue;
     }
     uint64_t top = 0; // lane k: this group's k-th best child key so far (0: none)
-    uint32_t hself = 0, hlen = 0; // HIST: the parent's key index, and its game's positions so far (0: no history)
-    if constexpr (HIST) {
-      const gn_history h = (history.hist, ...)[p];
-      hself = h.self;
-      hlen = (h.first <= h.self && (size_t)h.self < (history.n_keys, ...)) ? h.self - h.first + 1 : 0u;
-    }
+    HistWindow hw = {0, 0}; // HIST: the parent's game so far (len 0: no history)
+    if constexpr (HIST) hw = hist_window((history, ...), p);
+    const uint32_t glen = hw.len ? hw.len + 1 : 0u; // the window as a grandchild counts it, a ply further on
     for (uint64_t cb = c0; cb < c1; cb += GROUPS) {
       const uint64_t c = cb + q;
       const bool have = c < c1;
@@ -1338,28 +1343,29 @@ __global__ void __launch_bounds__(RANK_WG)
       if (have) {
         g0 = goffsets[c], g1 = goffsets[c + 1];
         mv = moves[c];
-        check = (rec[c].flags & GN_FLAG_IN_CHECK) ? 1u : 0u;
+        check = (rec[c].flags & GN_FLAG_IN_CHECK) ? KEY_CHECK : 0u;
       }
-      const uint32_t none = g0 == g1 ? 1u : 0u;
+      const uint32_t none = g0 == g1 ? KEY_NO_MOVES : 0u;
       uint64_t best = 0; // the lane's best reply key
-      uint64_t key = 0;
-      if constexpr (HIST) {
+      uint32_t cdraw = 0; // HIST: the child is drawn by rule (uniform in the group)
+      if (HIST || __any(g0 < g1)) { // (HIST: every lane of the wave reaches the sum's shuffles)
         Board C;
-        uint32_t seen = 0; // the lane's share of the child's earlier occurrences
-        if (!none) {
-          unpack_fields(children[c], C);
-          const uint32_t lim = C.rule50 < hlen ? (uint32_t)C.rule50 : hlen;
-          if (C.rule50 >= 100) {
-            seen = 2;
-          } else if (lim >= 4) {
-            const uint64_t ck = position_key(C);
-            const uint64_t *const at = (history.keys, ...) + ((size_t)hself + 1);
-            for (uint32_t d = 4 + 2 * (uint32_t)lane; d <= lim; d += 2 * W) seen += *(at - d) == ck ? 1u : 0u;
+        if (!none) unpack_fields(children[c], C);
+        if constexpr (HIST) {
+          uint32_t seen = 0; // the lane's share of the child's earlier occurrences
+          if (!none) {
+            const uint32_t lim = C.rule50 < hw.len ? (uint32_t)C.rule50 : hw.len;
+            if (C.rule50 >= 100) {
+              seen = 2;
+            } else if (lim >= 4) {
+              const uint64_t ck = position_key(C);
+              const uint64_t *const at = (history.keys, ...) + ((size_t)hw.self + 1);
+              for (uint32_t d = 4 + 2 * (uint32_t)lane; d <= lim; d += 2 * W) seen += *(at - d) == ck ? 1u : 0u;
+            }
           }
+          cdraw = group_sum_w<W>(seen) >= 2 ? KEY_DRAW : 0u;
         }
-        const uint32_t cdraw = group_sum_w<W>(seen) >= 2 ? 1u : 0u;
         const uint64_t ge = cdraw ? g0 : g1; // a drawn child's replies are not consulted
-        const uint32_t glen = hlen ? hlen + 1 : 0u;
         for (uint64_t g = g0; __any(g < ge); g += W) {
           if (g + lane < ge) {
             const uint32_t gm = gmoves[g + lane];
@@ -1368,62 +1374,23 @@ __global__ void __launch_bounds__(RANK_WG)
             int32_t v1 = (r.flags & GN_FLAG_IN_CHECK) ? -VALUE_MATE : 0;
             uint32_t draw = 0;
             if (any_legal(G, T)) {
-              const uint32_t lim = G.rule50 < glen ? (uint32_t)G.rule50 : glen;
-              if (G.rule50 >= 100) {
-                draw = 1;
-              } else if (lim >= 4) {
-                const uint64_t gk = position_key(G);
-                uint32_t n2 = 0;
-                // four keys per trip, their loads independent of each other (a trip's tail re-reads
-                // d = 4, which lim >= 4 makes valid, and ignores it); the walk ends between trips
-                const uint64_t *const at = (history.keys, ...) + ((size_t)hself + 2);
-                for (uint32_t d = 4; d <= lim && n2 < 2; d += 8) {
-#pragma unroll
-                  for (uint32_t j = 0; j < 8; j += 2) {
-                    const bool in = d + j <= lim;
-                    const uint64_t k = *(at - (in ? d + j : 4u));
-                    n2 += in && k == gk ? 1u : 0u;
-                  }
-                }
-                draw = n2 >= 2 ? 1u : 0u;
-              }
+              if constexpr (HIST)
+                draw = drawn_by_rule(G, (history.keys, ...) + ((size_t)hw.self + 2), glen);
               v1 = draw ? 0 : r.final_v;
             }
-            const uint64_t k = (uint64_t)(uint32_t)(negate_ply(v1) + 32768) << 17 | (uint64_t)(0xFFFFu - gm) << 1 | draw;
+            const uint64_t k = Reply::pack(negate_ply(v1), 0xFFFFu - gm, draw);
             best = k > best ? k : best;
           }
         }
-        best = group_max_w<W>(best);
-        if (have) {
-          const bool leaf = none || cdraw; // the line ends at the child
-          const int32_t R = none ? (check ? -VALUE_MATE : 0) : cdraw ? 0 : (int32_t)(best >> 17) - 32768;
-          const uint32_t reply = leaf ? 0u : 0xFFFFu - (uint32_t)((best >> 1) & 0xFFFFu);
-          const uint32_t draw = none ? 0u : cdraw ? 1u : (uint32_t)(best & 1);
-          key = (uint64_t)(uint32_t)(negate_ply(R) + 32768) << 35 | (uint64_t)(0xFFFFu - mv) << 19 |
-                (uint64_t)reply << 3 | none << 2 | check << 1 | draw;
-        }
-      } else {
-        if (__any(g0 < g1)) {
-          Board C;
-          if (!none) unpack_fields(children[c], C);
-          for (uint64_t g = g0; __any(g < g1); g += W) {
-            if (g + lane < g1) {
-              const uint32_t gm = gmoves[g + lane];
-              const gn_eval r = grec[g + lane];
-              const Board G = do_move(C, (uint16_t)gm, nullptr);
-              const int32_t v1 = any_legal(G, T) ? r.final_v : (r.flags & GN_FLAG_IN_CHECK) ? -VALUE_MATE : 0;
-              const uint64_t k = (uint64_t)(uint32_t)(negate_ply(v1) + 32768) << 16 | (0xFFFFu - gm);
-              best = k > best ? k : best;
-            }
-          }
-        }
-        best = group_max_w<W>(best);
-        if (have) {
-          const int32_t R = none ? (check ? -VALUE_MATE : 0) : (int32_t)(best >> 16) - 32768;
-          const uint32_t reply = none ? 0u : 0xFFFFu - (uint32_t)(best & 0xFFFFu);
-          key = (uint64_t)(uint32_t)(negate_ply(R) + 32768) << 34 | (uint64_t)(0xFFFFu - mv) << 18 |
-                (uint64_t)reply << 2 | none << 1 | check;
-        }
+      }
+      best = group_max_w<W>(best);
+      uint64_t key = 0;
+      if (have) {
+        const bool leaf = none || cdraw; // the line ends at the child
+        const int32_t R = none ? (check ? -VALUE_MATE : 0) : cdraw ? 0 : Reply::value(best);
+        const uint32_t reply = leaf ? 0u : 0xFFFFu - Reply::payload(best);
+        const uint32_t draw = none ? 0u : cdraw ? KEY_DRAW : Reply::flags(best) ? KEY_DRAW : 0u;
+        key = Child::pack(negate_ply(R), (uint64_t)(0xFFFFu - mv) << 16 | reply, draw | none | check);
       }
       // sorted insert: lane k takes the key if it beats top[k] but not top[k - 1], the neighbour's
       // old value if it beats both
@@ -1440,18 +1407,13 @@ __global__ void __launch_bounds__(RANK_WG)
         rank_parent(parents[p], B, T); // (it has children: it passed the gate)
         gn_line2 l = {0, 0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE, 0};
         if (t2) {
-          uint32_t fl;
-          if constexpr (HIST)
-            fl = ((t2 & 2) ? GN_FLAG_IN_CHECK : 0u) | ((t2 & 4) ? GN_FLAG_NO_MOVES : 0u) | ((t2 & 1) ? GN_FLAG_DRAW : 0u);
-          else
-            fl = ((t2 & 1) ? GN_FLAG_IN_CHECK : 0u) | ((t2 & 2) ? GN_FLAG_NO_MOVES : 0u);
-          l.value = (int32_t)(t2 >> (32 + FB)) - 32768;
-          l.move = (uint16_t)(0xFFFFu - (uint32_t)((t2 >> (16 + FB)) & 0xFFFFu));
-          l.reply = (uint16_t)((t2 >> FB) & 0xFFFFu);
+          uint32_t fl = line_flags(Child::flags(t2));
+          l.value = Child::value(t2);
+          l.move = (uint16_t)(0xFFFFu - (Child::payload(t2) >> 16));
+          l.reply = (uint16_t)Child::payload(t2);
           l.score = rule_score(l.value, wdl_material(B, P), P, fl);
           l.flags = (uint16_t)fl;
-          if constexpr (HIST) l.plies = l.reply ? 2 : 1;
-          else l.plies = (t2 & 2) ? 1 : 2;
+          l.plies = l.reply ? 2 : 1;
         }
         lines[p * (size_t)K + threadIdx.x] = l;
       }
@@ -1461,34 +1423,20 @@ __global__ void __launch_bounds__(RANK_WG)
 }
 
 // (history: keys / n_keys / hist of the history variant, or nullptr: the plain kernel)
-template <class Parent, class Off>
-static hipError_t rank_lines2_t(const Parent *parents, size_t n, const Off *offsets, const gn_board *children,
-                                const gn_eval *rec, const uint16_t *moves, const Off *goffsets, const uint16_t *gmoves,
-                                const gn_eval *grec, const gn_eval_params &P, const Tables *tables, int K,
-                                gn_line2 *lines, hipStream_t s, const RankHistory *history = nullptr) {
-  if (!n) return hipSuccess;
-  const size_t blocks = std::min<size_t>(n, 8192);
-  if (history)
-    hipLaunchKernelGGL((rank_lines2_kernel<Parent, Off, RankHistory>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n,
-                       offsets, children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines, *history);
-  else
-    hipLaunchKernelGGL((rank_lines2_kernel<Parent, Off>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets,
-                       children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines);
-  return hipGetLastError();
-}
 hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t *offsets, const gn_board *children,
                               const gn_eval *rec, const uint16_t *moves, const uint32_t *goffsets,
                               const uint16_t *gmoves, const gn_eval *grec, const gn_eval_params &P,
-                              const Tables *tables, int K, gn_line2 *lines, hipStream_t s) {
-  return rank_lines2_t(parents, n, offsets, children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines, s);
-}
-hipError_t launch_rank_lines2_history(const gn_board *parents, size_t n, const uint32_t *offsets,
-                                      const gn_board *children, const gn_eval *rec, const uint16_t *moves,
-                                      const uint32_t *goffsets, const uint16_t *gmoves, const gn_eval *grec,
-                                      const gn_eval_params &P, const Tables *tables, int K, gn_line2 *lines,
-                                      const RankHistory &history, hipStream_t s) {
-  return rank_lines2_t(parents, n, offsets, children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines, s,
-                       &history);
+                              const Tables *tables, int K, gn_line2 *lines, const RankHistory *history,
+                              hipStream_t s) {
+  if (!n) return hipSuccess;
+  const size_t blocks = std::min<size_t>(n, 8192);
+  if (history)
+    hipLaunchKernelGGL((rank_lines2_kernel<gn_board, uint32_t, RankHistory>), dim3(blocks), dim3(RANK_WG), 0, s, parents,
+                       n, offsets, children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines, *history);
+  else
+    hipLaunchKernelGGL((rank_lines2_kernel<gn_board, uint32_t>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets,
+                       children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines);
+  return hipGetLastError();
 }
 
 hipError_t launch_classify(const gn_board *boards, size_t n, const gn_eval_params &P, uint8_t *need_small,

@@ -19,10 +19,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 FLAG_DRAW = 512
 
 
-def fixture_games():
-    """[(root_fen, uci_moves, skip)] of tests/golden/history_games.txt."""
+def fixture_games(name="history_games.txt"):
+    """[(root_fen, uci_moves, skip)] of tests/golden/<name>, a `root | moves | skip` line per game."""
     out = []
-    with open(os.path.join(HERE, "golden", "history_games.txt")) as f:
+    with open(os.path.join(HERE, "golden", name)) as f:
         for l in f:
             if not l.strip() or l.startswith("#"):
                 continue

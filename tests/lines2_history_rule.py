@@ -8,8 +8,6 @@ a child without a legal move is tests/lines2_rule.py's; otherwise (R(c), reply, 
 history_rule's depth-1 lines of c, taken as position k + 1 of the game fens[:k + 1] + [c] -- the
 grandchildren are counted against positions 0..=k, c itself having the other side to move.
 """
-import os
-
 import numpy as np
 
 import history_rule as H
@@ -23,14 +21,7 @@ EMPTY2 = R2.EMPTY2
 
 def fixture_games():
     """[(root_fen, uci_moves, skip)] of tests/golden/lines2_history_games.txt."""
-    out = []
-    with open(os.path.join(H.HERE, "golden", "lines2_history_games.txt")) as f:
-        for l in f:
-            if not l.strip() or l.startswith("#"):
-                continue
-            root, moves, skip = (x.strip() for x in l.split("|"))
-            out.append((root, moves, tuple(int(x) for x in skip.split())))
-    return out
+    return H.fixture_games("lines2_history_games.txt")
 
 
 def both_fixtures():
