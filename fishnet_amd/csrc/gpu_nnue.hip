@@ -280,7 +280,7 @@ struct ExpSet {
   // for the row stream (GN_OPT_EXPAND_PIPELINE 2) waits for it before it overwrites the set
   hipEvent_t scored = nullptr;
   DevBuf<uint32_t> perr;            // the planned expansion's error word ...
-  DevBuf<unsigned long long> pstat; // ... and pad count (each expansion of the pipeline its own)
+  DevBuf<unsigned long long> pstat; // ... and its counts: [0] pads, [1] zero-row entries (each expansion of the pipeline its own)
   // the plan's output the row stream reads (GN_OPT_EXPAND_PIPELINE 2: the next plan runs beside
   // this expansion's row stream)
   DevBuf<uint64_t> ent, eoff;
@@ -670,7 +670,7 @@ static int create(const uint8_t *big, size_t big_len, const uint8_t *small, size
     HIP_TRY(hipMalloc(&d.tables, sizeof(Tables)));
     for (ExpSet *x : {&d.cur, &d.alt}) { // the planned expansion's error word and pad count
       HIP_TRY(x->perr.ensure(1));
-      HIP_TRY(x->pstat.ensure(1));
+      HIP_TRY(x->pstat.ensure(2));
       HIP_TRY(hipEventCreateWithFlags(&x->scored, hipEventDisableTiming));
     }
     HIP_TRY(hipMemset(d.alt.perr.p, 0, sizeof(uint32_t)));
@@ -821,7 +821,7 @@ static int finalize_all(gn_ctx *ctx, Dev &d, const gn_board *parents, const gn_b
   const gn_eval_params &P = ctx->P;
   const ExpSet &x = d.cur;
   const SlicedOut sc = {&d.net[BIG], d.part.p, x.pinfo.p, (uint64_t)(n + total), (uint64_t)n},
-                  sp = {&d.net[BIG], d.part.p, x.pinfo.p, (uint64_t)(n + total), 0};
+                  sp = {&d.net[BIG], d.part.p, x.pinfo.p, (uint64_t)(n + total), 0, x.offsets.p};
   // children from their parents as write_children unpacked them
   const bool fast = x.child_moves != nullptr;
   HIP_TRY(launch_finalize(children, total, mode, x.eb.osm.p, x.eb.obg.p, x.eb.nsm.p, x.eb.nbg.p, P, d.tables, child_out,
@@ -870,7 +870,7 @@ static int generate_children(Dev &d, const gn_board *parents, size_t n, gn_board
   x.planned = o.deltas && o.plan;
   if (x.planned) { // a stale error bit of an earlier expansion must not fail this one
     HIP_TRY(hipMemsetAsync(x.perr.p, 0, sizeof(uint32_t), s));
-    HIP_TRY(hipMemsetAsync(x.pstat.p, 0, sizeof(unsigned long long), s));
+    HIP_TRY(hipMemsetAsync(x.pstat.p, 0, 2 * sizeof(unsigned long long), s));
   }
   if (x.chain_k > 1) HIP_TRY(d.nslot.ensure(n));
   HIP_TRY(x.counts.ensure(n + 1));
@@ -3194,6 +3194,7 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
     *value = (int64_t)(m * 1e6);
     return GN_OK;
   }
+  case GN_STAT_ZERO_ROW_ENTRIES: // ... and its entries on the zero row summed
   case GN_STAT_SCRATCH_PADS: { // read-only: the last planned expansion's GN_SCR_GAP no-op entries, summed
     int64_t sum = 0;
     for (auto &dp : ctx->devs) {
@@ -3202,9 +3203,9 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
       if (!d.cur.pstat.p) continue;
       HIP_TRY(hipSetDevice(d.id));
       if (d.done_on) HIP_TRY(hipEventSynchronize(d.done));
-      unsigned long long v = 0;
-      HIP_TRY(hipMemcpy(&v, d.cur.pstat.p, sizeof(v), hipMemcpyDeviceToHost));
-      sum += (int64_t)v;
+      unsigned long long v[2] = {0, 0};
+      HIP_TRY(hipMemcpy(v, d.cur.pstat.p, sizeof(v), hipMemcpyDeviceToHost));
+      sum += (int64_t)(option == GN_STAT_SCRATCH_PADS ? v[0] : v[1]);
     }
     *value = sum;
     return GN_OK;

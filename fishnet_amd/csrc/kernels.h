@@ -9,8 +9,9 @@
 // Row-ring depth of the planned expansion's stream (stream.hip: entries in flight per wave,
 // 4 or 8), and GN_SCR_GAP, the least distance in entries of one list from a king-cache store to
 // a later load of that row (the plan pads the lists to keep it and asserts it: error bit 2).
-// The ring issues an entry's row loads while consuming the entry GN_RING before it, and the
-// store happens while consuming its own entry, so at a distance >= GN_RING the load is issued
+// The store rides on its slot's last row entry (no entry of its own), so the distance counts
+// from that entry.  The ring issues an entry's row loads while consuming the entry GN_RING
+// before it, and the store happens while consuming its own entry, so at a distance >= GN_RING the load is issued
 // after the store, by the same lanes, to the same address.  One work-item's later load of an
 // address it stored needs no wait on this hardware: hipcc itself emits `global_store_dword`
 // directly followed by `global_load_dword` for C++ `p[i] = x; y = p[i ^ j];`
@@ -96,8 +97,17 @@ hipError_t launch_expand_net(const NetDevice &net, const gn_board *parents, size
 // parents) with <= 2 buckets among its evaluated slots.  e_end: list 0 / list 1 entries
 // of the block up to the end of this tile (padded to a multiple of 4); p_first: the
 // parent owning slot 0; first: the block-relative index of slot 0; meta[t]: bit 0
-// evaluated, bits 1-3 bucket, bit 4 a parent slot, bit 5 the slot's side to move;
+// evaluated (clear for a chained parent: it has no entries, its result is that of the child
+// that is its position), bits 1-3 bucket, bit 4 a parent slot, bit 5 the slot's side to move,
+// bit 6 (META_NEXT_PARENT) a child that is the next parent's position and whose result is that
+// parent's too (the whole-row streams store it to both; the sliced stream's finish: PINFO_ALIAS);
 // psq[t][side]: the slot's PSQT accumulators at its bucket (side 0: the perspective to move).
+constexpr uint32_t META_NEXT_PARENT = 1u << 6; // (TileDesc.meta)
+// pinfo[position].y of the column-sliced stream: < 0 not evaluated by the big net; else bits 0-2 the
+// bucket, and for a chained parent (its slot is not evaluated) PINFO_ALIAS and from PINFO_NS_SH the
+// child c of its predecessor P - 1 that is its position: its fc_0 sums are those of output index
+// np + offsets[P - 1] + c (relative, so that no batch size is too large for the field)
+constexpr int PINFO_ALIAS = 1 << 3, PINFO_NS_SH = 4;
 struct TileDesc {
   uint32_t e_end[2];
   uint32_t p_first;
@@ -137,7 +147,9 @@ struct PlanStreamArgs {
   // entries to its list's last store to scratch
   uint32_t *err = nullptr;
   unsigned long long *rows_out = nullptr; // += FT rows the stream gathers (bias, carry and king-cache rows included)
-  unsigned long long *pads_out = nullptr; // (optional) += no-op entries the plan inserted to keep GN_SCR_GAP
+  // (optional, 2 words) [0] += no-op entries the plan inserted to keep GN_SCR_GAP, [1] += entries put on
+  // the zero row (they move no row and add nothing)
+  unsigned long long *pads_out = nullptr;
   const uint32_t *order = nullptr;        // block order of the stream (block_order) or NULL
   // slices == 3 (L1 3072; part, pinfo non-null): the stream runs as three launches over 1,024
   // columns each (stream_eval_kernel<3072, 3>); part = GN_PART_SLICES x npos x 16 int32 fc_0
@@ -173,6 +185,7 @@ struct SlicedOut {
   const int32_t *part;
   const int2 *pinfo;
   uint64_t npos, qoff;
+  const uint64_t *offsets = nullptr; // the parents' launch (qoff 0): their child offsets, for PINFO_ALIAS
 };
 hipError_t launch_finalize(const gn_board *boards, size_t n, int mode, const int2 *out_small,
                            const int2 *out_big, const uint8_t *need_small, const uint8_t *need_big,

@@ -798,7 +798,7 @@ __global__ void finalize_kernel(const gn_board *__restrict__ boards, size_t n, i
                                 const uint32_t *__restrict__ owner, const uint16_t *__restrict__ moves,
                                 const Board *__restrict__ unpacked, int score, const uint64_t *__restrict__ counts,
                                 NetDevice bnet, const int32_t *__restrict__ part, const int2 *__restrict__ pinfo,
-                                uint64_t npos, uint64_t qoff) {
+                                uint64_t npos, uint64_t qoff, const uint64_t *__restrict__ poffsets) {
   __shared__ Tables T;
   // (part: the big net's outputs from the sliced stream's partial sums, slice_sums and
   // slice_finish_from -- their reads overlap this kernel's arithmetic instead of running as a
@@ -819,9 +819,19 @@ __global__ void finalize_kernel(const gn_board *__restrict__ boards, size_t n, i
     int4v sums[4];
     if (part) {
       info = pinfo[qoff + i];
+      uint64_t q = qoff + i;
+      if constexpr (!CHILD) {
+        // a chained parent (PINFO_ALIAS) has no sums of its own: those of its predecessor's child
+        // that is its position (the predecessor's offset is loaded beside pinfo: one round trip
+        // more than a child's, in the parents' launch only)
+        if (poffsets && i > 0) {
+          const uint64_t prev = poffsets[i - 1];
+          if (info.y >= 0 && (info.y & PINFO_ALIAS)) q = n + prev + (uint64_t)(info.y >> PINFO_NS_SH);
+        }
+      }
       // (mode FULL: only the positions the big net evaluates have sums -- the small net's read
       // none; mode BIG: every position, with no load in front of the sums')
-      if (mode == GN_MODE_BIG || (mode == GN_MODE_FULL && need_big[i])) slice_sums<GN_PART_SLICES>(part, npos, qoff + i, sums);
+      if (mode == GN_MODE_BIG || (mode == GN_MODE_FULL && need_big[i])) slice_sums<GN_PART_SLICES>(part, npos, q, sums);
     }
     auto big_out = [&](size_t j) -> int2 {
       return part && info.y >= 0 ? slice_finish_from(bnet, w1s, sums, info) : out_big[j];
@@ -1469,7 +1479,7 @@ hipError_t launch_finalize(const gn_board *boards, size_t n, int mode, const int
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, boards, n, mode, out_small, out_big, need_small,
                        need_big, P, tables, out, owner, moves, unpacked, score, counts, bnet,
                        sliced ? sliced->part : nullptr, sliced ? sliced->pinfo : nullptr, sliced ? sliced->npos : 0,
-                       sliced ? sliced->qoff : 0);
+                       sliced ? sliced->qoff : 0, sliced ? sliced->offsets : nullptr);
   };
   if (unpacked) launch(finalize_kernel<true>);
   else launch(finalize_kernel<false>);

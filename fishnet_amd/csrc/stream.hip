@@ -10,8 +10,10 @@
 //                       descriptor per 16-slot tile, in HBM.  Every decision that is
 //                       sequential inside a block is made here: the sibling cache, the
 //                       chain (parent p + 1 starts from parent p's child that is its
-//                       position: that child is evaluated last among its siblings and its
-//                       accumulators become the parent accumulators), the king cache
+//                       position: that child is evaluated last among its siblings, its
+//                       accumulators become the parent accumulators and its result is the
+//                       parent's -- the parent's own slot has no entries and is not
+//                       evaluated), the king cache
 //                       (Stockfish's AccumulatorCaches analog: a king-move refresh starts
 //                       from the accumulator the block last computed for that perspective
 //                       and king square, plus the placement difference), the list balance,
@@ -23,17 +25,18 @@
 //                       fc_1 / fc_2 and writes the outputs while the others stream on.
 //
 // Entry (u64, built by the plan kernel in the form the stream consumes):
-//   lo = the row's byte offset: an FT row, the zero row, or (bit 31, SCR) a row of the
-//        workgroup's scratch slot counted from its first row (2 + 64 h + ksq: the
-//        king-cache row of (h, ksq)); the workgroup adds its slot's offset (the FT table is
-//        < 2^28 bytes, so bit 31 is free)
-//   hi = [15:0] the 16-bit multiplier of the row (1 add, 0xFFFF subtract, 0 no-op; a
-//        store-only KST entry loads the zero row and has its target scratch row here),
+//   lo = the row's byte offset: an FT row, or (bit 31, SCR) a row of the workgroup's scratch
+//        slot counted from its first row (2 + 64 h + ksq: the king-cache row of (h, ksq)); the
+//        workgroup adds its slot's offset (the FT table is < 2^28 bytes, so bit 31 is free).
+//        [6:0] (zero in every row offset: rows are 128-B aligned) of a KST entry: 64 h + ksq of
+//        the king-cache row it stores to; the stream masks them off the offset and, at a KST
+//        entry only, reads them back from the list
+//   hi = [15:0] the 16-bit multiplier of the row (1 add, 0xFFFF subtract, 0 no-op),
 //        [17:16] the init before the entry (0 none, 1 ZERO: acc = row, 2 PACC: acc = parent
 //        - row, saved as the sibling base, 3 BASE: acc = base +- row), [18] LAST entry of its
 //        slot, [19] X (PAR_E or KST), [20] PAR_E (the slot's accumulator becomes pacc: a
-//        parent, or the child that is the next parent), [21] KST (store the slot's
-//        accumulator to the scratch row of this entry), [31:22] where the slot's features go
+//        parent, or the child that is the next parent), [21] KST (the slot's last row entry:
+//        store the slot's accumulator to the king-cache row in lo[6:0]), [31:22] where the slot's features go
 //        in the LDS tile: (slot in tile) * xu + (side) * hu, side 0 the perspective to move,
 //        in the stream's units (plan_kernel's xu / hu: 16-B units of the tile row XS and of
 //        the half LC / 2 for the column-sliced and 1024-wide streams; slot * 2 + side for
@@ -47,6 +50,9 @@
 // after the last store to scratch in its list (no-op entries are inserted when needed): the
 // load is then issued after the store, by the same lanes (kernels.h: why that suffices).
 // The ring runs across tiles.
+// Every entry moves a row: nothing is put on the all-zero row (GN_STAT_ZERO_ROW_ENTRIES counts
+// such entries: 0).  A king-cache hit without a difference is its load entry alone, LAST and KST:
+// it writes the row back as it is (the snapshot, the owner and the gap are kept as for any store).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -106,7 +112,7 @@ namespace ps {
 // (bits 16-17 of the header word: the kind field HZ / HP / HB below)
 constexpr uint32_t H_LAST = 1u << 18, H_X = 1u << 19,
                    H_PAR_E = H_X | 1u << 20, H_KST = H_X | 1u << 21, H_LDS_SH = 22;
-constexpr uint32_t L_SCR = 1u << 31; // (in lo)
+constexpr uint32_t L_SCR = 1u << 31, L_KT = 127u; // (in lo)
 // Each put site knows its entry's kind, so hi is a constant mask or'd with the slot / side
 // field (round 3 built a u32 entry and decoded it per put: ~25 VALU per entry in an
 // issue-bound kernel).
@@ -166,6 +172,7 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
   uint2 *E = reinterpret_cast<uint2 *>(ent + rbeg); // list 0 from E[0] up, list 1 from E[rtot - 1] down
   const uint32_t rtot = (uint32_t)(rend - rbeg); // the block's entry region (both lists; < 2^32)
   uint32_t bad = 0;                  // this lane's error bits (reported once per wave)
+  uint32_t zrow = 0;                 // this lane's entries put on the zero row (GN_STAT_ZERO_ROW_ENTRIES)
   // a block's tiles: <= ceil(slots / 16) + one bucket cut per parent (a parent's own slots hold
   // <= 2 buckets, so a tile is cut at most once per parent), hence this base
   TileDesc *T = tiles + us_b / 16 + (uint64_t)(K + 2) * blk;
@@ -182,6 +189,7 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
   auto put = [&](int g, uint32_t i, uint32_t lo, uint32_t hi) {
     // a scratch-row load must sit GN_SCR_GAP entries after the list's last scratch store
     if ((lo & L_SCR) && i < (g ? safe1 : safe0)) bad |= 4u;
+    zrow += lo == LO_ZERO; // (none by construction: every entry moves a row; counted per lane)
     const uint32_t ic = i < rlast ? i : rlast;
     const uint32_t x = g ? rlast - ic : ic;
     *reinterpret_cast<uint2 *>(reinterpret_cast<char *>(E) + (x << 3)) = make_uint2(lo, hi);
@@ -197,7 +205,7 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
   uint16_t(*prow)[32] = prow_s[w];
   uint32_t len0 = 0, len1 = 0, tile_k = 0, p_first = pbeg, u_fill = 0, t_first = 0, tile_bm = 0;
   unsigned long long pp_a = 0, pp_b = 0, pp_c = 0, pp_d = 0; // GN_PLAN_PROF: section cycles
-  int t_fill = 0, carried = 0;
+  int t_fill = 0, carried = 0, carried_ns = 0;
   uint32_t rows = 0, pads = 0, fpads = 0; // (per block: < 2^32)
   auto pad_to = [&](int g, uint32_t target) { // no-op entries up to target (lane-parallel, < 64)
     uint32_t &len = g ? len1 : len0;
@@ -243,6 +251,7 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
     if (lane == 0) {
       x.m = word(next_slot ? next_slot + p : any);
       x.nd = word(need_parent ? need_parent + p : any);
+      x.a = word(need_parent && p + 1 < pend ? need_parent + p + 1 : any); // (is the next parent evaluated?)
     } else if ((uint32_t)lane - 1 < nch) {
       const uint32_t *src = reinterpret_cast<const uint32_t *>(deltas + off + lane - 1);
       x.a = src[0], x.b = src[1], x.c = src[2], x.d = src[3], x.m = src[4];
@@ -268,6 +277,8 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
     const uint32_t f0 =
         (need_parent ? byte_of((uint32_t)__builtin_amdgcn_readlane((int)xd.nd, 0), need_parent + p) : 1u) |
         (next_slot ? byte_of((uint32_t)__builtin_amdgcn_readlane((int)xd.m, 0), next_slot + p) : 255u) << 8;
+    // (p + 1 < pend) the next parent is evaluated: the child that is its position then carries its result
+    const bool next_wanted = !need_parent || byte_of((uint32_t)__builtin_amdgcn_readlane((int)xd.a, 0), need_parent + p + 1) != 0;
     const bool pre = total <= 64; // the parent's slots are one pass, its inputs prefetched
     const int P = wave_features(pb, prow[0], prow[1], lane);
     ps::wave_sync();
@@ -277,7 +288,7 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
       for (int q = lane; q < total; q += 64)
         want |= q == 0 ? (int)(f0 & 0xFF) : (need_child ? need_child[off + q - 1] : 1);
     const bool live = __ballot(want) != 0 && P != 0;
-    const int have = live ? carried : 0;
+    const int have = live ? carried : 0, have_ns = carried_ns; // (have: have_ns = its predecessor's child that it is)
     carried = 0;
     const int stm = pb.stm_ep >> 7;
     const int bp = P ? (P - 1) / 4 : 0, b2 = P >= 2 ? (P - 2) / 4 : bp;
@@ -293,7 +304,7 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
         if (nd) nxq = ns + 1;
       }
     }
-    carried = nxq > 0;
+    carried = nxq > 0, carried_ns = nxq - 1;
     // the child that is the next parent is evaluated last among its siblings (its accumulators
     // then become the parent accumulators the next parent starts from): processing position q
     // (1..nch) takes child ci(q), the others keep their order
@@ -494,8 +505,8 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
       }
       int d0 = 0, d1 = 0;
       if (kinds == 15) {
-        d0 = have ? 1 : pnd[0] >= 0 ? pnd[0] + 2 : P + 1 + (pst[0] ? 1 : 0);
-        d1 = have ? 1 : pnd[1] >= 0 ? pnd[1] + 2 : P + 1 + (pst[1] ? 1 : 0);
+        d0 = have ? 0 : pnd[0] >= 0 ? pnd[0] + 1 : P + 1;
+        d1 = have ? 0 : pnd[1] >= 0 ? pnd[1] + 1 : P + 1;
       }
       else {
         if ((kinds & 3) == 1) d0 = n0 - (hit0 ? 1 : 0);
@@ -523,12 +534,16 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
         }
         // the column-sliced stream's finish takes each evaluated position's PSQT value and
         // bucket from here (Network::evaluate's psqt term, a15 / a17), by output index
+        // (a chained parent, PINFO_ALIAS: its sums are those of the child that is its position)
         if (pinfo && vld)
           pinfo[q == 0 ? (uint64_t)p : (uint64_t)np + off + (uint64_t)child_of(q)] =
-              make_int2((int32_t)((uint32_t)sv[0] - (uint32_t)sv[1]) / 2, bk);
+              make_int2((int32_t)((uint32_t)sv[0] - (uint32_t)sv[1]) / 2, bk | (q == 0 && have ? PINFO_ALIAS | have_ns << PINFO_NS_SH : 0));
       }
       if (in) {
-        *tf(tk0 + tix, offsetof(TileDesc, meta) + t) = (char)((live && vld ? 1 : 0) | bk << 1 | (q == 0 ? 16 : 0) | cst << 5);
+        // (a chained parent's slot is not evaluated: the child that is its position, bit 6, is)
+        *tf(tk0 + tix, offsetof(TileDesc, meta) + t) =
+            (char)((live && vld && !(q == 0 && have) ? 1 : 0) | bk << 1 | (q == 0 ? 16 : 0) | cst << 5 |
+                   (nx && next_wanted ? META_NEXT_PARENT : 0));
         *reinterpret_cast<int16_t *>(tf(tk0 + tix, offsetof(TileDesc, adj) + 2 * t)) =
             (int16_t)(q == 0 ? 0 : child_of(q) - (q - 1));
       }
@@ -541,13 +556,15 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
       // stores are still the ones before it (put() checks the distance)
       if (live && q0 == 0 && lane == 0) {
         const uint32_t t0w = hs(tf0, stm != 0, xu, hu), t1w = hs(tf0, stm != 1, xu, hu);
-        if (have) { // the parent is its predecessor's last child: pacc, one entry per list
-          put(0, len0, LO_ZERO, M_SUB | HP | t0w | H_PAR_E | H_LAST);
-          put(1, len1, LO_ZERO, M_SUB | HP | t1w | H_PAR_E | H_LAST);
-        } else { // bias entry or the cache row; the rest follows (lane = square / row)
-          put(0, len0, pnd[0] >= 0 ? lo_scr(2 + pkq[0]) : LO_BIAS, M_ADD | HZ | t0w | H_PAR_E);
-          put(1, len1, pnd[1] >= 0 ? lo_scr(2 + 64 + pkq[1]) : LO_BIAS,
-              M_ADD | HZ | t1w | H_PAR_E);
+        // (a chained parent has no entries: its accumulators are pacc, left by its predecessor's last
+        // child, whose result is its own)
+        if (!have) { // bias entry or the cache row; the rest follows (lane = square / row)
+          // (a cache row without a difference is the parent's accumulator: the slot's only entry,
+          // which then carries the store as any last entry does)
+          put(0, len0, pnd[0] >= 0 ? lo_scr(2 + pkq[0]) | (pnd[0] == 0 ? (uint32_t)pkq[0] : 0u) : LO_BIAS,
+              M_ADD | HZ | t0w | H_PAR_E | (pnd[0] == 0 ? H_LAST | H_KST : 0u));
+          put(1, len1, pnd[1] >= 0 ? lo_scr(2 + 64 + pkq[1]) | (pnd[1] == 0 ? (uint32_t)(64 + pkq[1]) : 0u) : LO_BIAS,
+              M_ADD | HZ | t1w | H_PAR_E | (pnd[1] == 0 ? H_LAST | H_KST : 0u));
         }
       }
       if (live && q0 == 0 && !have) {
@@ -555,21 +572,27 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
 #pragma unroll 1
         for (int hh = 0; hh < 2; ++hh) {
           const uint32_t tp = hs(tf0, stm != hh, xu, hu), b0 = (hh ? len1 : len0) + 1;
-          const uint32_t kr = (uint32_t)(2 + 64 * hh + pkq[hh]); // the cache row (scratch row index)
+          // the slot's last row entry stores the accumulator to the cache row (lo[6:0]: 64 hh + ksq)
+          const uint32_t kt7 = (uint32_t)(64 * hh + pkq[hh]), KL = H_KST | H_LAST | H_PAR_E;
           if (pnd[hh] >= 0) { // the cache row's differences: removed pieces, then added ones
             int spc;
             uint64_t bs, ba;
             cache_diff(64 * hh + pkq[hh], ppc, spc, bs, ba);
-            if ((bs >> lane) & 1)
-              put(hh, b0 + popcnt(bs & lt2), (uint32_t)feature_index(hh, lane, spc, pkq[hh]) * RS, M_SUB | tp | H_PAR_E);
-            if ((ba >> lane) & 1)
-              put(hh, b0 + popcnt(bs) + popcnt(ba & lt2), (uint32_t)feature_index(hh, lane, ppc, pkq[hh]) * RS,
-                  M_ADD | tp | H_PAR_E);
-            if (lane == 0) put(hh, b0 + pnd[hh], LO_ZERO, kr | tp | H_KST | H_LAST | H_PAR_E);
-          } else {
-            if (lane < P)
-              put(hh, b0 + lane, ft_row(prow[hh][lane]) * RS, M_ADD | tp | H_PAR_E | (lane == P - 1 && !pst[hh] ? H_LAST : 0u));
-            if (pst[hh] && lane == 0) put(hh, b0 + P, LO_ZERO, kr | tp | H_KST | H_LAST | H_PAR_E);
+            const uint32_t ie = b0 + (uint32_t)pnd[hh] - 1; // the last of them
+            if ((bs >> lane) & 1) {
+              const uint32_t i = b0 + popcnt(bs & lt2);
+              put(hh, i, (uint32_t)feature_index(hh, lane, spc, pkq[hh]) * RS | (i == ie ? kt7 : 0u),
+                  M_SUB | tp | (i == ie ? KL : H_PAR_E));
+            }
+            if ((ba >> lane) & 1) {
+              const uint32_t i = b0 + popcnt(bs) + popcnt(ba & lt2);
+              put(hh, i, (uint32_t)feature_index(hh, lane, ppc, pkq[hh]) * RS | (i == ie ? kt7 : 0u),
+                  M_ADD | tp | (i == ie ? KL : H_PAR_E));
+            }
+          } else if (lane < P) {
+            const bool le = lane == P - 1;
+            put(hh, b0 + lane, ft_row(prow[hh][lane]) * RS | (le && pst[hh] ? kt7 : 0u),
+                M_ADD | tp | (le ? (pst[hh] ? KL : H_LAST | H_PAR_E) : H_PAR_E));
           }
           if (pnd[hh] >= 0 || pst[hh]) { // list hh stored the row: its snapshot and state
             uint32_t x = (uint32_t)ppc << (4 * (lane & 7));
@@ -578,8 +601,9 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
             if ((lane & 7) == 0) ksnap[w][kci][lane >> 3] = x;
             kstate_set(hh, pkq[hh], 1 | hh << 1);
             uint32_t &sf = hh ? safe1 : safe0;
-            sf = b0 + (uint32_t)(pnd[hh] >= 0 ? pnd[hh] : P) + GN_SCR_GAP; // the store's index + the gap
+            sf = b0 + (uint32_t)(pnd[hh] >= 0 ? pnd[hh] : P) - 1 + GN_SCR_GAP; // the storing entry's index + the gap
           }
+          if (pnd[hh] >= 0 || pst[hh]) ++rows; // (the cache row counts as it did when its store was an entry)
         }
         ps::wave_sync();
       }
@@ -655,21 +679,24 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
         const uint32_t base = g ? len1 : len0;
         const uint32_t L = H_LAST | (nxl ? H_PAR_E : 0u);
         const uint32_t kr = (uint32_t)(2 + kci); // the cache row (scratch row index)
+        // the slot's last row entry stores the accumulator to the cache row (lo[6:0]: 64 hh + ksq);
+        // a hit without a difference is its load entry alone, which then carries the store
+        const uint32_t KL = L | (kuse ? H_KST : 0u), k7 = kuse ? (uint32_t)kci : 0u;
         int ne;
         if (hit) {
           const int nd = popcnt(bs) + popcnt(ba);
-          ne = nd + 2;
+          ne = nd + 1;
           const int ps = 1 + popcnt(bs & lt), pa = 1 + popcnt(bs) + popcnt(ba & lt);
-          if (lane == 0) put(g, base, lo_scr(kr), M_ADD | HZ | tw);
-          if ((bs >> lane) & 1) put(g, base + ps, (uint32_t)feature_index(hh, lane, spc, kt) * RS, M_SUB | tw);
-          if ((ba >> lane) & 1) put(g, base + pa, (uint32_t)row * RS, M_ADD | tw);
-          if (lane == 0) put(g, base + ne - 1, LO_ZERO, kr | tw | H_KST | L);
+          if (lane == 0) put(g, base, lo_scr(kr) | (nd == 0 ? k7 : 0u), M_ADD | HZ | tw | (nd == 0 ? KL : 0u));
+          if ((bs >> lane) & 1)
+            put(g, base + ps, (uint32_t)feature_index(hh, lane, spc, kt) * RS | (ps == nd ? k7 : 0u), M_SUB | tw | (ps == nd ? KL : 0u));
+          if ((ba >> lane) & 1) put(g, base + pa, (uint32_t)row * RS | (pa == nd ? k7 : 0u), M_ADD | tw | (pa == nd ? KL : 0u));
           rows += (uint32_t)(nd + 1);
         } else {
-          ne = cn + 1 + (kuse ? 1 : 0);
+          ne = cn + 1;
           if (lane == 0) put(g, base, LO_BIAS, M_ADD | HZ | tw);
-          if (row >= 0 && pos < cn) put(g, base + 1 + pos, (uint32_t)row * RS, M_ADD | tw | (!kuse && pos == cn - 1 ? L : 0u));
-          if (kuse && lane == 0) put(g, base + ne - 1, LO_ZERO, kr | tw | H_KST | L);
+          if (row >= 0 && pos < cn)
+            put(g, base + 1 + pos, (uint32_t)row * RS | (pos == cn - 1 ? k7 : 0u), M_ADD | tw | (pos == cn - 1 ? KL : 0u));
           rows += (uint32_t)(cn + 1);
         }
         if (kuse) { // the cache row now holds this child's accumulator, stored by list g
@@ -747,6 +774,7 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
   // error bits: 1 entries beyond the block's region (eoff under-counted), 4 a scratch-row load
   // closer than GN_SCR_GAP to its list's last scratch store; neither can happen by construction
   const uint32_t werr = __ballot(bad & 1u) ? 1u : 0u, werr4 = __ballot(bad & 4u) ? 4u : 0u;
+  if (pads_out && __ballot(zrow != 0)) atomicAdd(pads_out + 1, (unsigned long long)zrow); // (per lane: never in practice)
   if (lane == 0) {
     if ((uint64_t)len0 + len1 > (uint64_t)(rtot - ENT_SPARE) || werr) atomicOr(err, 1u);
     if (werr4) atomicOr(err, 4u);
@@ -861,7 +889,7 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
 #endif
   // ---- scratch slot (carry + king-cache rows) from this XCD's pool: never waits on another
   // workgroup; the pool (POOL_PER_XCD slots) outnumbers the workgroups an XCD holds
-  uint32_t scr = 0, my_slot = 0;
+  uint32_t scr = 0, slot1 = 0; // slot1: the slot + 1 (0: none; the one register the kernel's end tests)
   if (use_scr) {
     if (tid == 0) {
       uint32_t x;
@@ -887,8 +915,8 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
       sslot = (uint32_t)got;
     }
     __syncthreads();
-    my_slot = sslot;
-    scr = (uint32_t)FT_ROWS + (uint32_t)SCR_ROWS * my_slot;
+    slot1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)sslot) + 1u;
+    scr = (uint32_t)FT_ROWS + (uint32_t)SCR_ROWS * (slot1 - 1u);
   }
 
   // the stream and the tile loop are compiled once per perspective group (HU = hu): the
@@ -946,10 +974,12 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
   typedef uint32_t u8e __attribute__((ext_vector_type(2 * GV), aligned(8)));
   typedef const __attribute__((address_space(4))) u8e cu8e;
   typedef const __attribute__((address_space(4))) uint64_t cu64;
-  cu64 *EL = (cu64 *)(HU ? ent + rend : ent + rbeg);
-  // entries i .. i + GV - 1 of this group's list by one s_load_dwordx8 / x16 (list 1 is stored
-  // downward: its entries arrive reversed, see elo / ehi)
-  auto group = [&](uint32_t i) -> u8e { return *(cu8e *)(HU ? EL - GV - i : EL + i); };
+  cu64 *EL = (cu64 *)(ent + rbeg);
+  // entry i of this group's list is word eix(i) of the block's region: list 1 is stored downward
+  // from the region's end (elim + ENT_SPARE entries, as the plan's rtot)
+  auto eix = [&](uint32_t i) -> uint32_t { return HU ? elim + (ENT_SPARE - 1) - i : i; };
+  // entries i .. i + GV - 1 by one s_load_dwordx8 / x16 (list 1's arrive reversed, see elo / ehi)
+  auto group = [&](uint32_t i) -> u8e { return *(cu8e *)(EL + eix(HU ? i + GV - 1 : i)); };
   auto elo = [&](const u8e v, int r) -> uint32_t { return HU ? v[2 * (GV - 1 - r)] : v[2 * r]; };
   auto ehi = [&](const u8e v, int r) -> uint32_t { return HU ? v[2 * (GV - 1 - r) + 1] : v[2 * r + 1]; };
   int tl0 = tid;
@@ -963,9 +993,11 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
                    (int)(((size_t)ZERO_ROW + 1) * RS), 0x00020000};
   // this slot's rows from the first scratch row, less the SCR bit the entry carries in lo
   const uint32_t scr_off = (scr - (uint32_t)FT_ROWS) * RS - L_SCR;
+  // (lo[6:0] of a KST entry: the king-cache row it stores to, below the rows' alignment)
+  static_assert(RS % (L_KT + 1) == 0, "a row offset leaves lo[6:0] free");
   auto offset = [&](uint32_t lo, uint32_t h) -> uint32_t {
     (void)h;
-    return lo + ((uint32_t)((int32_t)lo >> 31) & scr_off);
+    return (lo & ~L_KT) + ((uint32_t)((int32_t)lo >> 31) & scr_off);
   };
   auto issue = [&](int r, uint32_t lo, uint32_t h) {
     eh[r] = h;
@@ -989,7 +1021,7 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
     asm volatile("s_waitcnt vmcnt(%2)" : "+v"(rlo[r]), "+v"(rhi[r]) : "n"(RWAIT));
   };
   uint32_t A[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  auto consume = [&](int r) {
+  auto consume = [&](int r, uint32_t ei) { // ring slot r holds entry ei of the list
     ring_wait(r);
     const uint32_t h = eh[r];
     // every entry is one 16-bit multiply-add per dword, acc = src + sg * row, its multiplier
@@ -1074,7 +1106,18 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
       }
       if (h & (H_KST & ~H_X)) { // the accumulator to its king-cache row
         asm volatile("");
-        const uint32_t so = (scr + (h & 0xFFFFu)) * RS;
+        // its row (2 + 64 h + ksq) is in the entry's lo[6:0], which the ring did not keep: one
+        // scalar load of the entry's own word (the group load brought its line into the scalar
+        // cache a revolution or two ago), on this path only
+        // (the region's base + a 32-bit byte offset, the loaded word in the offset's register:
+        // the path takes one scalar register)
+        uint32_t kl = eix(ei) << 3;
+        asm volatile("s_load_dword %0, %1, %0\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "+s"(kl)
+                     : "s"(EL));
+        // (from scr_off, which the ring keeps live anyway: (scr + 2 + row) * RS)
+        const uint32_t so = scr_off + (L_SCR + ((uint32_t)FT_ROWS + 2u) * RS) + (kl & L_KT) * RS;
         // cache policy of the king-cache stores: default.  The same-address store -> load order
         // the reload relies on is pinned for default-policy stores only (kernels.h); non-temporal
         // (" nt") measured 205.5 -> 205.0 ms, within noise
@@ -1187,7 +1230,7 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
         if (r0 != 0) {
 #pragma unroll
           for (int r = 1; r < RD; ++r)
-            if (r0 <= (uint32_t)r && pos < e_end) consume(r), issue(r, elo(gw, r), ehi(gw, r)), ++pos;
+            if (r0 <= (uint32_t)r && pos < e_end) consume(r, pos), issue(r, elo(gw, r), ehi(gw, r)), ++pos;
         }
       }
 #pragma unroll 1
@@ -1196,18 +1239,18 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
         gw = gp;
         gp = group(pos + 2 * RD);
 #pragma unroll
-        for (int r = 0; r < RD; ++r) consume(r), issue(r, elo(gw, r), ehi(gw, r));
+        for (int r = 0; r < RD; ++r) consume(r, pos + r), issue(r, elo(gw, r), ehi(gw, r));
         pos += RD;
       }
       if (pos < e_end) {
         __builtin_amdgcn_s_waitcnt(0xC07F);
         gw = gp;
         gp = group(pos + 2 * RD);
-        consume(0), issue(0, elo(gw, 0), ehi(gw, 0));
+        consume(0, pos), issue(0, elo(gw, 0), ehi(gw, 0));
         ++pos;
 #pragma unroll
         for (int r = 1; r < RD - 1; ++r)
-          if (pos < e_end) consume(r), issue(r, elo(gw, r), ehi(gw, r)), ++pos;
+          if (pos < e_end) consume(r, pos), issue(r, elo(gw, r), ehi(gw, r)), ++pos;
       }
     } else {
 #pragma unroll 1
@@ -1220,12 +1263,12 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
           __builtin_amdgcn_s_waitcnt(0xC07F);
           gw = gp;
           gp = group(pos + 2 * RD);
-          consume(0), issue(0, elo(gw, 0), ehi(gw, 0));
+          consume(0, pos), issue(0, elo(gw, 0), ehi(gw, 0));
           ++pos;
         }
 #pragma unroll
         for (int r = 1; r < RD; ++r)
-          if (r0 <= (uint32_t)r && pos < e_end) consume(r), issue(r, elo(gw, r), ehi(gw, r)), ++pos;
+          if (r0 <= (uint32_t)r && pos < e_end) consume(r, pos), issue(r, elo(gw, r), ehi(gw, r)), ++pos;
       }
     }
     asm volatile("" ::: "memory");
@@ -1395,8 +1438,10 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
               const int32_t psqt = (int32_t)((uint32_t)pq[i].x - (uint32_t)pq[i].y) / 2;
               const int2 val = make_int2(psqt / 16, positional / 16);
               const uint32_t P = p_first + (uint32_t)__builtin_popcount(pm & ((2u << pos) - 1)) - (pm & 1);
-              if ((pm >> pos) & 1) out_parent[P] = val;
-              else out_child[u0 + pos - P - 1 + adj[i]] = val;
+              // (a child that is the next parent's position, bit 6: the chained parent's output too)
+              const bool par = (pm >> pos) & 1;
+              if (!par) out_child[u0 + pos - P - 1 + adj[i]] = val;
+              if (par || (m & META_NEXT_PARENT)) out_parent[P + (par ? 0u : 1u)] = val;
             }
           }
         }
@@ -1416,7 +1461,8 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
   };
   if (hu) run_group(std::integral_constant<int, 1>{});
   else run_group(std::integral_constant<int, 0>{});
-  if (use_scr) { // every wave's stores are complete before the slot goes back to the pool
+  if (slot1) { // every wave's stores are complete before the slot goes back to the pool
+    const uint32_t my_slot = slot1 - 1u;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0)

@@ -154,6 +154,12 @@ extern "C" {
 #define GN_STAT_FINISH_NS 104         /* ... and the column-sliced stream's layer-stack
                                          finish as a step of its own (~0: finalize computes
                                          each output itself, as with one launch)           */
+#define GN_STAT_ZERO_ROW_ENTRIES 105  /* list entries the last planned expansion put on the
+                                         all-zero row (per device, summed): entries that
+                                         move no feature row and add nothing.  0: a chained
+                                         parent takes the result of the child that is its
+                                         position, and a king-cache store rides on its
+                                         slot's last row entry (both were such entries)  */
 #define GN_STAT_SCRATCH_PADS 103      /* no-op entries the last planned expansion inserted
                                          (per device, summed) so that every king-cache load
                                          sits >= ring depth (4) list entries after the
