@@ -179,10 +179,19 @@ static int parse_net(const uint8_t *data, size_t len, HostNet &h) {
 }
 
 // ----------------------------------------------------------- context ------
+// Device resources are owned by the members that name them: each of the types below frees what it
+// holds in its destructor and is move-only, so a context is torn down by its destructors (~Dev
+// makes the device current and idle first) and a timing call's events go on every way out.
 template <class T>
 struct DevBuf {
   T *p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept { return std::swap(p, o.p), std::swap(cap, o.cap), *this; }
+  ~DevBuf() { release(); }
   hipError_t ensure(size_t n) {
     if (n <= cap) return hipSuccess;
     const size_t want = std::max(n, cap + cap / 2);
@@ -195,9 +204,41 @@ struct DevBuf {
     if (e == hipSuccess) cap = want;
     return e;
   }
-  void release() {
+  void release() { // (also mid-life: memory given back when an allocation beside it failed)
     if (p) (void)hipFree(p);
     p = nullptr, cap = 0;
+  }
+};
+// A HIP handle (it converts to the handle wherever one is taken; h is set by the hip*Create call).
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+  H h = nullptr;
+  Handle() = default;
+  Handle(const Handle &) = delete;
+  Handle &operator=(const Handle &) = delete;
+  Handle(Handle &&o) noexcept : h(o.h) { o.h = nullptr; }
+  Handle &operator=(Handle &&o) noexcept { return std::swap(h, o.h), *this; }
+  ~Handle() {
+    if (h) (void)Destroy(h);
+  }
+  operator H() const { return h; }
+};
+static hipError_t idle_then_destroy(hipStream_t s) {
+  (void)hipStreamSynchronize(s);
+  return hipStreamDestroy(s);
+}
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, idle_then_destroy>;
+// The events of one timing call: make() creates one for each handle it is given.
+struct Events {
+  std::vector<Event> v;
+  hipError_t make(std::initializer_list<hipEvent_t *> es) {
+    for (hipEvent_t *e : es) {
+      v.emplace_back();
+      if (const hipError_t r = hipEventCreate(&v.back().h); r != hipSuccess) return r;
+      *e = v.back();
+    }
+    return hipSuccess;
   }
 };
 
@@ -205,7 +246,6 @@ struct DevBuf {
 struct EvalBufs {
   DevBuf<int2> osm, obg;
   DevBuf<uint8_t> nsm, nbg;
-  void release() { osm.release(), obg.release(), nsm.release(), nbg.release(); }
 };
 
 // ---- the drop-in's small batches ------------------------------------
@@ -227,9 +267,9 @@ struct FastBatch {
   size_t nb = 0, c1 = 0, c2 = 0;
   int mode = -1;
   uint64_t gen = 0;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  hipEvent_t done = nullptr; // recorded behind each launch (the caller waits for it without d.mu)
+  Handle<hipGraph_t, hipGraphDestroy> graph;
+  Handle<hipGraphExec_t, hipGraphExecDestroy> exec;
+  Event done; // recorded behind each launch (the caller waits for it without d.mu)
   bool busy = false;         // a launch of this instance is in flight (d.mu)
   gn_board *h_in = nullptr; // pinned: nb boards
   gn_eval *h_out = nullptr; // pinned: one record holding the overflow flag, then nb records
@@ -244,14 +284,8 @@ struct FastBatch {
   DevBuf<int32_t> sv1, sv2;
   EvalBufs eb;
   ~FastBatch() {
-    if (done) (void)hipEventDestroy(done);
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
     if (h_in) (void)hipHostFree(h_in);
     if (h_out) (void)hipHostFree(h_out);
-    all.release(), rec.release();
-    off0.release(), off1.release(), m1.release(), m2.release(), sv1.release(), sv2.release();
-    eb.release();
   }
 };
 
@@ -274,11 +308,12 @@ struct ExpSet {
   int slices = 1;       // this expansion's stream: column slices (3) or whole rows (1)
   bool planned = false; // this expansion runs the planned kernels (stream.hip; perr is meaningful)
   uint64_t etot = 0;    // eoff[n] of this expansion
-  void *scan_tmp = nullptr, *sort_tmp = nullptr; // (the two streams' scans / sorts run at once)
-  size_t scan_bytes = 0, sort_bytes = 0;
+  // the scans' / sorts' scratch, which they grow themselves (cap in bytes; the two streams' scans /
+  // sorts run at once)
+  DevBuf<void> scan_tmp, sort_tmp;
   // recorded on the device stream behind this set's last score rule: a front that does not wait
   // for the row stream (GN_OPT_EXPAND_PIPELINE 2) waits for it before it overwrites the set
-  hipEvent_t scored = nullptr;
+  Event scored;
   DevBuf<uint32_t> perr;            // the planned expansion's error word ...
   DevBuf<unsigned long long> pstat; // ... and its counts: [0] pads, [1] zero-row entries (each expansion of the pipeline its own)
   // the plan's output the row stream reads (GN_OPT_EXPAND_PIPELINE 2: the next plan runs beside
@@ -286,27 +321,15 @@ struct ExpSet {
   DevBuf<uint64_t> ent, eoff;
   DevBuf<TileDesc> tiles;
   DevBuf<uint32_t> btiles, border;
-  void release() {
-    perr.release(), pstat.release();
-    ent.release(), eoff.release(), tiles.release(), btiles.release(), border.release();
-    counts.release(), offsets.release(), owner.release(), unpacked.release(), moves_tmp.release();
-    pinfo.release(), p_osm.release(), p_obg.release(), p_nsm.release(), p_nbg.release(), eb.release();
-    children.release();
-    if (scan_tmp) (void)hipFree(scan_tmp);
-    if (sort_tmp) (void)hipFree(sort_tmp);
-    scan_tmp = sort_tmp = nullptr, scan_bytes = sort_bytes = 0;
-    if (scored) (void)hipEventDestroy(scored);
-    scored = nullptr;
-  }
 };
 
 struct Dev {
   int id = 0;
-  hipStream_t stream = nullptr;
-  void *net_mem[2] = {nullptr, nullptr};
+  Stream stream; // (the first member: destroyed after everything queued on it is freed)
+  DevBuf<uint8_t> net_mem[2];
   NetDevice net[2] = {};
   bool has[2] = {false, false};
-  Tables *tables = nullptr;
+  DevBuf<Tables> tables;
   // The current expansion's buffers (generate_children, expand_evaluate, resolve_scores and
   // evaluate_on work in cur) and the other set, in which the pipeline's next front runs.  What an
   // expansion's back half reads belongs in ExpSet.  Here stay only: what the front half that wrote
@@ -332,7 +355,7 @@ struct Dev {
   // Cross-stream ordering of the library-owned scratch above: every launch sequence
   // waits for the previous one when it runs on another stream (gn_*_device take a
   // caller stream and return while their kernels are still queued).
-  hipEvent_t done = nullptr;
+  Event done;
   hipStream_t done_on = nullptr;
   float plan_ms = 0, stream_ms = 0, finish_ms = 0; // the last timed planned expansion (GN_STAT_PLAN_NS /
                                                     // _STREAM_NS / _FINISH_NS)
@@ -345,20 +368,16 @@ struct Dev {
     DevBuf<uint16_t> moves;
     DevBuf<gn_eval> ce;
     DevBuf<int32_t> sv;
-    void release() {
-      sel.release(), pos.release(), counts.release(), offsets.release(), idx.release(), owner.release();
-      boards.release(), children.release(), moves.release(), ce.release(), sv.release();
-    }
   } lv[2];
   // the host-buffer calls' pipeline (expand_pipelined): per chunk slot the parent / child
   // records and child moves a drain thread downloads on the copy stream while the next chunk
   // computes; the lichess replay's inputs and outputs (replay_games_kernel)
-  hipStream_t copy = nullptr;
-  hipEvent_t cev[2] = {nullptr, nullptr};
+  Stream copy;
+  Event cev[2];
   DevBuf<gn_eval> po2[2], co2[2];
   DevBuf<gn_child> cc2[2]; // co2 packed as the host's 12-B child records (ABI v4)
   DevBuf<gn_line> ln2[2];  // or ranked: the chunk's lines (gn_evaluate_games_lines)
-  hipEvent_t rev[2] = {nullptr, nullptr}; // around a chunk's rank_children_kernel (GN_STAT_RANK_NS)
+  Event rev[2]; // around a chunk's rank_children_kernel (GN_STAT_RANK_NS)
   DevBuf<uint16_t> mv2[2];
   // gn_evaluate_lines2: one chunk's depth-2 expansion (gn_expand2_device's outputs, library-owned
   // and grown to the chunk's exact counts) and its lines
@@ -368,10 +387,6 @@ struct Dev {
     DevBuf<gn_board> ch;
     DevBuf<uint16_t> mv, gmv;
     DevBuf<gn_line2> ln;
-    void release() {
-      po.release(), co.release(), gco.release(), off.release(), goff.release(), ch.release(), mv.release();
-      gmv.release(), ln.release();
-    }
   } l2;
   DevBuf<gn_board> roots, rboards, par;
   DevBuf<uint64_t> moff;
@@ -392,9 +407,15 @@ struct Dev {
   std::condition_variable fast_cv; // an instance's launch completed (its busy flag cleared; d.mu)
   // the expansion pipeline: the front's stream and its two events (the back's row stream done:
   // the front may overwrite the plan's lists; the plan done)
-  hipStream_t front = nullptr;
-  hipEvent_t ev_streamed = nullptr, ev_planned = nullptr;
+  Stream front;
+  Event ev_streamed, ev_planned;
   std::mutex mu;
+  // the device current and its streams idle before the members above free what may still be in use
+  ~Dev() {
+    (void)hipSetDevice(id);
+    for (hipStream_t s : {stream.h, front.h, copy.h})
+      if (s) (void)hipStreamSynchronize(s);
+  }
 };
 
 // The Dev's current expansion buffers <-> its other set (host-side pointers only: launches already
@@ -562,9 +583,8 @@ static int upload_net(Dev &d, int which, const HostNet &h) {
   const void *src[10] = {h.ft.data(), h.bias.data(), h.w0.data(), h.b0.data(),
                          h.w1.data(), h.b1.data(), h.w2.data(), h.b2.data(), psqt.data(), w0f.data()};
   for (int i = 0; i < 10; ++i) off[i] = o, o += align256(sz[i]);
-  uint8_t *m = nullptr;
-  if (hipMalloc(&m, o) != hipSuccess) return fail(GN_E_NOMEM, "device allocation of %zu bytes failed", o);
-  d.net_mem[which] = m;
+  if (d.net_mem[which].ensure(o) != hipSuccess) return fail(GN_E_NOMEM, "device allocation of %zu bytes failed", o);
+  uint8_t *const m = d.net_mem[which].p;
   for (int i = 0; i < 10; ++i)
     HIP_TRY(hipMemcpy(m + off[i], src[i], i == 0 ? (size_t)FT_ROWS * RS : sz[i], hipMemcpyHostToDevice));
   if (carry) HIP_TRY(hipMemset(m + off[0] + (size_t)FT_ROWS * RS, 0, 4 * (size_t)carry * RS));
@@ -588,44 +608,7 @@ static int upload_net(Dev &d, int which, const HostNet &h) {
   return GN_OK;
 }
 
-static void destroy(gn_ctx *ctx) {
-  if (!ctx) return;
-  for (auto &dp : ctx->devs) {
-    Dev &d = *dp;
-    (void)hipSetDevice(d.id);
-    if (d.stream) (void)hipStreamSynchronize(d.stream);
-    for (void *m : d.net_mem)
-      if (m) (void)hipFree(m);
-    if (d.tables) (void)hipFree(d.tables);
-    d.cur.release(), d.alt.release();
-    d.io_boards.release(), d.frontier.release(), d.io_out.release(), d.io_out2.release();
-    d.off32.release(), d.moves.release(), d.sum.release(), d.deltas.release();
-    d.part.release();
-    if (d.front) (void)hipStreamSynchronize(d.front), (void)hipStreamDestroy(d.front);
-    if (d.ev_streamed) (void)hipEventDestroy(d.ev_streamed);
-    if (d.ev_planned) (void)hipEventDestroy(d.ev_planned);
-    d.kkeys.release(), d.kkeys2.release(), d.kidx.release(), d.kperm.release();
-    d.nslot.release();
-    d.ebound.release(), d.pool.release();
-    d.bkeys.release(), d.bkeys2.release(), d.bidx.release();
-    d.lv[0].release(), d.lv[1].release();
-    d.l2.release();
-    for (auto &row : d.fast)
-      for (auto &pair : row)
-        for (auto &f : pair) f.reset();
-    for (int i = 0; i < 2; ++i) {
-      d.po2[i].release(), d.co2[i].release(), d.cc2[i].release(), d.mv2[i].release(), d.ln2[i].release();
-      if (d.rev[i]) (void)hipEventDestroy(d.rev[i]);
-      if (d.cev[i]) (void)hipEventDestroy(d.cev[i]);
-    }
-    d.roots.release(), d.rboards.release(), d.par.release(), d.moff.release(), d.codes.release();
-    d.smoves.release(), d.rstatus.release(), d.gidx.release(), d.rkeys.release(), d.hist.release();
-    if (d.copy) (void)hipStreamSynchronize(d.copy), (void)hipStreamDestroy(d.copy);
-    if (d.done) (void)hipEventDestroy(d.done);
-    if (d.stream) (void)hipStreamDestroy(d.stream);
-  }
-  delete ctx;
-}
+static void destroy(gn_ctx *ctx) { delete ctx; }
 
 static int create(const uint8_t *big, size_t big_len, const uint8_t *small, size_t small_len, const int *devices,
                   int n_devices, gn_ctx **out) {
@@ -646,7 +629,7 @@ static int create(const uint8_t *big, size_t big_len, const uint8_t *small, size
   std::vector<int> ids;
   if (devices && n_devices > 0) ids.assign(devices, devices + n_devices);
   else ids.push_back(0);
-  std::unique_ptr<gn_ctx, void (*)(gn_ctx *)> ctx(new gn_ctx(), destroy);
+  std::unique_ptr<gn_ctx> ctx(new gn_ctx());
   ctx->P = default_params();
   for (int w = 0; w < 2; ++w) ctx->l1[w] = hn[w].L1, ctx->hash[w] = hn[w].hash;
   for (int id : ids) {
@@ -659,22 +642,17 @@ static int create(const uint8_t *big, size_t big_len, const uint8_t *small, size
     Dev &d = *ctx->devs.back();
     d.id = id;
     HIP_TRY(hipSetDevice(id));
-    HIP_TRY(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&d.done, hipEventDisableTiming));
-    HIP_TRY(hipStreamCreateWithFlags(&d.copy, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&d.front, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&d.ev_streamed, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&d.ev_planned, hipEventDisableTiming));
-    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&d.cev[i], hipEventDisableTiming));
-    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&d.rev[i]));
-    HIP_TRY(hipMalloc(&d.tables, sizeof(Tables)));
+    for (Stream *s : {&d.stream, &d.copy, &d.front}) HIP_TRY(hipStreamCreateWithFlags(&s->h, hipStreamNonBlocking));
+    for (Event *e : {&d.done, &d.ev_streamed, &d.ev_planned, &d.cev[0], &d.cev[1], &d.cur.scored, &d.alt.scored})
+      HIP_TRY(hipEventCreateWithFlags(&e->h, hipEventDisableTiming));
+    for (Event &e : d.rev) HIP_TRY(hipEventCreate(&e.h));
+    HIP_TRY(d.tables.ensure(1));
     for (ExpSet *x : {&d.cur, &d.alt}) { // the planned expansion's error word and pad count
       HIP_TRY(x->perr.ensure(1));
       HIP_TRY(x->pstat.ensure(2));
-      HIP_TRY(hipEventCreateWithFlags(&x->scored, hipEventDisableTiming));
     }
     HIP_TRY(hipMemset(d.alt.perr.p, 0, sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(d.tables, &host_tables(), sizeof(Tables), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.tables.p, &host_tables(), sizeof(Tables), hipMemcpyHostToDevice));
     for (int w = 0; w < 2; ++w)
       if (hn[w].L1) {
         int rc = upload_net(d, w, hn[w]);
@@ -698,25 +676,34 @@ static bool read_file(const char *path, std::vector<uint8_t> &buf) {
 }
 
 // ---------------------------------------------------------- launches ------
-struct KernelTimes {
-  hipEvent_t ev[10];
-  bool on = false;
+// The marks of one timed evaluation, in stream order: gn_time_evaluate_device's four stages are
+// [begun, sorted] classify (+ the king sort), [sorted, small_done] the small net (+ reeval),
+// [small_done, big_done] the big net, [big_done, finalized] finalize.
+struct EvalEvents {
+  hipEvent_t begun, sorted, small_done, big_done, finalized;
+  hipError_t create(Events &from) { return from.make({&begun, &sorted, &small_done, &big_done, &finalized}); }
 };
-
-// Launch sequence of one evaluation.  ev (optional) = 5 events recorded between
-// the stages [classify(+)] [small net (+reeval)] [big net] [finalize].
-// score: the records are positions (the score rule's static part; resolve_scores does the
-// in-check ones) rather than child records; counts (optional): their legal-move counts.
-// eb (optional): the net outputs and selections in these buffers instead of the current set's (the
-// drop-in's captured small-batch graphs own theirs, FastBatch); sort false: no king sort.
+// evaluate_on's optional arguments.
+struct EvalOnOpts {
+  EvalEvents *ev = nullptr;           // recorded between the stages
+  unsigned long long *rows = nullptr; // += FT rows the gather reads (the big net's, or the small net's in GN_MODE_SMALL)
+  // the records are positions (the score rule's static part; resolve_scores does the in-check
+  // ones) rather than child records (0)
+  int score = 1;
+  const uint64_t *counts = nullptr; // their legal-move counts
+  // the net outputs and selections in these buffers instead of the current set's (the drop-in's
+  // captured small-batch graphs own theirs, FastBatch)
+  EvalBufs *eb = nullptr;
+  bool sort = true; // false: no king sort
+};
+// Launch sequence of one evaluation.
 static int evaluate_on(gn_ctx *ctx, Dev &d, const gn_board *b, size_t n, int mode, gn_eval *out, hipStream_t s,
-                       hipEvent_t *ev, unsigned long long *rows_out = nullptr, int score = 1,
-                       const uint64_t *counts = nullptr, EvalBufs *eb = nullptr, bool sort = true) {
+                       const EvalOnOpts &o = {}) {
   if (mode < GN_MODE_FULL || mode > GN_MODE_SMALL) return fail(GN_E_INVALID, "bad mode %d", mode);
   if ((mode != GN_MODE_SMALL && !d.has[BIG]) || (mode != GN_MODE_BIG && !d.has[SMALL]))
     return fail(GN_E_NONET, "mode %d needs a network that is not loaded", mode);
   if (!n) return GN_OK;
-  EvalBufs &B = eb ? *eb : d.cur.eb;
+  EvalBufs &B = o.eb ? *o.eb : d.cur.eb;
   DevBuf<int2> &osm = B.osm, &obg = B.obg;
   DevBuf<uint8_t> &nsm = B.nsm, &nbg = B.nbg;
   if (mode != GN_MODE_BIG) HIP_TRY(osm.ensure(n));
@@ -725,25 +712,25 @@ static int evaluate_on(gn_ctx *ctx, Dev &d, const gn_board *b, size_t n, int mod
     HIP_TRY(nsm.ensure(n));
     HIP_TRY(nbg.ensure(n));
   }
-  auto mark = [&](int k) -> hipError_t { return ev ? hipEventRecord(ev[k], s) : hipSuccess; };
+  auto mark = [&](hipEvent_t EvalEvents::*m) { return o.ev ? hipEventRecord(o.ev->*m, s) : hipSuccess; };
   const gn_eval_params &P = ctx->P;
-  HIP_TRY(mark(0)); // (mode FULL's selection runs inside the small net's launch: launch_eval_net cls)
+  HIP_TRY(mark(&EvalEvents::begun)); // (mode FULL's selection runs inside the small net's launch: launch_eval_net cls)
   const uint32_t *perm = nullptr;
   // a small batch (one game, a handful of in-check replies) gains nothing from the order and
   // would pay the sort's launches on its latency (bench.py secondary.dropin)
   constexpr size_t KING_SORT_MIN = 1024;
-  if (sort && (ctx->king_sort == 2 || (ctx->king_sort == 1 && n >= KING_SORT_MIN))) {
+  if (o.sort && (ctx->king_sort == 2 || (ctx->king_sort == 1 && n >= KING_SORT_MIN))) {
     if (n > 0x7FFFFFFFull) return fail(GN_E_INVALID, "king sort supports < 2^31 positions per call");
     HIP_TRY(d.kkeys.ensure(n));
     HIP_TRY(d.kkeys2.ensure(n));
     HIP_TRY(d.kidx.ensure(n));
     HIP_TRY(d.kperm.ensure(n));
-    HIP_TRY(king_sort(b, n, d.kkeys.p, d.kidx.p, d.kkeys2.p, d.kperm.p, mode != GN_MODE_SMALL, d.cur.sort_tmp,
-                      d.cur.sort_bytes, s));
+    HIP_TRY(king_sort(b, n, d.kkeys.p, d.kidx.p, d.kkeys2.p, d.kperm.p, mode != GN_MODE_SMALL, d.cur.sort_tmp.p,
+                      d.cur.sort_tmp.cap, s));
     perm = d.kperm.p;
   }
   const int swz = (ctx->swizzle >> 1) & 1;
-  HIP_TRY(mark(1));
+  HIP_TRY(mark(&EvalEvents::sorted));
   if (mode == GN_MODE_FULL && d.net[SMALL].L1 != 128) {
     // only the 128-wide kernel selects inside its launch: a wider net in the small slot gets the
     // selection, the selected positions and the re-evaluation marks as launches of their own
@@ -751,15 +738,14 @@ static int evaluate_on(gn_ctx *ctx, Dev &d, const gn_board *b, size_t n, int mod
     HIP_TRY(launch_eval_net(d.net[SMALL], b, nsm.p, n, osm.p, perm, swz, s, nullptr));
     HIP_TRY(launch_reeval(osm.p, nsm.p, n, P, nbg.p, s));
   } else if (mode != GN_MODE_BIG)
-    HIP_TRY(launch_eval_net(d.net[SMALL], b, nullptr, n, osm.p, perm, swz, s, mode == GN_MODE_SMALL ? rows_out : nullptr,
+    HIP_TRY(launch_eval_net(d.net[SMALL], b, nullptr, n, osm.p, perm, swz, s, mode == GN_MODE_SMALL ? o.rows : nullptr,
                             mode == GN_MODE_FULL ? &P : nullptr, nsm.p, nbg.p));
-  HIP_TRY(mark(2));
+  HIP_TRY(mark(&EvalEvents::small_done));
   if (mode != GN_MODE_SMALL)
-    HIP_TRY(launch_eval_net(d.net[BIG], b, mode == GN_MODE_FULL ? nbg.p : nullptr, n, obg.p, perm, swz, s,
-                            rows_out));
-  HIP_TRY(mark(3));
-  HIP_TRY(launch_finalize(b, n, mode, osm.p, obg.p, nsm.p, nbg.p, P, d.tables, out, s, score, counts));
-  HIP_TRY(mark(4));
+    HIP_TRY(launch_eval_net(d.net[BIG], b, mode == GN_MODE_FULL ? nbg.p : nullptr, n, obg.p, perm, swz, s, o.rows));
+  HIP_TRY(mark(&EvalEvents::big_done));
+  HIP_TRY(launch_finalize(b, n, mode, osm.p, obg.p, nsm.p, nbg.p, P, d.tables.p, out, s, o.score, o.counts));
+  HIP_TRY(mark(&EvalEvents::finalized));
   return GN_OK;
 }
 
@@ -824,11 +810,11 @@ static int finalize_all(gn_ctx *ctx, Dev &d, const gn_board *parents, const gn_b
                   sp = {&d.net[BIG], d.part.p, x.pinfo.p, (uint64_t)(n + total), 0, x.offsets.p};
   // children from their parents as write_children unpacked them
   const bool fast = x.child_moves != nullptr;
-  HIP_TRY(launch_finalize(children, total, mode, x.eb.osm.p, x.eb.obg.p, x.eb.nsm.p, x.eb.nbg.p, P, d.tables, child_out,
+  HIP_TRY(launch_finalize(children, total, mode, x.eb.osm.p, x.eb.obg.p, x.eb.nsm.p, x.eb.nbg.p, P, d.tables.p, child_out,
                           s, 0, nullptr, fast ? x.owner.p : nullptr, fast ? x.child_moves : nullptr,
                           fast ? x.unpacked.p : nullptr, sliced ? &sc : nullptr));
   if (parent_out) // the parents' legal-move counts are generate_children's
-    HIP_TRY(launch_finalize(parents, n, mode, x.p_osm.p, x.p_obg.p, x.p_nsm.p, x.p_nbg.p, P, d.tables, parent_out, s,
+    HIP_TRY(launch_finalize(parents, n, mode, x.p_osm.p, x.p_obg.p, x.p_nsm.p, x.p_nbg.p, P, d.tables.p, parent_out, s,
                             score_parents ? 1 : 0, x.counts.p, nullptr, nullptr, nullptr, sliced ? &sp : nullptr));
   return GN_OK;
 }
@@ -839,8 +825,8 @@ static hipError_t count_children(Dev &d, const gn_board *parents, size_t n, hipS
   hipError_t e;
   if ((e = x.counts.ensure(n + 1)) != hipSuccess || (e = x.offsets.ensure(n + 1)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(x.counts.p + n, 0, sizeof(uint64_t), s)) != hipSuccess) return e;
-  if ((e = launch_count_children(parents, n, d.tables, x.counts.p, s)) != hipSuccess) return e;
-  if ((e = exclusive_scan_u64(x.counts.p, x.offsets.p, n + 1, x.scan_tmp, x.scan_bytes, s)) != hipSuccess) return e;
+  if ((e = launch_count_children(parents, n, d.tables.p, x.counts.p, s)) != hipSuccess) return e;
+  if ((e = exclusive_scan_u64(x.counts.p, x.offsets.p, n + 1, x.scan_tmp.p, x.scan_tmp.cap, s)) != hipSuccess) return e;
   uint64_t t = 0;
   if ((e = hipMemcpyAsync(&t, x.offsets.p + n, sizeof(t), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
@@ -848,9 +834,23 @@ static hipError_t count_children(Dev &d, const gn_board *parents, size_t n, hipS
   return hipSuccess;
 }
 
+// The marks of one timed expansion (gn_time_expand_device makes the stage times of them), each
+// recorded by the function that reaches it: start by run_expansions; counted (count + scan),
+// total_read (the host has the child count) and written by generate_children; classified ...
+// finalized by expand_evaluate (stream_begun by a pipelined back half alone: the row stream's start
+// behind its wait for the plan); scored (the score rule queued) by the timing call.
+struct ExpEvents {
+  hipEvent_t start, counted, total_read, written, classified, small_done, plan_done, stream_begun, stream_done, big_done,
+      finalized, scored;
+  hipError_t create(Events &from) {
+    return from.make({&start, &counted, &total_read, &written, &classified, &small_done, &plan_done, &stream_begun,
+                      &stream_done, &big_done, &finalized, &scored});
+  }
+};
+
 // generate_children's optional arguments.
 struct GenOpts {
-  hipEvent_t *ev = nullptr; // 3 events: after count + scan, after the host read of the total, after write_children
+  ExpEvents *ev = nullptr;            // records counted, total_read, written
   unsigned long long *rows = nullptr; // += FT rows by write_children's formula
   bool deltas = false;                // + each child's ChildDelta (the incremental evaluation's input)
   int chain_k = 1;                    // with deltas: block length of the chained walk (chain_len)
@@ -881,17 +881,17 @@ static int generate_children(Dev &d, const gn_board *parents, size_t n, gn_board
     HIP_TRY(x.eoff.ensure(n + 1));
     HIP_TRY(hipMemsetAsync(d.ebound.p + n, 0, sizeof(uint64_t), s));
   }
-  HIP_TRY(launch_count_children(parents, n, d.tables, x.counts.p, s, x.planned ? d.ebound.p : nullptr, o.trusted));
-  HIP_TRY(exclusive_scan_u64(x.counts.p, x.offsets.p, n + 1, x.scan_tmp, x.scan_bytes, s));
-  if (x.planned) HIP_TRY(exclusive_scan_u64(d.ebound.p, x.eoff.p, n + 1, x.scan_tmp, x.scan_bytes, s));
-  if (o.ev) HIP_TRY(hipEventRecord(o.ev[0], s));
+  HIP_TRY(launch_count_children(parents, n, d.tables.p, x.counts.p, s, x.planned ? d.ebound.p : nullptr, o.trusted));
+  HIP_TRY(exclusive_scan_u64(x.counts.p, x.offsets.p, n + 1, x.scan_tmp.p, x.scan_tmp.cap, s));
+  if (x.planned) HIP_TRY(exclusive_scan_u64(d.ebound.p, x.eoff.p, n + 1, x.scan_tmp.p, x.scan_tmp.cap, s));
+  if (o.ev) HIP_TRY(hipEventRecord(o.ev->counted, s));
   uint64_t t = 0;
   HIP_TRY(hipMemcpyAsync(&t, x.offsets.p + n, sizeof(t), hipMemcpyDeviceToHost, s));
   if (x.planned) HIP_TRY(hipMemcpyAsync(&x.etot, x.eoff.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   *total = (size_t)t;
   if (t > o.limit) return fail(GN_E_CAPACITY, "%zu children exceed capacity %zu", (size_t)t, o.limit);
-  if (o.ev) HIP_TRY(hipEventRecord(o.ev[1], s));
+  if (o.ev) HIP_TRY(hipEventRecord(o.ev->total_read, s));
   gn_board *children = children_or_null;
   const bool skip_boards = !children_or_null && x.planned && o.skip_internal;
   if (!children && !skip_boards) {
@@ -907,11 +907,11 @@ static int generate_children(Dev &d, const gn_board *parents, size_t n, gn_board
   }
   x.child_moves = moves;
   if (t) {
-    HIP_TRY(launch_write_children(parents, n, d.tables, x.offsets.p, 0, t, children, moves, x.owner.p,
+    HIP_TRY(launch_write_children(parents, n, d.tables.p, x.offsets.p, 0, t, children, moves, x.owner.p,
                                   o.deltas ? d.deltas.p : nullptr, x.chain_k > 1 ? d.nslot.p : nullptr, x.chain_k,
                                   o.rows, s, x.unpacked.p, o.trusted));
   }
-  if (o.ev) HIP_TRY(hipEventRecord(o.ev[2], s));
+  if (o.ev) HIP_TRY(hipEventRecord(o.ev->written, s));
   return GN_OK;
 }
 
@@ -926,10 +926,7 @@ static GenOpts gen_opts(const gn_ctx *ctx, Dev &d, size_t n, int mode, size_t li
 // expand_evaluate's optional arguments.
 constexpr int EXP_FRONT = 1, EXP_BACK = 2;
 struct EvalOpts {
-  // [0] after classify, [1] after the small net (+ reeval), [2] after the big net, [3] after
-  // finalize, [4] the plan -> stream boundary, [6] after the stream launches, [7] (EXP_BACK alone)
-  // the stream's start
-  hipEvent_t *ev = nullptr;
+  ExpEvents *ev = nullptr; // records classified ... finalized (EXP_FRONT: to plan_done; EXP_BACK: from stream_begun)
   unsigned long long *rows = nullptr; // += FT rows the row stream gathers
   // the parents are positions (the score rule's static part; callers run resolve_scores on them)
   // rather than child records (depth 2's level 2)
@@ -949,19 +946,19 @@ static int expand_evaluate(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t 
   if ((mode != GN_MODE_SMALL && !d.has[BIG]) || (mode != GN_MODE_BIG && !d.has[SMALL]))
     return fail(GN_E_NONET, "mode %d needs a network that is not loaded", mode);
   ExpSet &x = d.cur;
-  hipEvent_t *const ev = o.ev;
   const int phases = o.phases;
   if (!ctx->incremental) {
     if (!(phases & EXP_BACK)) return GN_OK; // (no front half: every child is a full refresh)
+    EvalOnOpts as_children, as_parents;
+    as_children.score = 0;
+    as_parents.score = o.score_parents ? 1 : 0, as_parents.counts = x.counts.p;
     if (total) {
-      int rc = evaluate_on(ctx, d, children, total, mode, child_out, s, nullptr, nullptr, 0);
+      int rc = evaluate_on(ctx, d, children, total, mode, child_out, s, as_children);
       if (rc) return rc;
     }
-    return parent_out ? evaluate_on(ctx, d, parents, n, mode, parent_out, s, nullptr, nullptr, o.score_parents ? 1 : 0,
-                                    x.counts.p)
-                      : GN_OK;
+    return parent_out ? evaluate_on(ctx, d, parents, n, mode, parent_out, s, as_parents) : GN_OK;
   }
-  auto mark = [&](int k) -> hipError_t { return ev ? hipEventRecord(ev[k], s) : hipSuccess; };
+  auto mark = [&](hipEvent_t ExpEvents::*m) { return o.ev ? hipEventRecord(o.ev->*m, s) : hipSuccess; };
   const gn_eval_params &P = ctx->P;
   const uint64_t *off = x.offsets.p;
   const ChildDelta *dl = d.deltas.p;
@@ -1000,7 +997,7 @@ static int expand_evaluate(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t 
       HIP_TRY(launch_classify(parents, n, P, x.p_nsm.p, x.p_nbg.p, s));
       HIP_TRY(launch_classify(children, total, P, x.eb.nsm.p, x.eb.nbg.p, s));
     }
-    HIP_TRY(mark(0));
+    HIP_TRY(mark(&ExpEvents::classified));
     if (mode != GN_MODE_BIG) {
       HIP_TRY(launch_expand_net(d.net[SMALL], parents, n, off, children, dl, f ? x.p_nsm.p : nullptr,
                                 f ? x.eb.nsm.p : nullptr, x.p_osm.p, x.eb.osm.p, ctx->swizzle & 1, s));
@@ -1009,7 +1006,7 @@ static int expand_evaluate(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t 
         HIP_TRY(launch_reeval(x.eb.osm.p, x.eb.nsm.p, total, P, x.eb.nbg.p, s));
       }
     }
-    HIP_TRY(mark(1));
+    HIP_TRY(mark(&ExpEvents::small_done));
     x.slices = 1;
     if (mode != GN_MODE_SMALL && x.planned) {
       HIP_TRY(x.ent.ensure(x.etot + (size_t)ENT_SPARE * (nblk + 1)));
@@ -1037,11 +1034,10 @@ static int expand_evaluate(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t 
         HIP_TRY(d.bidx.ensure(nblk));
         HIP_TRY(x.border.ensure(nblk));
         HIP_TRY(block_order(parents, n, (uint32_t)K, (uint32_t)nblk, d.bkeys.p, d.bidx.p, d.bkeys2.p, x.border.p,
-                            x.sort_tmp, x.sort_bytes, s));
+                            x.sort_tmp.p, x.sort_tmp.cap, s));
       }
-      PlanStreamArgs a = plan_args();
-      a.mid = ev ? ev[4] : nullptr;
-      HIP_TRY(launch_plan_stream(d.net[BIG], a, PLAN_PHASE, s));
+      HIP_TRY(launch_plan_stream(d.net[BIG], plan_args(), PLAN_PHASE, s));
+      HIP_TRY(mark(&ExpEvents::plan_done));
     }
   }
   if (!(phases & EXP_BACK)) return GN_OK;
@@ -1051,21 +1047,22 @@ static int expand_evaluate(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t 
   if (mode != GN_MODE_SMALL) {
     if (x.planned) {
       HIP_TRY(hipMemsetAsync(d.pool.p, 0, 88 * sizeof(uint32_t), s)); // per stream launch (<= 3)
-      if (ev && (phases & EXP_FRONT) == 0) HIP_TRY(hipEventRecord(ev[7], s)); // (the pipeline: the stream's start)
+      if (!(phases & EXP_FRONT)) HIP_TRY(mark(&ExpEvents::stream_begun)); // (the pipeline: the stream's start)
       PlanStreamArgs a = plan_args();
       a.swz = (ctx->swizzle >> 2) & 1 ? 1 : (ctx->swizzle >> 3) & 1 ? 2 : 0;
       a.order = ordered ? x.border.p : nullptr;
-      a.fin = ev ? ev[6] : nullptr, a.streamed = o.streamed;
       HIP_TRY(launch_plan_stream(d.net[BIG], a, STREAM_PHASE, s));
+      HIP_TRY(mark(&ExpEvents::stream_done));
+      if (o.streamed) HIP_TRY(hipEventRecord(o.streamed, s));
     } else { // a 128-wide net loaded as the big net
       HIP_TRY(launch_expand_net(d.net[BIG], parents, n, off, children, dl, f ? x.p_nbg.p : nullptr,
                                 f ? x.eb.nbg.p : nullptr, x.p_obg.p, x.eb.obg.p, ctx->swizzle & 1, s));
     }
   }
-  HIP_TRY(mark(2));
+  HIP_TRY(mark(&ExpEvents::big_done));
   int rc = finalize_all(ctx, d, parents, children, mode, parent_out, child_out, n, total, s, o.score_parents, sliced);
   if (rc) return rc;
-  HIP_TRY(mark(3));
+  HIP_TRY(mark(&ExpEvents::finalized));
   return GN_OK;
 }
 
@@ -1094,7 +1091,7 @@ static int resolve_scores(gn_ctx *ctx, Dev &d, const gn_board *boards, size_t n,
   HIP_TRY(L.sel.ensure(n + 1));
   HIP_TRY(L.pos.ensure(n + 1));
   HIP_TRY(launch_score_select(out, n, L.sel.p, s));
-  HIP_TRY(exclusive_scan_u64(L.sel.p, L.pos.p, n + 1, d.cur.scan_tmp, d.cur.scan_bytes, s));
+  HIP_TRY(exclusive_scan_u64(L.sel.p, L.pos.p, n + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap, s));
   uint64_t m = 0;
   HIP_TRY(hipMemcpyAsync(&m, L.pos.p + n, sizeof(m), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1103,17 +1100,17 @@ static int resolve_scores(gn_ctx *ctx, Dev &d, const gn_board *boards, size_t n,
   HIP_TRY(L.boards.ensure(m));
   HIP_TRY(L.counts.ensure(m + 1));
   HIP_TRY(L.offsets.ensure(m + 1));
-  HIP_TRY(launch_score_gather(boards, L.sel.p, L.pos.p, n, replies ? nullptr : d.tables, L.idx.p, L.boards.p, s));
+  HIP_TRY(launch_score_gather(boards, L.sel.p, L.pos.p, n, replies ? nullptr : d.tables.p, L.idx.p, L.boards.p, s));
   if (replies) {
     uint64_t t = 0;
-    HIP_TRY(launch_score_replies(L.idx.p, m, d.cur.offsets.p, L.counts.p, L.offsets.p, d.cur.scan_tmp,
-                                 d.cur.scan_bytes, &t, s));
+    HIP_TRY(launch_score_replies(L.idx.p, m, d.cur.offsets.p, L.counts.p, L.offsets.p, d.cur.scan_tmp.p,
+                                 d.cur.scan_tmp.cap, &t, s));
     HIP_TRY(L.moves.ensure(std::max<uint64_t>(t, 1)));
     HIP_TRY(L.children.ensure(std::max<uint64_t>(t, 1)));
     HIP_TRY(L.ce.ensure(std::max<uint64_t>(t, 1)));
     HIP_TRY(L.sv.ensure(std::max<uint64_t>(t, 1)));
     HIP_TRY(launch_score_replies_fill(L.idx.p, m, d.cur.offsets.p, L.offsets.p, replies->rec, replies->moves,
-                                      d.cur.unpacked.p, d.tables, L.ce.p, L.children.p, L.moves.p, s));
+                                      d.cur.unpacked.p, d.tables.p, L.ce.p, L.children.p, L.moves.p, s));
     int rc = resolve_scores(ctx, d, L.children.p, t, mode, L.ce.p, L.sv.p, s, depth - 1);
     if (rc) return rc;
     HIP_TRY(launch_score_reduce(L.boards.p, m, L.idx.p, L.offsets.p, L.moves.p, L.ce.p, L.sv.p, ctx->P, out, sv_out,
@@ -1121,8 +1118,8 @@ static int resolve_scores(gn_ctx *ctx, Dev &d, const gn_board *boards, size_t n,
     return GN_OK;
   }
   HIP_TRY(hipMemsetAsync(L.counts.p + m, 0, sizeof(uint64_t), s));
-  HIP_TRY(launch_count_children(L.boards.p, m, d.tables, L.counts.p, s));
-  HIP_TRY(exclusive_scan_u64(L.counts.p, L.offsets.p, m + 1, d.cur.scan_tmp, d.cur.scan_bytes, s));
+  HIP_TRY(launch_count_children(L.boards.p, m, d.tables.p, L.counts.p, s));
+  HIP_TRY(exclusive_scan_u64(L.counts.p, L.offsets.p, m + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap, s));
   uint64_t t = 0;
   HIP_TRY(hipMemcpyAsync(&t, L.offsets.p + m, sizeof(t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1131,13 +1128,52 @@ static int resolve_scores(gn_ctx *ctx, Dev &d, const gn_board *boards, size_t n,
   HIP_TRY(L.children.ensure(std::max<uint64_t>(t, 1)));
   HIP_TRY(L.ce.ensure(std::max<uint64_t>(t, 1)));
   HIP_TRY(L.sv.ensure(std::max<uint64_t>(t, 1)));
-  HIP_TRY(launch_write_children(L.boards.p, m, d.tables, L.offsets.p, 0, t, L.children.p, L.moves.p, L.owner.p,
+  HIP_TRY(launch_write_children(L.boards.p, m, d.tables.p, L.offsets.p, 0, t, L.children.p, L.moves.p, L.owner.p,
                                 nullptr, nullptr, 1, nullptr, s));
-  int rc = evaluate_on(ctx, d, L.children.p, t, mode, L.ce.p, s, nullptr);
+  int rc = evaluate_on(ctx, d, L.children.p, t, mode, L.ce.p, s);
   if (rc) return rc;
   if ((rc = resolve_scores(ctx, d, L.children.p, t, mode, L.ce.p, L.sv.p, s, depth - 1)) != GN_OK) return rc;
   HIP_TRY(launch_score_reduce(L.boards.p, m, L.idx.p, L.offsets.p, L.moves.p, L.ce.p, L.sv.p, ctx->P, out, sv_out, s));
   return GN_OK;
+}
+
+// ------------------------------------------------------- one level -------
+// expand_level's optional arguments.
+struct LevelOpts {
+  gn_board *children = nullptr; // the caller's child boards (NULL: the set's own, library-internal)
+  bool trusted = false;         // the parents are the library's own boards (GenOpts::trusted)
+  // the parents are positions and get the score rule, from the replies this level evaluated; false:
+  // they are child records (depth 2's level 2)
+  bool score_parents = true;
+  const char *what = "children"; // (the 32-bit offsets' message)
+};
+// One synchronous expansion level on stream s (gn_expand_device; both levels of expand2_on): the
+// n parents' children generated (at most cap, else GN_E_CAPACITY with *total set and d_offsets
+// written), d_offsets (n + 1) as 32-bit, parents and children evaluated, the parents' score rule,
+// and the planned expansion's error word checked.  The stream is idle on return.
+static int expand_level(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t n, int mode, gn_eval *parent_out,
+                        uint32_t *d_offsets, uint16_t *d_moves, gn_eval *child_out, size_t cap, size_t *total,
+                        hipStream_t s, const LevelOpts &o = {}) {
+  GenOpts g = gen_opts(ctx, d, n, mode, cap);
+  g.trusted = o.trusted;
+  size_t t = 0;
+  int rc = generate_children(d, parents, n, o.children, d_moves, &t, s, g);
+  *total = t;
+  if (t > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "%zu %s exceed 32-bit offsets", t, o.what);
+  HIP_TRY(launch_offsets_u32(d.cur.offsets.p, n + 1, d_offsets, s));
+  if (rc) {
+    HIP_TRY(hipStreamSynchronize(s));
+    return rc;
+  }
+  EvalOpts e;
+  e.score_parents = o.score_parents;
+  rc = expand_evaluate(ctx, d, parents, n, o.children ? o.children : d.cur.children.p, t, mode, parent_out, child_out, s,
+                       e);
+  const Replies rp{child_out, d_moves}; // the replies this level evaluated
+  if (!rc && o.score_parents) rc = resolve_scores(ctx, d, parents, n, mode, parent_out, nullptr, s, 2, &rp);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(s));
+  return check_plan(d, s);
 }
 
 // ---------------------------------------------------------- sharding -----
@@ -1203,7 +1239,7 @@ static int fast_build(gn_ctx *ctx, Dev &d, FastBatch &f, size_t nb, int mode) {
   // smaller one is cheaper, and a batch beyond them reruns on the general path
   f.nb = nb, f.c1 = nb / 2 + 256, f.c2 = nb / 4 + 256, f.mode = mode, f.gen = ctx->graph_gen.load();
   const size_t na = nb + f.c1 + f.c2;
-  HIP_TRY(hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&f.done.h, hipEventDisableTiming));
   HIP_TRY(hipHostMalloc((void **)&f.h_in, nb * sizeof(gn_board), hipHostMallocDefault));
   HIP_TRY(hipHostMalloc((void **)&f.h_out, (nb + 1) * sizeof(gn_eval), hipHostMallocDefault));
   HIP_TRY(f.all.ensure(na));
@@ -1230,9 +1266,11 @@ static int fast_build(gn_ctx *ctx, Dev &d, FastBatch &f, size_t nb, int mode) {
     // level 1: the replies of the in-check positions; level 2: those of the replies in check --
     // both from the boards alone (the selection is board properties), so that one evaluation
     // then covers the three levels (round 6: three evaluations, one per level, nine launches)
-    HIP_TRY(launch_reply_level(f.in, nb, d.tables, f.off0.p, f.c1, f.r1, f.m1.p, flag, 1, s));
-    HIP_TRY(launch_reply_level(f.r1, f.c1, d.tables, f.off1.p, f.c2, f.r2, f.m2.p, flag, 0, s));
-    int rc = evaluate_on(ctx, d, f.all.p, na, mode, f.out, s, nullptr, nullptr, 1, nullptr, &f.eb, false);
+    HIP_TRY(launch_reply_level(f.in, nb, d.tables.p, f.off0.p, f.c1, f.r1, f.m1.p, flag, 1, s));
+    HIP_TRY(launch_reply_level(f.r1, f.c1, d.tables.p, f.off1.p, f.c2, f.r2, f.m2.p, flag, 0, s));
+    EvalOnOpts own; // the graph's own buffers, in the order given
+    own.eb = &f.eb, own.sort = false;
+    int rc = evaluate_on(ctx, d, f.all.p, na, mode, f.out, s, own);
     if (rc) return rc;
     HIP_TRY(launch_score_reduce2(f.r1, f.c1, f.off1.p, f.m2.p, f.e2, f.sv2.p, f.e1, f.sv1.p, f.in, nb, f.off0.p, f.m1.p,
                                  ctx->P, f.out, s));
@@ -1240,15 +1278,10 @@ static int fast_build(gn_ctx *ctx, Dev &d, FastBatch &f, size_t nb, int mode) {
     return GN_OK;
   };
   const int rc = seq();
-  hipGraph_t g = nullptr;
-  const hipError_t ec = hipStreamEndCapture(s, &g);
-  if (rc) {
-    if (g) (void)hipGraphDestroy(g);
-    return rc;
-  }
+  const hipError_t ec = hipStreamEndCapture(s, &f.graph.h); // (a failed sequence's graph goes with f)
+  if (rc) return rc;
   HIP_TRY(ec);
-  f.graph = g;
-  HIP_TRY(hipGraphInstantiate(&f.exec, f.graph, nullptr, nullptr, 0));
+  HIP_TRY(hipGraphInstantiate(&f.exec.h, f.graph, nullptr, nullptr, 0));
   return GN_OK;
 }
 
@@ -1333,7 +1366,7 @@ static int evaluate_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, i
       HIP_TRY(d.io_out.ensure(hi - lo));
       HIP_TRY(hipMemcpyAsync(d.io_boards.p, boards + lo, (hi - lo) * sizeof(gn_board), hipMemcpyHostToDevice,
                              d.stream));
-      int r = evaluate_on(ctx, d, d.io_boards.p, hi - lo, mode, d.io_out.p, d.stream, nullptr);
+      int r = evaluate_on(ctx, d, d.io_boards.p, hi - lo, mode, d.io_out.p, d.stream);
       if (!r) r = resolve_scores(ctx, d, d.io_boards.p, hi - lo, mode, d.io_out.p, nullptr, d.stream);
       if (r) return r;
       HIP_TRY(hipMemcpyAsync(out + lo, d.io_out.p, (hi - lo) * sizeof(gn_eval), hipMemcpyDeviceToHost, d.stream));
@@ -1530,8 +1563,7 @@ struct ExpStep {
   gn_eval *parent_out = nullptr, *child_out = nullptr; // (NULL: the device's io_out / io_out2)
   uint16_t *moves = nullptr; // the children's moves (NULL: the buffer set's own)
   size_t cap = SIZE_MAX;     // more children than this fail the call (GN_E_CAPACITY)
-  // 12 stage events (optional): [0] the start, [1..3] generate_children's, [4..11] expand_evaluate's
-  hipEvent_t *ev = nullptr;
+  ExpEvents *ev = nullptr; // the expansion's marks (a timed one)
   // 2 row counters (optional): [0] += rows by write_children's formula, when no planned row stream
   // counts them (a per-wave atomic over every child would sit in a timed region), [1] += rows the
   // row stream gathered
@@ -1574,16 +1606,16 @@ static int run_expansions(gn_ctx *ctx, Dev &d, int mode, size_t count, size_t la
     int rc = step(i, x.st);
     if (rc) return rc;
     const ExpStep &st = x.st;
-    if (st.ev) HIP_TRY(hipEventRecord(st.ev[0], F));
+    if (st.ev) HIP_TRY(hipEventRecord(st.ev->start, F));
     GenOpts g = gen_opts(ctx, d, st.n, mode, st.cap);
-    g.ev = st.ev ? st.ev + 1 : nullptr, g.rows = g.plan ? nullptr : st.rows;
+    g.ev = st.ev, g.rows = g.plan ? nullptr : st.rows;
     if ((rc = generate_children(d, st.parents, st.n, nullptr, st.moves, &x.total, F, g)) != GN_OK) return rc;
     if (!st.parent_out) HIP_TRY(d.io_out.ensure(st.n));
     if (!st.child_out) HIP_TRY(d.io_out2.ensure(std::max<size_t>(x.total, 1)));
     x.po = st.parent_out ? st.parent_out : d.io_out.p, x.co = st.child_out ? st.child_out : d.io_out2.p;
     if (!pipe) return GN_OK; // (serial: the back half evaluates both phases)
     EvalOpts e;
-    e.ev = st.ev ? st.ev + 4 : nullptr, e.rows = st.rows ? st.rows + 1 : nullptr, e.phases = EXP_FRONT;
+    e.ev = st.ev, e.rows = st.rows ? st.rows + 1 : nullptr, e.phases = EXP_FRONT;
     rc = expand_evaluate(ctx, d, st.parents, st.n, d.cur.children.p, x.total, mode, nullptr, nullptr, F, e);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(d.ev_planned, F));
@@ -1617,7 +1649,7 @@ static int run_expansions(gn_ctx *ctx, Dev &d, int mode, size_t count, size_t la
     const Queued &x = q[i & 1];
     const bool more = i + 1 < count;
     EvalOpts e; // d.cur's row stream and finalize
-    e.ev = x.st.ev ? x.st.ev + 4 : nullptr, e.rows = x.st.rows ? x.st.rows + 1 : nullptr;
+    e.ev = x.st.ev, e.rows = x.st.rows ? x.st.rows + 1 : nullptr;
     if (pipe) {
       HIP_TRY(hipStreamWaitEvent(s, d.ev_planned, 0));
       e.phases = EXP_BACK, e.streamed = d.ev_streamed;
@@ -1731,7 +1763,7 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
           // set is queued after the synchronisation below)
           const RankHistory h = {o.history.keys, o.history.n_keys, o.history.hist ? o.history.hist + pa : nullptr};
           HIP_TRY(hipEventRecord(d.rev[0], s));
-          HIP_TRY(launch_rank_children(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P, d.tables,
+          HIP_TRY(launch_rank_children(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P, d.tables.p,
                                        n_lines, d.ln2[k].p, h.hist ? &h : nullptr, s));
           HIP_TRY(hipEventRecord(d.rev[1], s));
         } else {
@@ -2026,13 +2058,13 @@ static int games_replay(const GamesCall &c, GameShard &sh, Dev &d, size_t g0, si
   HIP_TRY(hipStreamSynchronize(s));
   d.t_upload += ms_since(t0);
   const auto t1 = Clock::now();
-  HIP_TRY(launch_replay_games(d.roots.p, ng, d.moff.p, d.codes.p, d.tables, d.rboards.p, d.smoves.p, d.rstatus.p, s));
+  HIP_TRY(launch_replay_games(d.roots.p, ng, d.moff.p, d.codes.p, d.tables.p, d.rboards.p, d.smoves.p, d.rstatus.p, s));
   if (c.history) { // the keys of every replayed board (a failed game's unwritten ones are never indexed),
                    // queued behind the replay: the status read-back below waits for both
     HIP_TRY(d.rkeys.ensure(nm + ng));
     d.n_rkeys = nm + ng;
     HIP_TRY(hipEventRecord(d.rev[0], s));
-    HIP_TRY(launch_position_keys(d.rboards.p, nm + ng, false, d.tables, d.rkeys.p, s));
+    HIP_TRY(launch_position_keys(d.rboards.p, nm + ng, false, d.tables.p, d.rkeys.p, s));
     HIP_TRY(hipEventRecord(d.rev[1], s));
   }
   sh.status.resize(ng);
@@ -2155,7 +2187,7 @@ static int games_evaluate_or_count(const GamesCall &c, GameShard &sh, Dev &d) {
   if (c.with_children) return count_shard(d, sh.parents_of(d), m, sh.off);
   const auto t1 = Clock::now();
   HIP_TRY(d.io_out.ensure(m));
-  int r = evaluate_on(c.ctx, d, sh.parents_of(d), m, c.mode, d.io_out.p, s, nullptr);
+  int r = evaluate_on(c.ctx, d, sh.parents_of(d), m, c.mode, d.io_out.p, s);
   if (!r) r = resolve_scores(c.ctx, d, sh.parents_of(d), m, c.mode, d.io_out.p, nullptr, s);
   if (r) return r;
   HIP_TRY(hipStreamSynchronize(s));
@@ -2580,7 +2612,7 @@ int gn_evaluate_device(gn_ctx *ctx, int device_slot, const gn_board *d_boards, s
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
   const hipStream_t s = call.s;
-  int rc = evaluate_on(ctx, *d, d_boards, n, mode, d_out, s, nullptr);
+  int rc = evaluate_on(ctx, *d, d_boards, n, mode, d_out, s);
   if (!rc) rc = resolve_scores(ctx, *d, d_boards, n, mode, d_out, nullptr, s);
   if (rc) return rc;
   HIP_TRY(call.sg->finish()); // blocking (gpu_nnue.h): d_out is written when the call returns
@@ -2594,48 +2626,44 @@ int gn_time_evaluate_device(gn_ctx *ctx, int device_slot, const gn_board *d_boar
   if (iters <= 0 || !ms_total) return fail(GN_E_INVALID, "bad iters / ms_total");
   DevCall call(*d);
   if (call.rc) return call.rc;
-  std::vector<hipEvent_t> ev((size_t)iters * 5 + 2, nullptr);
-  auto cleanup = [&] {
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e);
-  };
-  for (auto &e : ev)
-    if (hipEventCreate(&e) != hipSuccess) {
-      cleanup();
-      return fail(GN_E_HIP, "hipEventCreate failed");
-    }
-  int rc = GN_OK;
+  const hipStream_t s = call.s;
+  Events events;
+  hipEvent_t begin, end;
+  HIP_TRY(events.make({&begin, &end}));
+  std::vector<EvalEvents> marks(per_kernel_ms ? (size_t)iters : 0);
+  for (EvalEvents &e : marks) HIP_TRY(e.create(events));
   if (ft_rows) {
     HIP_TRY(d->sum.ensure(2));
-    HIP_TRY(hipMemsetAsync(d->sum.p, 0, sizeof(unsigned long long), d->stream));
+    HIP_TRY(hipMemsetAsync(d->sum.p, 0, sizeof(unsigned long long), s));
   }
-  hipError_t he = hipEventRecord(ev[0], d->stream);
-  for (int it = 0; it < iters && rc == GN_OK && he == hipSuccess; ++it) {
-    rc = evaluate_on(ctx, *d, d_boards, n, mode, d_out, d->stream, per_kernel_ms ? &ev[2 + 5 * it] : nullptr,
-                     ft_rows && it == 0 ? d->sum.p : nullptr);
-    if (rc == GN_OK) rc = resolve_scores(ctx, *d, d_boards, n, mode, d_out, nullptr, d->stream);
+  HIP_TRY(hipEventRecord(begin, s));
+  for (int it = 0; it < iters; ++it) {
+    EvalOnOpts o;
+    o.ev = per_kernel_ms ? &marks[it] : nullptr, o.rows = ft_rows && it == 0 ? d->sum.p : nullptr;
+    int rc = evaluate_on(ctx, *d, d_boards, n, mode, d_out, s, o);
+    if (rc == GN_OK) rc = resolve_scores(ctx, *d, d_boards, n, mode, d_out, nullptr, s);
+    if (rc) return rc;
   }
-  if (rc == GN_OK && he == hipSuccess) he = hipEventRecord(ev[1], d->stream);
-  if (rc == GN_OK && he == hipSuccess) he = hipEventSynchronize(ev[1]);
-  if (rc == GN_OK && he == hipSuccess) he = hipEventElapsedTime(ms_total, ev[0], ev[1]);
-  if (rc == GN_OK && he == hipSuccess && per_kernel_ms) {
+  HIP_TRY(hipEventRecord(end, s));
+  HIP_TRY(hipEventSynchronize(end));
+  HIP_TRY(hipEventElapsedTime(ms_total, begin, end));
+  if (per_kernel_ms) {
     float acc[4] = {0, 0, 0, 0};
-    for (int it = 0; it < iters && he == hipSuccess; ++it)
-      for (int k = 0; k < 4 && he == hipSuccess; ++k) {
+    for (const EvalEvents &e : marks) {
+      const hipEvent_t in_order[5] = {e.begun, e.sorted, e.small_done, e.big_done, e.finalized};
+      for (int k = 0; k < 4; ++k) {
         float ms = 0;
-        he = hipEventElapsedTime(&ms, ev[2 + 5 * it + k], ev[2 + 5 * it + k + 1]);
+        HIP_TRY(hipEventElapsedTime(&ms, in_order[k], in_order[k + 1]));
         acc[k] += ms;
       }
+    }
     for (int k = 0; k < 4; ++k) per_kernel_ms[k] = acc[k] / (float)iters;
   }
-  cleanup();
-  if (rc) return rc;
-  if (ft_rows && he == hipSuccess) {
+  if (ft_rows) {
     unsigned long long r = 0;
-    he = hipMemcpy(&r, d->sum.p, sizeof(r), hipMemcpyDeviceToHost);
+    HIP_TRY(hipMemcpy(&r, d->sum.p, sizeof(r), hipMemcpyDeviceToHost));
     *ft_rows = r;
   }
-  if (he != hipSuccess) return fail(GN_E_HIP, "timing failed: %s", hipGetErrorString(he));
   return GN_OK;
 }
 
@@ -2670,7 +2698,7 @@ int gn_random_positions_device(gn_ctx *ctx, int device_slot, uint64_t seed, size
   if (max_plies < 0) return fail(GN_E_INVALID, "max_plies < 0");
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
-  HIP_TRY(launch_random_positions(seed, first_index, n, max_plies, d->tables, d_out, call.s));
+  HIP_TRY(launch_random_positions(seed, first_index, n, max_plies, d->tables.p, d_out, call.s));
   return GN_OK;
 }
 
@@ -2748,21 +2776,9 @@ int gn_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, si
   *total = 0;
   if (!n) return GN_OK;
   if (!d_children || !d_moves || !d_child_out) return fail(GN_E_INVALID, "NULL child buffer");
-  size_t t = 0;
-  int rc = generate_children(*d, d_parents, n, d_children, d_moves, &t, s, gen_opts(ctx, *d, n, mode, cap));
-  *total = t;
-  if (t > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "%zu children exceed 32-bit offsets", t);
-  HIP_TRY(launch_offsets_u32(d->cur.offsets.p, n + 1, d_offsets, s));
-  if (rc) {
-    HIP_TRY(hipStreamSynchronize(s));
-    return rc;
-  }
-  rc = expand_evaluate(ctx, *d, d_parents, n, d_children, t, mode, d_parent_out, d_child_out, s);
-  const Replies rp{d_child_out, d_moves}; // the replies this expansion evaluated
-  if (!rc) rc = resolve_scores(ctx, *d, d_parents, n, mode, d_parent_out, nullptr, s, 2, &rp);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(s));
-  return check_plan(*d, s);
+  LevelOpts o;
+  o.children = d_children;
+  return expand_level(ctx, *d, d_parents, n, mode, d_parent_out, d_offsets, d_moves, d_child_out, cap, total, s, o);
 }
 
 // What the four gn_rank_*_device calls check before they take the device, in this order: the slot,
@@ -2786,7 +2802,7 @@ int gn_rank_children_device(gn_ctx *ctx, int device_slot, const gn_board *d_pare
   if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, nullptr, d)) return rc;
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
-  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables, n_lines, d_lines, nullptr,
+  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables.p, n_lines, d_lines, nullptr,
                                call.s));
   return GN_OK;
 }
@@ -2798,7 +2814,7 @@ int gn_position_keys_device(gn_ctx *ctx, int device_slot, const gn_board *d_boar
   if (n && (!d_boards || !d_keys)) return fail(GN_E_INVALID, "NULL buffer");
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
-  HIP_TRY(launch_position_keys(d_boards, n, true, d->tables, d_keys, call.s));
+  HIP_TRY(launch_position_keys(d_boards, n, true, d->tables.p, d_keys, call.s));
   return GN_OK;
 }
 
@@ -2811,7 +2827,7 @@ int gn_rank_children_history_device(gn_ctx *ctx, int device_slot, const gn_board
   if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, &h, d)) return rc;
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
-  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables, n_lines, d_lines, &h,
+  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables.p, n_lines, d_lines, &h,
                                call.s));
   return GN_OK;
 }
@@ -2841,27 +2857,15 @@ static int expand2_on(gn_ctx *ctx, Dev *d, const gn_board *d_parents, size_t n, 
   *total = *gtotal = 0;
   if (!n) return GN_OK;
   // a size query (NULL child buffers or too small): the counts, GN_E_CAPACITY
-  size_t t = 0;
   if (!d_children || !d_moves || !d_child_out || !cap) {
-    HIP_TRY(count_children(*d, d_parents, n, s, &t));
-    *total = t;
-    return t ? fail(GN_E_CAPACITY, "%zu children exceed capacity %zu", t, cap) : GN_OK;
+    HIP_TRY(count_children(*d, d_parents, n, s, total));
+    return *total ? fail(GN_E_CAPACITY, "%zu children exceed capacity %zu", *total, cap) : GN_OK;
   }
-  // level 1
-  int rc = generate_children(*d, d_parents, n, d_children, d_moves, &t, s, gen_opts(ctx, *d, n, mode, cap));
-  *total = t;
-  if (t > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "%zu children exceed 32-bit offsets", t);
-  HIP_TRY(launch_offsets_u32(d->cur.offsets.p, n + 1, d_offsets, s));
-  if (rc) {
-    HIP_TRY(hipStreamSynchronize(s));
-    return rc;
-  }
-  rc = expand_evaluate(ctx, *d, d_parents, n, d_children, t, mode, d_parent_out, d_child_out, s);
+  LevelOpts l1;
+  l1.children = d_children;
+  int rc = expand_level(ctx, *d, d_parents, n, mode, d_parent_out, d_offsets, d_moves, d_child_out, cap, total, s, l1);
   if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(s));
-  if ((rc = check_plan(*d, s)) != GN_OK) return rc;
-  const Replies rp{d_child_out, d_moves}; // level 1's replies
-  if ((rc = resolve_scores(ctx, *d, d_parents, n, mode, d_parent_out, nullptr, s, 2, &rp)) != GN_OK) return rc;
+  const size_t t = *total;
   size_t g = 0;
   if (size_grand) { // (the library's own level-2 buffers, grown to the exact count)
     if (t) HIP_TRY(count_children(*d, d_children, t, s, &g));
@@ -2874,25 +2878,16 @@ static int expand2_on(gn_ctx *ctx, Dev *d, const gn_board *d_parents, size_t n, 
   }
   // level 2: the children as parents (their grandchildren boards stay library-internal)
   if (!gr.d_goffsets || !gr.d_gmoves || !gr.d_grand_out || !gr.gcap) {
-    HIP_TRY(count_children(*d, d_children, t, s, &g));
-    *gtotal = g;
-    return g ? fail(GN_E_CAPACITY, "%zu grandchildren exceed capacity %zu", g, gr.gcap) : GN_OK;
+    HIP_TRY(count_children(*d, d_children, t, s, gtotal));
+    return *gtotal ? fail(GN_E_CAPACITY, "%zu grandchildren exceed capacity %zu", *gtotal, gr.gcap) : GN_OK;
   }
-  GenOpts g2 = gen_opts(ctx, *d, t, mode, gr.gcap);
-  g2.trusted = true; // level 1's children, written above
-  rc = generate_children(*d, d_children, t, nullptr, gr.d_gmoves, &g, s, g2);
-  *gtotal = g;
-  if (g > 0xFFFFFFFFull) return fail(GN_E_CAPACITY, "%zu grandchildren exceed 32-bit offsets", g);
-  HIP_TRY(launch_offsets_u32(d->cur.offsets.p, t + 1, gr.d_goffsets, s));
-  if (rc) {
-    HIP_TRY(hipStreamSynchronize(s));
-    return rc;
-  }
+  // (level 1's children, written above: trusted; as parents they are child records here too,
+  // compared with level 1's below)
+  LevelOpts l2;
+  l2.trusted = true, l2.score_parents = false, l2.what = "grandchildren";
   HIP_TRY(d->io_out.ensure(t));
-  // (the children as parents are child records here too: compared with level 1's below)
-  EvalOpts as_children;
-  as_children.score_parents = false;
-  rc = expand_evaluate(ctx, *d, d_children, t, d->cur.children.p, g, mode, d->io_out.p, gr.d_grand_out, s, as_children);
+  rc = expand_level(ctx, *d, d_children, t, mode, d->io_out.p, gr.d_goffsets, gr.d_gmoves, gr.d_grand_out, gr.gcap, gtotal,
+                    s, l2);
   if (rc) return rc;
   // the children evaluated twice (level 1 as children, level 2 as parents) must agree
   HIP_TRY(d->sum.ensure(2));
@@ -2902,7 +2897,6 @@ static int expand2_on(gn_ctx *ctx, Dev *d, const gn_board *d_parents, size_t n, 
   unsigned long long cs[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(cs, d->sum.p, sizeof(cs), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if ((rc = check_plan(*d, s)) != GN_OK) return rc;
   if (cs[0] != cs[1]) return fail(GN_E_HIP, "depth 2: the children's level-1 and level-2 evaluations differ");
   return GN_OK;
 }
@@ -2929,7 +2923,7 @@ int gn_rank_lines2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parent
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
   HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
-                             ctx->P, d->tables, n_lines, d_lines, nullptr, call.s));
+                             ctx->P, d->tables.p, n_lines, d_lines, nullptr, call.s));
   return GN_OK;
 }
 
@@ -2944,7 +2938,7 @@ int gn_rank_lines2_history_device(gn_ctx *ctx, int device_slot, const gn_board *
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
   HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
-                             ctx->P, d->tables, n_lines, d_lines, &h, call.s));
+                             ctx->P, d->tables.p, n_lines, d_lines, &h, call.s));
   return GN_OK;
 }
 
@@ -2956,22 +2950,14 @@ int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parent
   DevCall call(*d);
   if (call.rc) return call.rc;
   const hipStream_t s = call.s;
-  // start, [count+scan], [total read], [write], [classify], [small], [big], [finalize], the
-  // planned big net's plan -> stream boundary, [score rule] (ends at e[9]), and the stream ->
-  // finish boundary (e[10])
-  const int NE = 12;
-  struct Events { // destroyed on every way out
-    std::vector<hipEvent_t> v;
-    ~Events() {
-      for (auto &e : v)
-        if (e) (void)hipEventDestroy(e);
-    }
-  } events{std::vector<hipEvent_t>((size_t)iters * NE + 2, nullptr)};
-  std::vector<hipEvent_t> &ev = events.v;
-  for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+  Events events;
+  hipEvent_t begin, end;
+  HIP_TRY(events.make({&begin, &end}));
+  std::vector<ExpEvents> marks((size_t)iters);
+  for (ExpEvents &e : marks) HIP_TRY(e.create(events));
   HIP_TRY(d->sum.ensure(2)); // [0] rows by write_children's formula, [1] rows the row stream gathered
   HIP_TRY(hipMemsetAsync(d->sum.p, 0, 2 * sizeof(unsigned long long), s));
-  HIP_TRY(hipEventRecord(ev[0], s));
+  HIP_TRY(hipEventRecord(begin, s));
   const bool pipe = pipelined(ctx, *d, mode, (size_t)iters);
   size_t t = 0;
   int rc = run_expansions(
@@ -2982,13 +2968,13 @@ int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parent
         // the last expansion)
         st.moves = pipe ? nullptr : d_moves;
         if (d_moves || d_child_out) st.cap = cap;
-        st.ev = &ev[2 + (size_t)NE * it];
+        st.ev = &marks[it];
         st.rows = it == 0 ? d->sum.p : nullptr;
         return GN_OK;
       },
       [&](size_t it, size_t children) -> int {
         t = children;
-        HIP_TRY(hipEventRecord(ev[2 + (size_t)NE * it + 9], s));
+        HIP_TRY(hipEventRecord(marks[it].scored, s));
         return GN_OK;
       });
   *total = t;
@@ -2996,31 +2982,44 @@ int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parent
   if (pipe && d_moves && t)
     HIP_TRY(hipMemcpyAsync(d_moves, d->cur.child_moves, t * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
   if (d_offsets) HIP_TRY(launch_offsets_u32(d->cur.offsets.p, n + 1, d_offsets, s));
-  HIP_TRY(hipEventRecord(ev[1], s));
-  HIP_TRY(hipEventSynchronize(ev[1]));
-  HIP_TRY(hipEventElapsedTime(ms_total, ev[0], ev[1]));
-  auto add_ms = [&](float &acc, size_t from, size_t to) -> hipError_t {
-    float ms = 0;
-    const hipError_t e = hipEventElapsedTime(&ms, ev[from], ev[to]);
-    acc += ms / (float)iters;
-    return e;
+  HIP_TRY(hipEventRecord(end, s));
+  HIP_TRY(hipEventSynchronize(end));
+  HIP_TRY(hipEventElapsedTime(ms_total, begin, end));
+  // The eight public stages (include/gpu_nnue.h) and the planned big net's three parts, each a span
+  // between two marks of an iteration, averaged over the iterations.  Pipelined, the front's stages
+  // are on the second stream, and two spans differ: the big net is its plan plus its row stream
+  // from the stream's own start (behind its wait for the plan), and the stream's part starts there.
+  using E = ExpEvents;
+  struct Span {
+    hipEvent_t E::*from, E::*to;
   };
-  // stage k from event k to k + 1 (score: 7 -> 9).  Pipelined, the front's stages are on the second
-  // stream and the big net is the plan (5 -> 8) plus the stream (11 -> 10, after its wait)
+  constexpr Span STAGE_SPANS[8] = {{&E::start, &E::counted},         {&E::counted, &E::total_read},
+                                   {&E::total_read, &E::written},    {&E::written, &E::classified},
+                                   {&E::classified, &E::small_done}, {&E::small_done, &E::big_done},
+                                   {&E::big_done, &E::finalized},    {&E::finalized, &E::scored}};
+  constexpr int BIG_NET = 5;
+  constexpr Span PLAN = {&E::small_done, &E::plan_done}, STREAM = {&E::plan_done, &E::stream_done},
+                 FINISH = {&E::stream_done, &E::big_done}, // (the sliced stream's finish)
+      PIPE_BIG_NET_STREAM = {&E::stream_begun, &E::big_done}, PIPE_STREAM = {&E::stream_begun, &E::stream_done};
   float stage[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pl = 0, st = 0, fi = 0;
-  for (int it = 0; it < iters; ++it) {
-    const size_t o = 2 + (size_t)NE * it;
+  for (const ExpEvents &e : marks) {
+    auto add_ms = [&](float &acc, const Span &sp) -> hipError_t {
+      float ms = 0;
+      const hipError_t r = hipEventElapsedTime(&ms, e.*sp.from, e.*sp.to);
+      acc += ms / (float)iters;
+      return r;
+    };
     for (int k = 0; k < 8 && stage_ms; ++k)
-      if (pipe && k == 5) {
-        HIP_TRY(add_ms(stage[k], o + 5, o + 8));
-        HIP_TRY(add_ms(stage[k], o + 11, o + 6));
+      if (pipe && k == BIG_NET) {
+        HIP_TRY(add_ms(stage[k], PLAN));
+        HIP_TRY(add_ms(stage[k], PIPE_BIG_NET_STREAM));
       } else {
-        HIP_TRY(add_ms(stage[k], o + k, o + (k < 7 ? k + 1 : 9)));
+        HIP_TRY(add_ms(stage[k], STAGE_SPANS[k]));
       }
     if (!d->cur.planned) continue; // the big net's two kernels apart
-    HIP_TRY(add_ms(pl, o + 5, o + 8));
-    HIP_TRY(add_ms(st, o + (pipe ? 11 : 8), o + 10)); // the stream launches
-    HIP_TRY(add_ms(fi, o + 10, o + 6));               // the sliced stream's finish
+    HIP_TRY(add_ms(pl, PLAN));
+    HIP_TRY(add_ms(st, pipe ? PIPE_STREAM : STREAM));
+    HIP_TRY(add_ms(fi, FINISH));
   }
   if (stage_ms) std::copy(stage, stage + 8, stage_ms);
   if (d->cur.planned) d->plan_ms = pl, d->stream_ms = st, d->finish_ms = fi;
@@ -3062,7 +3061,7 @@ int gn_random_games_device(gn_ctx *ctx, int device_slot, uint64_t seed, size_t f
   if (plies < 0 || plies > 1000) return fail(GN_E_INVALID, "plies out of range");
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
-  HIP_TRY(launch_random_games(seed, first_game, n_games, plies, d->tables, d_out, call.s));
+  HIP_TRY(launch_random_games(seed, first_game, n_games, plies, d->tables.p, d_out, call.s));
   return GN_OK;
 }
 
@@ -3265,7 +3264,7 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
     if (rc) return rc;
     const RankHistory h = {history.keys, history.n_keys, history.hist ? history.hist + a : nullptr};
     HIP_TRY(hipEventRecord(d.rev[0], s));
-    HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables, K,
+    HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables.p, K,
                                x.ln.p, h.hist ? &h : nullptr, s));
     HIP_TRY(hipEventRecord(d.rev[1], s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -3349,7 +3348,7 @@ int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {
   if (n) {
     HIP_TRY(d->sum.ensure(1));
     HIP_TRY(hipMemsetAsync(d->sum.p, 0, sizeof(unsigned long long), s));
-    HIP_TRY(launch_count_sum(d->frontier.p, n, d->tables, d->sum.p, s));
+    HIP_TRY(launch_count_sum(d->frontier.p, n, d->tables.p, d->sum.p, s));
     HIP_TRY(hipMemcpyAsync(&sum, d->sum.p, sizeof(sum), hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(hipStreamSynchronize(s));

@@ -124,7 +124,7 @@ static_assert(sizeof(TileDesc) == 192, "TileDesc is 192 bytes");
 // phases: PLAN_PHASE (the pinfo reset and plan_kernel) and / or STREAM_PHASE (the stream
 // launches), so that an expansion's plan can run on another stream than its row stream (the
 // expansion pipeline, gpu_nnue.hip): the two calls take the same PlanStreamArgs, and differ in
-// phases, swz and the events.
+// phases and swz.
 constexpr int PLAN_PHASE = 1, STREAM_PHASE = 2;
 struct PlanStreamArgs {
   const gn_board *parents = nullptr;
@@ -161,8 +161,6 @@ struct PlanStreamArgs {
   size_t npos = 0;
   int2 *pinfo = nullptr;
   int swz = 0;
-  hipEvent_t mid = nullptr;                     // (optional) recorded between the kernels
-  hipEvent_t fin = nullptr, streamed = nullptr; // (optional) recorded after the stream launches
 };
 hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int phases, hipStream_t s);
 // GN_MODE_FULL preparation: need_small = valid && |simple_eval| > threshold,

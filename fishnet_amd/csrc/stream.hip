@@ -1494,10 +1494,6 @@ hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int
   const int scr = K > 1 && a.kc; // the king cache's rows (the chained walk itself needs no scratch)
   const uint32_t nb = (uint32_t)((n + K - 1) / K), B0 = 0, B1 = nb; // every block of the n parents
   const unsigned pg = (nb + PLAN_WAVES - 1) / PLAN_WAVES, g = a.swz == 1 ? 8 * ((nb + 7) / 8) : nb + nb / 16 + 8; // (stream_eval_kernel: claims)
-  auto stream_done = [&] {
-    if (a.fin) (void)hipEventRecord(a.fin, s);
-    if (a.streamed) (void)hipEventRecord(a.streamed, s);
-  };
   if (net.L1 == 3072) {
     const bool sliced = a.slices == 3 && a.part && a.pinfo;
     if (do_plan) {
@@ -1509,7 +1505,6 @@ hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int
                          a.need_parent, a.need_child, next_slot, (uint32_t)n, K, B0, B1, kc, a.eoff, a.ent, a.tiles,
                          a.btiles, a.rows_out, a.pads_out, a.err, sliced ? a.pinfo : nullptr,
                          sliced ? ps::field_xu(3072, 3) : ps::field_xu(3072, 1), sliced ? ps::field_hu(3072, 3) : ps::field_hu(3072, 1));
-      if (a.mid) (void)hipEventRecord(a.mid, s);
     }
     if (!do_stream) {
     } else if (sliced) { // three launches over 1,024 columns each (claim counters pool[64 + 8 slice ..]);
@@ -1518,25 +1513,21 @@ hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int
         hipLaunchKernelGGL((stream_eval_kernel<3072, 3>), dim3(g), dim3(128), 0, s, net, a.offsets, (uint32_t)n, K, B0,
                            B1, a.swz, a.eoff, a.ent, a.tiles, a.btiles, a.order, a.out_parent, a.out_child, a.pool, scr,
                            a.err, a.pool + 64 + 8 * sl, sl, a.part, (uint64_t)a.npos, a.pinfo);
-      stream_done();
     } else {
       hipLaunchKernelGGL((stream_eval_kernel<3072>), dim3(g), dim3(384), 0, s, net, a.offsets, (uint32_t)n, K, B0, B1,
                          a.swz, a.eoff, a.ent, a.tiles, a.btiles, a.order, a.out_parent, a.out_child, a.pool, scr, a.err,
                          a.pool + 64, 0, nullptr, (uint64_t)0, nullptr);
-      stream_done();
     }
   } else if (net.L1 == 1024) {
     if (do_plan) {
       hipLaunchKernelGGL((plan_kernel<1024>), dim3(pg), dim3(GN_FRONT_WG), 0, s, net, a.parents, a.offsets, a.deltas,
                          a.need_parent, a.need_child, next_slot, (uint32_t)n, K, B0, B1, kc, a.eoff, a.ent, a.tiles,
                          a.btiles, a.rows_out, a.pads_out, a.err, nullptr, ps::field_xu(1024, 1), ps::field_hu(1024, 1));
-      if (a.mid) (void)hipEventRecord(a.mid, s);
     }
     if (do_stream) {
       hipLaunchKernelGGL((stream_eval_kernel<1024>), dim3(g), dim3(128), 0, s, net, a.offsets, (uint32_t)n, K, B0, B1,
                          a.swz, a.eoff, a.ent, a.tiles, a.btiles, a.order, a.out_parent, a.out_child, a.pool, scr, a.err,
                          a.pool + 64, 0, nullptr, (uint64_t)0, nullptr);
-      stream_done();
     }
   } else {
     return hipErrorInvalidValue;

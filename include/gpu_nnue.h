@@ -695,19 +695,6 @@ GN_API int gn_evaluate_device(gn_ctx *ctx, int device_slot, const gn_board *d_bo
 GN_API int gn_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, int mode,
                      gn_eval *d_parent_out, uint32_t *d_offsets, gn_board *d_children,
                      uint16_t *d_moves, gn_eval *d_child_out, size_t cap, size_t *total, void *stream);
-/* Time `iters` complete expansions of device-resident parents (child count +
- * scan + child generation with deltas + evaluation of parents and children in
- * `mode` + the parents' score rule).  Outputs go to the caller's device buffers when given (d_parent_out[n],
- * d_offsets[n + 1], d_moves[cap], d_child_out[cap]; GN_E_CAPACITY when the
- * children exceed cap), else to library-owned buffers; every iteration writes the
- * same values, so after the call they hold the timed expansion's results.
- * *total = children per expansion;
- * stage_ms (optional, length 8) = average ms of [count+scan, total read-back,
- * write children, classify, small net, big net, finalize, score rule]; ft_rows (optional)
- * = feature-transformer rows one incremental expansion gathers: for the big
- * nets the row stream's own count (bias, carry and king-cache rows included:
- * GN_OPT_CHAIN, GN_OPT_KING_CACHE), else parent refreshes + child deltas /
- * king-move refreshes; 0 when not incremental. */
 /* Ranks the outputs of a preceding gn_expand_device of the same parents (d_offsets, d_moves,
  * d_child_out as it wrote them): d_lines[i * n_lines + k] = line k + 1 of parent i (gn_line).
  * Asynchronous on `stream` (NULL = the context's own), no read-back.  n_lines outside
@@ -759,6 +746,19 @@ GN_API int gn_rank_lines2_history_device(gn_ctx *ctx, int device_slot, const gn_
                                          const uint32_t *d_goffsets, const uint16_t *d_gmoves,
                                          const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
                                          const gn_history *d_hist, int n_lines, gn_line2 *d_lines, void *stream);
+/* Time `iters` complete expansions of device-resident parents (child count +
+ * scan + child generation with deltas + evaluation of parents and children in
+ * `mode` + the parents' score rule).  Outputs go to the caller's device buffers when given (d_parent_out[n],
+ * d_offsets[n + 1], d_moves[cap], d_child_out[cap]; GN_E_CAPACITY when the
+ * children exceed cap), else to library-owned buffers; every iteration writes the
+ * same values, so after the call they hold the timed expansion's results.
+ * *total = children per expansion;
+ * stage_ms (optional, length 8) = average ms of [count+scan, total read-back,
+ * write children, classify, small net, big net, finalize, score rule]; ft_rows (optional)
+ * = feature-transformer rows one incremental expansion gathers: for the big
+ * nets the row stream's own count (bias, carry and king-cache rows included:
+ * GN_OPT_CHAIN, GN_OPT_KING_CACHE), else parent refreshes + child deltas /
+ * king-move refreshes; 0 when not incremental. */
 GN_API int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, int mode,
                                  int iters, float *ms_total, size_t *total, float *stage_ms, uint64_t *ft_rows,
                                  gn_eval *d_parent_out, uint32_t *d_offsets, uint16_t *d_moves,
