@@ -387,7 +387,22 @@ struct Dev {
     DevBuf<gn_board> ch;
     DevBuf<uint16_t> mv, gmv;
     DevBuf<gn_line2> ln;
+    DevBuf<int32_t> gext; // the extended calls: the grandchildren's check extensions
   } l2;
+  // the check extension of one expansion level (extend_checks): the selection and its scan, the
+  // selected leaves' indices, boards, records and rule values, the count of extended ones; ext:
+  // the one-ply extended games call's per-chunk extensions
+  struct Extend {
+    DevBuf<uint64_t> sel, pos;
+    DevBuf<uint32_t> idx;
+    DevBuf<gn_board> boards;
+    DevBuf<gn_eval> rec;
+    DevBuf<int32_t> sv;
+    DevBuf<unsigned long long> count;
+  } ex;
+  DevBuf<int32_t> ext;
+  double t_extend = 0;     // the extension stage of the last host-buffer call (GN_STAT_EXTEND_NS), ms
+  uint64_t n_extended = 0; // ... and the leaves it extended (GN_STAT_EXTENDED_LEAVES)
   DevBuf<gn_board> roots, rboards, par;
   DevBuf<uint64_t> moff;
   DevBuf<uint16_t> codes, smoves;
@@ -1137,6 +1152,57 @@ static int resolve_scores(gn_ctx *ctx, Dev &d, const gn_board *boards, size_t n,
   return GN_OK;
 }
 
+// ---------------------------------------------------- check extension ----
+// The check extension of one expansion level (include/gpu_nnue.h, gn_extend_checks_device): the
+// leaves [offsets[i], offsets[i + 1]) of the n parents (moves, records rec; the parents unpacked
+// with 64-bit offsets as write_children left them, or packed with the C-ABI's 32-bit offsets).
+// ext[j] = value(leaf j, 2) of the score rule where leaf j is in check with a legal move,
+// GN_NOT_EXTENDED elsewhere; *extended = how many.  The leaves whose records say in check are
+// selected and their boards made (extend_boards_kernel), then they are positions: evaluate_on and
+// resolve_scores with its sv output, as gn_evaluate_device runs them, on the extension's own
+// records -- resolve_scores rewrites score / flags / best_move of what it is given, so it never
+// sees rec.  A selected leaf without a legal move is no position in check with a move to the score
+// rule: its value stays GN_NOT_EXTENDED.  Synchronous (the counts size the next launches; every
+// buffer is sized from a read-back count before anything is queued on it); the stream is idle on
+// return.  d.mu held, inside a sequence on s, no expansion in flight on d.cur.
+template <class Parent, class Off>
+static int extend_checks(gn_ctx *ctx, Dev &d, const Parent *parents, size_t n, const Off *offsets,
+                         const uint16_t *moves, const gn_eval *rec, size_t total, int mode, int32_t *ext,
+                         size_t *extended, hipStream_t s) {
+  *extended = 0;
+  if (mode < GN_MODE_FULL || mode > GN_MODE_SMALL) return fail(GN_E_INVALID, "bad mode %d", mode);
+  if ((mode != GN_MODE_SMALL && !d.has[BIG]) || (mode != GN_MODE_BIG && !d.has[SMALL]))
+    return fail(GN_E_NONET, "mode %d needs a network that is not loaded", mode);
+  if (!total || !n) return GN_OK;
+  if (total > 0x7FFFFFFFull) return fail(GN_E_INVALID, "the check extension supports < 2^31 leaves per call");
+  Dev::Extend &X = d.ex;
+  HIP_TRY(X.sel.ensure(total + 1));
+  HIP_TRY(X.pos.ensure(total + 1));
+  HIP_TRY(launch_extend_select(rec, total, X.sel.p, ext, s));
+  HIP_TRY(exclusive_scan_u64(X.sel.p, X.pos.p, total + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap, s));
+  uint64_t m = 0;
+  HIP_TRY(hipMemcpyAsync(&m, X.pos.p + total, sizeof(m), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (!m) return GN_OK;
+  if (m > total) return fail(GN_E_HIP, "check extension: %zu selected of %zu leaves", (size_t)m, total);
+  HIP_TRY(X.idx.ensure(m));
+  HIP_TRY(X.boards.ensure(m));
+  HIP_TRY(X.rec.ensure(m));
+  HIP_TRY(X.sv.ensure(m));
+  HIP_TRY(X.count.ensure(1));
+  HIP_TRY(launch_extend_boards(parents, n, offsets, moves, X.sel.p, X.pos.p, total, d.tables.p, X.idx.p, X.boards.p, X.sv.p,
+                               s));
+  int rc = evaluate_on(ctx, d, X.boards.p, m, mode, X.rec.p, s);
+  if (!rc) rc = resolve_scores(ctx, d, X.boards.p, m, mode, X.rec.p, X.sv.p, s, 2);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(X.count.p, 0, sizeof(unsigned long long), s));
+  HIP_TRY(launch_extend_scatter(X.idx.p, X.sv.p, m, ext, X.count.p, s));
+  unsigned long long cnt = 0;
+  HIP_TRY(hipMemcpyAsync(&cnt, X.count.p, sizeof(cnt), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *extended = (size_t)cnt;
+  return GN_OK;
+}
 // ------------------------------------------------------- one level -------
 // expand_level's optional arguments.
 struct LevelOpts {
@@ -1464,6 +1530,18 @@ static double ms_since(Clock::time_point t) {
   return std::chrono::duration<double, std::milli>(Clock::now() - t).count();
 }
 
+// The check extension (extend_checks) as a stage of a host-buffer call: its time and count into the
+// device's statistics
+template <class Parent, class Off>
+static int extend_stage(gn_ctx *ctx, Dev &d, const Parent *parents, size_t n, const Off *offsets,
+                        const uint16_t *moves, const gn_eval *rec, size_t total, int mode, int32_t *ext, hipStream_t s) {
+  const auto t0 = Clock::now();
+  size_t ne = 0;
+  const int rc = extend_checks(ctx, d, parents, n, offsets, moves, rec, total, mode, ext, &ne, s);
+  d.t_extend += ms_since(t0), d.n_extended += ne;
+  return rc;
+}
+
 // Every device lock, in slot order: a host-buffer call holds them all from here to its return.
 static std::vector<std::unique_lock<std::mutex>> lock_devices(gn_ctx *ctx) {
   std::vector<std::unique_lock<std::mutex>> locks;
@@ -1497,7 +1575,7 @@ static int run_shards(gn_ctx *ctx, const std::vector<size_t> &b, F &&f) {
 }
 
 static void reset_host_stats(gn_ctx *ctx) {
-  for (auto &dp : ctx->devs) dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = dp->t_keys = 0;
+  for (auto &dp : ctx->devs) dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = dp->t_keys = dp->t_extend = 0, dp->n_extended = 0;
 }
 
 // Chunk bounds of a shard's m parents: cut only where `starts` allows (the first parent of each
@@ -1581,11 +1659,14 @@ static bool pipelined(const gn_ctx *ctx, const Dev &d, int mode, size_t count) {
 // parents + children of the largest step, for which the sliced stream's partial sums are sized
 // before any front runs (otherwise step 0's front sizes them): a later front runs beside a back
 // half that reads them and may not reallocate them (part_locked).
+// serial: one after another whatever GN_OPT_EXPAND_PIPELINE says (done runs a blocking stage of its
+// own on the device's shared buffers: the one-ply extended games call).
 template <class Step, class Done>
-static int run_expansions(gn_ctx *ctx, Dev &d, int mode, size_t count, size_t largest, Step &&step, Done &&done) {
+static int run_expansions(gn_ctx *ctx, Dev &d, int mode, size_t count, size_t largest, Step &&step, Done &&done,
+                          bool serial = false) {
   if (!count) return GN_OK;
   const hipStream_t s = d.stream;
-  const bool pipe = pipelined(ctx, d, mode, count);
+  const bool pipe = !serial && pipelined(ctx, d, mode, count);
   const hipStream_t F = pipe ? d.front : s; // the front halves' stream
   struct Guard { // on every way out: nothing of a failed call's front may still run
     Dev &d;
@@ -1682,6 +1763,9 @@ struct ExpandOut {
   // gn_evaluate_games_lines_history: the shard's keys (device, n_keys of them) and one gn_history per
   // parent of the shard (device; chunk c's at hist + chunks[c]); hist NULL: the plain ranking
   RankHistory history = NO_HISTORY;
+  // gn_evaluate_games_lines_extended: each chunk's children in check are extended before the
+  // ranking (extend_stage), and the chunks run one after another
+  bool extend = false;
 };
 // Pass 2 of a shard (see above).  off: the shard's child offsets from pass 1.
 static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m, int mode,
@@ -1697,6 +1781,7 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
     HIP_TRY(d.co2[k].ensure(maxc));
     if (n_lines) HIP_TRY(d.ln2[k].ensure(maxp * (size_t)n_lines));
     else HIP_TRY(d.cc2[k].ensure(maxc));
+    if (o.extend) HIP_TRY(d.ext.ensure(maxc));
     HIP_TRY(d.mv2[k].ensure(maxc));
   }
   int drc[2] = {GN_OK, GN_OK};
@@ -1762,9 +1847,15 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
           // (d.cur's offsets and unpacked parents are this chunk's: the front that overwrites the
           // set is queued after the synchronisation below)
           const RankHistory h = {o.history.keys, o.history.n_keys, o.history.hist ? o.history.hist + pa : nullptr};
+          // (extended: the chunks run serially, so nothing else is queued on the device while the
+          // extension evaluates in the current set's and the score levels' buffers; t == 0: no entry
+          // is read)
+          if (o.extend)
+            if (int r = extend_stage(ctx, d, d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, t, mode, d.ext.p, s))
+              return r;
           HIP_TRY(hipEventRecord(d.rev[0], s));
           HIP_TRY(launch_rank_children(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P, d.tables.p,
-                                       n_lines, d.ln2[k].p, h.hist ? &h : nullptr, s));
+                                       n_lines, d.ln2[k].p, h.hist ? &h : nullptr, o.extend ? d.ext.p : nullptr, s));
           HIP_TRY(hipEventRecord(d.rev[1], s));
         } else {
           HIP_TRY(launch_pack_children(d.co2[k].p, t, d.cc2[k].p, s));
@@ -1781,7 +1872,8 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
         HIP_TRY(hipEventRecord(d.cev[k], s));
         drain_chunk(k, pa, mp, t, cb);
         return GN_OK;
-      });
+      },
+      o.extend);
   const auto tt = Clock::now();
   for (int k = 0; k < 2; ++k) {
     const int r = join(k);
@@ -2011,6 +2103,7 @@ struct GamesCall {
   uint64_t total = 0;            // positions
   bool all_in_place = true;
   std::string last_err;          // the last failed game's message (gn_last_error after GN_OK)
+  bool extend = false;           // the _extended calls: the lines' leaves in check take their check extension
 };
 
 // host: root FENs parsed, UCI moves tokenized (the wire form, AcquireResponseBody.moves); games
@@ -2237,6 +2330,7 @@ static int games_expand(const GamesCall &c, GameShard &sh, Dev &d) {
   ExpandOut o = c.n_lines ? ExpandOut{rec, nullptr, nullptr, c.n_lines, ln}
                           : ExpandOut{rec, c.child_moves + sh.child_base, c.child_out + sh.child_base};
   if (c.history) o.history = RankHistory{d.rkeys.p, d.n_rkeys, d.hist.p};
+  o.extend = c.extend;
   return expand_pipelined(c.ctx, d, sh.parents_of(d), sh.m, c.mode, sh.off,
                           chunk_plan(sh.m, sh.starts, c.ctx->chunk_parents), o);
 }
@@ -2346,10 +2440,29 @@ int gn_evaluate_games_lines_history(gn_ctx *ctx, const gn_game *games, size_t n_
 
 static int evaluate_games_lines2(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines, bool history,
                                  uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
-                                 size_t position_cap, gn_line2 *lines) {
+                                 size_t position_cap, gn_line2 *lines, bool extend = false) {
   if (int rc = check_n_lines(n_lines)) return rc;
-  return evaluate_games({ctx, games, n_games, mode, 0, n_lines, history, position_offsets, nullptr, game_status,
-                         position_out, position_cap, 0, nullptr, nullptr, nullptr, lines});
+  GamesCall c{ctx, games, n_games, mode, 0, n_lines, history, position_offsets, nullptr, game_status,
+              position_out, position_cap, 0, nullptr, nullptr, nullptr, lines};
+  c.extend = extend;
+  return evaluate_games(std::move(c));
+}
+
+int gn_evaluate_games_lines2_extended(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                      int history, uint32_t *position_offsets, int32_t *game_status,
+                                      gn_eval *position_out, size_t position_cap, gn_line2 *lines) {
+  return evaluate_games_lines2(ctx, games, n_games, mode, n_lines, history != 0, position_offsets, game_status,
+                               position_out, position_cap, lines, true);
+}
+
+int gn_evaluate_games_lines_extended(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                     int history, uint32_t *position_offsets, int32_t *game_status,
+                                     gn_eval *position_out, size_t position_cap, gn_line *lines) {
+  if (int rc = check_n_lines(n_lines)) return rc;
+  GamesCall c{ctx, games, n_games, mode, 1, n_lines, history != 0, position_offsets, nullptr, game_status,
+              position_out, position_cap, 0, nullptr, nullptr, lines};
+  c.extend = true;
+  return evaluate_games(std::move(c));
 }
 
 int gn_evaluate_games_lines2(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
@@ -2803,7 +2916,7 @@ int gn_rank_children_device(gn_ctx *ctx, int device_slot, const gn_board *d_pare
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
   HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables.p, n_lines, d_lines, nullptr,
-                               call.s));
+                               nullptr, call.s));
   return GN_OK;
 }
 
@@ -2828,7 +2941,54 @@ int gn_rank_children_history_device(gn_ctx *ctx, int device_slot, const gn_board
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
   HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables.p, n_lines, d_lines, &h,
-                               call.s));
+                               nullptr, call.s));
+  return GN_OK;
+}
+
+int gn_extend_checks_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
+                            const uint16_t *d_moves, const gn_eval *d_rec, size_t total, int mode, int32_t *d_ext,
+                            size_t *extended, void *stream) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d || !extended) return fail(GN_E_INVALID, "bad argument");
+  *extended = 0;
+  if (total && (!n || !d_parents || !d_offsets || !d_moves || !d_rec || !d_ext)) return fail(GN_E_INVALID, "NULL buffer");
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  const int rc = extend_checks(ctx, *d, d_parents, n, d_offsets, d_moves, d_rec, total, mode, d_ext, extended, call.s);
+  if (rc) return rc;
+  HIP_TRY(call.sg->finish()); // blocking (gpu_nnue.h): d_ext is written when the call returns
+  return GN_OK;
+}
+
+int gn_rank_children_extended_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                     const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out,
+                                     const uint64_t *d_keys, size_t n_keys, const gn_history *d_hist,
+                                     const int32_t *d_ext, int n_lines, gn_line *d_lines, void *stream) {
+  const RankHistory h = {d_keys, n_keys, d_hist};
+  Dev *d;
+  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, d_hist ? &h : nullptr, d))
+    return rc;
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables.p, n_lines, d_lines,
+                               d_hist ? &h : nullptr, d_ext, call.s));
+  return GN_OK;
+}
+
+int gn_rank_lines2_extended_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                   const uint32_t *d_offsets, const gn_board *d_children, const gn_eval *d_child_out,
+                                   const uint16_t *d_moves, const uint32_t *d_goffsets, const uint16_t *d_gmoves,
+                                   const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
+                                   const gn_history *d_hist, const int32_t *d_gext, int n_lines, gn_line2 *d_lines,
+                                   void *stream) {
+  const RankHistory h = {d_keys, n_keys, d_hist};
+  Dev *d;
+  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, d_hist ? &h : nullptr, d))
+    return rc;
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
+                             ctx->P, d->tables.p, n_lines, d_lines, d_hist ? &h : nullptr, d_gext, call.s));
   return GN_OK;
 }
 
@@ -2923,7 +3083,7 @@ int gn_rank_lines2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parent
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
   HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
-                             ctx->P, d->tables.p, n_lines, d_lines, nullptr, call.s));
+                             ctx->P, d->tables.p, n_lines, d_lines, nullptr, nullptr, call.s));
   return GN_OK;
 }
 
@@ -2938,7 +3098,7 @@ int gn_rank_lines2_history_device(gn_ctx *ctx, int device_slot, const gn_board *
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
   HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
-                             ctx->P, d->tables.p, n_lines, d_lines, &h, call.s));
+                             ctx->P, d->tables.p, n_lines, d_lines, &h, nullptr, call.s));
   return GN_OK;
 }
 
@@ -3193,6 +3353,18 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
     *value = (int64_t)(m * 1e6);
     return GN_OK;
   }
+  case GN_STAT_EXTEND_NS: { // the last host-buffer call's check extension, the slowest device
+    double m = 0;
+    for (auto &dp : ctx->devs) m = std::max(m, dp->t_extend);
+    *value = (int64_t)(m * 1e6);
+    return GN_OK;
+  }
+  case GN_STAT_EXTENDED_LEAVES: { // ... and its extended leaves, summed over the devices
+    int64_t sum = 0;
+    for (auto &dp : ctx->devs) sum += (int64_t)dp->n_extended;
+    *value = sum;
+    return GN_OK;
+  }
   case GN_STAT_ZERO_ROW_ENTRIES: // ... and its entries on the zero row summed
   case GN_STAT_SCRATCH_PADS: { // read-only: the last planned expansion's GN_SCR_GAP no-op entries, summed
     int64_t sum = 0;
@@ -3233,8 +3405,10 @@ int gn_expand_and_evaluate(gn_ctx *ctx, const char *const *parent_fens, size_t n
 // keys and its parents' gn_history entries (hist NULL: the plain one) -- and one download of the chunk's parent records and
 // lines into out / lines (the shard's first parent's).  The chunks need no cut at game starts: the
 // keys are the whole shard's.
+// extend: the grandchildren in check are extended after the expansion (extend_stage; the children
+// as parents, the library's own boards), and the ranking takes their values.
 static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m, int mode, int K, gn_eval *out,
-                         gn_line2 *lines, const RankHistory &history) {
+                         gn_line2 *lines, const RankHistory &history, bool extend) {
   hipStream_t s = d.stream;
   Dev::Lines2 &x = d.l2;
   // 1,024 parents are ~1 M grandchildren: a few hundred MB of records, boards and partial sums
@@ -3263,9 +3437,13 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
                         &size_grand);
     if (rc) return rc;
     const RankHistory h = {history.keys, history.n_keys, history.hist ? history.hist + a : nullptr};
+    if (extend) { // (t == 0 or g == 0: nothing is read)
+      HIP_TRY(x.gext.ensure(std::max<size_t>(g, 1)));
+      if ((rc = extend_stage(ctx, d, x.ch.p, t, x.goff.p, x.gmv.p, x.gco.p, g, mode, x.gext.p, s)) != GN_OK) return rc;
+    }
     HIP_TRY(hipEventRecord(d.rev[0], s));
     HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables.p, K,
-                               x.ln.p, h.hist ? &h : nullptr, s));
+                               x.ln.p, h.hist ? &h : nullptr, extend ? x.gext.p : nullptr, s));
     HIP_TRY(hipEventRecord(d.rev[1], s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0;
@@ -3283,7 +3461,7 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
 // gn_evaluate_lines2: the boards sharded equally over the devices, each shard uploaded and run
 // through lines2_chunks
 static int lines2_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int mode, int K, gn_eval *out,
-                              gn_line2 *lines) {
+                              gn_line2 *lines, bool extend) {
   const size_t nd = ctx->devs.size();
   std::vector<size_t> b(nd + 1);
   partition(nullptr, n, (int)nd, b.data());
@@ -3294,7 +3472,7 @@ static int lines2_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int
     HIP_TRY(hipMemcpyAsync(d.par.p, boards + lo, (hi - lo) * sizeof(gn_board), hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipStreamSynchronize(d.stream));
     d.t_upload += ms_since(t0);
-    return lines2_chunks(ctx, d, d.par.p, hi - lo, mode, K, out + lo, lines + lo * (size_t)K, NO_HISTORY);
+    return lines2_chunks(ctx, d, d.par.p, hi - lo, mode, K, out + lo, lines + lo * (size_t)K, NO_HISTORY, extend);
   });
 }
 
@@ -3305,18 +3483,28 @@ static int games_lines2(const GamesCall &c, GameShard &sh, Dev &d) {
   if (rc) return rc;
   gn_line2 *const ln = sh.in_place ? c.lines2 + sh.p0 * (size_t)c.n_lines : sh.l2res.data();
   return lines2_chunks(c.ctx, d, sh.parents_of(d), sh.m, c.mode, c.n_lines, sh.records_of(c.position_out), ln,
-                       c.history ? RankHistory{d.rkeys.p, d.n_rkeys, d.hist.p} : NO_HISTORY);
+                       c.history ? RankHistory{d.rkeys.p, d.n_rkeys, d.hist.p} : NO_HISTORY, c.extend);
 }
 
-int gn_evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,
-                       gn_line2 *lines) {
+static int evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,
+                           gn_line2 *lines, bool extend) {
   if (!slot(ctx, 0)) return fail(GN_E_INVALID, "bad context");
   if (int rc = check_n_lines(n_lines)) return rc;
   if (n && (!fens || !out || !lines)) return fail(GN_E_INVALID, "NULL argument");
   if (!n) return GN_OK;
   return on_packed_fens(ctx, fens, n, [&](const gn_board *boards) -> int {
-    return lines2_boards_host(ctx, boards, n, mode, n_lines, out, lines);
+    return lines2_boards_host(ctx, boards, n, mode, n_lines, out, lines, extend);
   });
+}
+
+int gn_evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,
+                       gn_line2 *lines) {
+  return evaluate_lines2(ctx, fens, n, mode, n_lines, out, lines, false);
+}
+
+int gn_evaluate_lines2_extended(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,
+                                gn_line2 *lines) {
+  return evaluate_lines2(ctx, fens, n, mode, n_lines, out, lines, true);
 }
 
 int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {

@@ -265,6 +265,8 @@ hipError_t launch_pack_children(const gn_eval *in, size_t n, gn_child *out, hipS
 // read only where the parent has children), or packed with the C-ABI's 32-bit offsets.
 // With history (include/gpu_nnue.h at gn_history) the game-history draws are applied: hist[i] names
 // parent i's game so far in keys[0, n_keys) (position_key of each position).  NULL: the plain ranking.
+// With ext (include/gpu_nnue.h, the check-extended calls): ext[c] is child c's check extension, or
+// GN_NOT_EXTENDED where it keeps its static value.  NULL: no extension, today's kernels.
 struct RankHistory {
   const uint64_t *keys;
   size_t n_keys;
@@ -272,10 +274,10 @@ struct RankHistory {
 };
 hipError_t launch_rank_children(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
                                 const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                gn_line *lines, const RankHistory *history, hipStream_t s);
+                                gn_line *lines, const RankHistory *history, const int32_t *ext, hipStream_t s);
 hipError_t launch_rank_children(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
                                 const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                gn_line *lines, const RankHistory *history, hipStream_t s);
+                                gn_line *lines, const RankHistory *history, const int32_t *ext, hipStream_t s);
 // keys[i] = position_key of boards[i], a lane per board.  gate: a caller's boards (unpack; a
 // rejected board's key is 0); else the library's own canonical boards (unpack_fields)
 hipError_t launch_position_keys(const gn_board *boards, size_t n, bool gate, const Tables *tables, uint64_t *keys,
@@ -288,12 +290,27 @@ hipError_t launch_position_keys(const gn_board *boards, size_t n, bool gate, con
 // the host path feeds it the same packed parents and 32-bit offsets as the C-ABI: level 2 of the
 // expansion has overwritten the buffer set's unpacked parents and 64-bit offsets by then.)
 // history: the game-history draws at both levels (include/gpu_nnue.h at gn_line2 and gn_history),
-// hist[i] naming parent i's game so far as above; NULL: the plain ranking.
+// hist[i] naming parent i's game so far as above; NULL: the plain ranking.  gext: the grandchildren's
+// check extensions (as ext above), NULL: none.
 hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t *offsets, const gn_board *children,
                               const gn_eval *rec, const uint16_t *moves, const uint32_t *goffsets,
                               const uint16_t *gmoves, const gn_eval *grec, const gn_eval_params &P,
                               const Tables *tables, int K, gn_line2 *lines, const RankHistory *history,
-                              hipStream_t s);
+                              const int32_t *gext, hipStream_t s);
+// Check extension of one expansion level (gpu_nnue.hip extend_checks): select (sel[total + 1] from
+// the leaf records' GN_FLAG_IN_CHECK, ext[total] = GN_NOT_EXTENDED), boards (pos = exclusive scan of
+// sel: the selected leaves' boards sb, leaf indices idx and sv = GN_NOT_EXTENDED, compacted; the
+// parents unpacked with 64-bit offsets, or packed with the C-ABI's 32-bit offsets, as for
+// launch_rank_children), scatter (ext[idx[k]] = sv[k], *extended += those that are values).
+hipError_t launch_extend_select(const gn_eval *rec, size_t total, uint64_t *sel, int32_t *ext, hipStream_t s);
+hipError_t launch_extend_boards(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
+                                const uint64_t *sel, const uint64_t *pos, size_t total, const Tables *tables,
+                                uint32_t *idx, gn_board *sb, int32_t *sv, hipStream_t s);
+hipError_t launch_extend_boards(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
+                                const uint64_t *sel, const uint64_t *pos, size_t total, const Tables *tables,
+                                uint32_t *idx, gn_board *sb, int32_t *sv, hipStream_t s);
+hipError_t launch_extend_scatter(const uint32_t *idx, const int32_t *sv, size_t m, int32_t *ext,
+                                 unsigned long long *extended, hipStream_t s);
 // narrowing copy of offsets for the C-ABI
 hipError_t launch_offsets_u32(const uint64_t *in, size_t n, uint32_t *out, hipStream_t s);
 // exclusive scan of n + 1 counts (counts[n] must be 0); temp grows on demand

@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include <hipcub/hipcub.hpp>
 
@@ -1111,17 +1112,33 @@ struct SortKey {
   static __device__ __forceinline__ uint32_t payload(uint64_t k) { return (uint32_t)(k >> FLAGS & ((1ull << PAYLOAD) - 1)); }
   static __device__ __forceinline__ uint32_t flags(uint64_t k) { return (uint32_t)(k & ((1u << FLAGS) - 1)); }
 };
-// The flags, in one order everywhere; the draw bit exists in the history variants' keys only.
-constexpr uint32_t KEY_CHECK = 1, KEY_NO_MOVES = 2, KEY_DRAW = 4;
+// The flags, in one order everywhere; the draw bit exists in the history variants' keys only, the
+// searched bit (the leaf's value is its check extension) in the extended variants' only, where the
+// draw bit's place is kept (always clear without history) so that the order holds.
+constexpr uint32_t KEY_CHECK = 1, KEY_NO_MOVES = 2, KEY_DRAW = 4, KEY_SEARCHED = 8;
 // a line of rank_children_kernel: payload 0xFFFF - move (the smaller move first)
-template <bool HIST> using LineKey = SortKey<16, HIST ? 3 : 2>;
-// a grandchild of rank_lines2_kernel: payload 0xFFFF - reply; its one flag is the draw bit (1: drawn)
-template <bool HIST> using ReplyKey = SortKey<16, HIST ? 1 : 0>;
+template <bool HIST, bool EXT = false> using LineKey = SortKey<16, EXT ? 4 : HIST ? 3 : 2>;
+// a grandchild of rank_lines2_kernel: payload 0xFFFF - reply; its flags are the draw bit (1: drawn)
+// and, extended, the searched bit above it
+constexpr uint32_t REPLY_DRAW = 1, REPLY_SEARCHED = 2;
+template <bool HIST, bool EXT = false> using ReplyKey = SortKey<16, EXT ? 2 : HIST ? 1 : 0>;
 // a child of rank_lines2_kernel: payload (0xFFFF - move) << 16 | reply (moves are distinct; the reply rides along)
-template <bool HIST> using ChildKey = SortKey<32, HIST ? 3 : 2>;
+template <bool HIST, bool EXT = false> using ChildKey = SortKey<32, EXT ? 4 : HIST ? 3 : 2>;
 __device__ __forceinline__ uint32_t line_flags(uint32_t kf) {
   return ((kf & KEY_CHECK) ? GN_FLAG_IN_CHECK : 0u) | ((kf & KEY_NO_MOVES) ? GN_FLAG_NO_MOVES : 0u) |
-         ((kf & KEY_DRAW) ? GN_FLAG_DRAW : 0u);
+         ((kf & KEY_DRAW) ? GN_FLAG_DRAW : 0u) | ((kf & KEY_SEARCHED) ? GN_FLAG_SEARCHED : 0u);
+}
+// The ranking kernels' optional trailing arguments: nothing, a RankHistory (the game-history draws),
+// a RankExtension (the leaves' check extensions), or both in that order.  has_arg / arg_of find one
+// by its type.
+struct RankExtension {
+  const int32_t *ext; // E of each leaf where the extension applies, GN_NOT_EXTENDED elsewhere
+};
+template <class T, class... A> constexpr bool has_arg = (std::is_same_v<T, A> || ...);
+template <class T, class A0, class... A>
+__device__ __forceinline__ const T &arg_of(const A0 &a0, const A &...a) {
+  if constexpr (std::is_same_v<T, A0>) return a0;
+  else return arg_of<T>(a...);
 }
 
 // Game-history draws (include/gpu_nnue.h at gn_history), shared by the history variants of both
@@ -1166,22 +1183,27 @@ __device__ __forceinline__ uint32_t drawn_by_rule(const Board &X, const uint64_t
 // keys[self].  The draw bit rides below the move with the other two flag bits, the value and the
 // move one bit higher: (value + 32768) << 19 | (0xFFFF - move) << 3 | draw << 2 | no-moves << 1 |
 // in-check.  The variant is chosen at compile time by an optional trailing kernel argument
-// (History: nothing, or one RankHistory), so the plain instantiations keep their arguments.
+// (Extra: nothing, or one RankHistory), so the plain instantiations keep their arguments.
 // Left to itself the history variant takes 181 VGPRs, 2 waves per SIMD where the
 // plain kernel (162) runs 3, and that, not the key arithmetic or the walk's loads, was its cost
 // (DESIGN.md §1.5); asked for 3 waves it fits 168 without scratch.  (The plain variant asks for 1,
 // which is what no request means.)
-template <class Parent, class Off, class... History>
-__global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(sizeof...(History) ? 3 : 1)))
+//
+// Extended variant (EXT; include/gpu_nnue.h at gn_line, "check-extended"): a second optional
+// trailing argument, RankExtension, chosen the same way.  Where the lane picks its child's value, a
+// child that has a legal move, is not drawn by rule and whose ext entry is not GN_NOT_EXTENDED takes
+// that entry instead of its static final_v, and the searched bit rides above the draw bit's place.
+template <class Parent, class Off, class... Extra>
+__global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(has_arg<RankHistory, Extra...> ? 3 : 1)))
     rank_children_kernel(const Parent *__restrict__ parents, size_t n, const Off *__restrict__ offsets,
                          const uint16_t *__restrict__ moves, const gn_eval *__restrict__ rec, gn_eval_params P,
-                         const Tables *__restrict__ tables, int K, gn_line *__restrict__ lines, History... history) {
-  static_assert(sizeof...(History) <= 1, "nothing, or one RankHistory");
-  constexpr bool HIST = sizeof...(History) != 0;
+                         const Tables *__restrict__ tables, int K, gn_line *__restrict__ lines, Extra... extra) {
+  constexpr bool HIST = has_arg<RankHistory, Extra...>, EXT = has_arg<RankExtension, Extra...>;
+  static_assert(sizeof...(Extra) == (HIST ? 1 : 0) + (EXT ? 1 : 0), "nothing, a RankHistory, a RankExtension, or both");
   __shared__ Tables T;
   load_tables(T, tables);
   constexpr int W = GN_RANK_WIDTH;
-  using Key = LineKey<HIST>;
+  using Key = LineKey<HIST, EXT>;
   const int lane = threadIdx.x & (W - 1);
   // a bounded grid striding over the parents (the 4 KiB table load once per workgroup)
   const size_t stride = (size_t)gridDim.x * (RANK_WG / W);
@@ -1194,7 +1216,7 @@ __global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(si
     const bool ok = c1 > c0 && rank_parent(parents[p], B, T);
     HistWindow hw = {0, 0}; // HIST: the parent's game so far (len 0: no history)
     if constexpr (HIST) {
-      if (ok) hw = hist_window((history, ...), p);
+      if (ok) hw = hist_window(arg_of<RankHistory>(extra...), p);
     }
     for (uint64_t c = c0; ok && c < c1; c += W) {
       uint64_t key = 0;
@@ -1206,10 +1228,16 @@ __global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(si
         const uint32_t none = any_legal(C, T) ? 0u : KEY_NO_MOVES;
         uint32_t draw = 0;
         if constexpr (HIST) {
-          if (!none && drawn_by_rule(C, (history.keys, ...) + ((size_t)hw.self + 1), hw.len)) draw = KEY_DRAW;
+          if (!none && drawn_by_rule(C, arg_of<RankHistory>(extra...).keys + ((size_t)hw.self + 1), hw.len)) draw = KEY_DRAW;
         }
-        const int32_t v = negate_ply(none ? (check ? -VALUE_MATE : 0) : draw ? 0 : r.final_v);
-        key = Key::pack(v, 0xFFFFu - mv, draw | none | check);
+        int32_t leaf = r.final_v; // the leaf's value: static, or (EXT) its check extension
+        uint32_t searched = 0;
+        if constexpr (EXT) {
+          const int32_t e = arg_of<RankExtension>(extra...).ext[c + lane];
+          if (!none && !draw && e != GN_NOT_EXTENDED) leaf = e, searched = KEY_SEARCHED;
+        }
+        const int32_t v = negate_ply(none ? (check ? -VALUE_MATE : 0) : draw ? 0 : leaf);
+        key = Key::pack(v, 0xFFFFu - mv, searched | draw | none | check);
       }
       top = top_k_rounds<W>(key, top, lane, K);
     }
@@ -1227,15 +1255,22 @@ __global__ void __launch_bounds__(RANK_WG) __attribute__((amdgpu_waves_per_eu(si
   }
 }
 
-// (history: keys / n_keys / hist of the history variant, or nullptr: the plain kernel)
+// (history: keys / n_keys / hist of the history variant, or nullptr: the plain kernel; ext: the
+// leaves' check extensions, or nullptr: today's instantiations)
 template <class Parent, class Off>
 static hipError_t rank_children_t(const Parent *parents, size_t n, const Off *offsets, const uint16_t *moves,
                                   const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                  gn_line *lines, const RankHistory *history, hipStream_t s) {
+                                  gn_line *lines, const RankHistory *history, const int32_t *ext, hipStream_t s) {
   if (!n) return hipSuccess;
   constexpr size_t per_wg = RANK_WG / GN_RANK_WIDTH, max_blocks = 8192;
   const size_t blocks = std::min<size_t>((n + per_wg - 1) / per_wg, max_blocks);
-  if (history)
+  if (history && ext)
+    hipLaunchKernelGGL((rank_children_kernel<Parent, Off, RankHistory, RankExtension>), dim3(blocks), dim3(RANK_WG), 0, s,
+                       parents, n, offsets, moves, rec, P, tables, K, lines, *history, RankExtension{ext});
+  else if (ext)
+    hipLaunchKernelGGL((rank_children_kernel<Parent, Off, RankExtension>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n,
+                       offsets, moves, rec, P, tables, K, lines, RankExtension{ext});
+  else if (history)
     hipLaunchKernelGGL((rank_children_kernel<Parent, Off, RankHistory>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n,
                        offsets, moves, rec, P, tables, K, lines, *history);
   else
@@ -1245,13 +1280,13 @@ static hipError_t rank_children_t(const Parent *parents, size_t n, const Off *of
 }
 hipError_t launch_rank_children(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
                                 const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                gn_line *lines, const RankHistory *history, hipStream_t s) {
-  return rank_children_t(unpacked, n, offsets, moves, rec, P, tables, K, lines, history, s);
+                                gn_line *lines, const RankHistory *history, const int32_t *ext, hipStream_t s) {
+  return rank_children_t(unpacked, n, offsets, moves, rec, P, tables, K, lines, history, ext, s);
 }
 hipError_t launch_rank_children(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
                                 const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
-                                gn_line *lines, const RankHistory *history, hipStream_t s) {
-  return rank_children_t(parents, n, offsets, moves, rec, P, tables, K, lines, history, s);
+                                gn_line *lines, const RankHistory *history, const int32_t *ext, hipStream_t s) {
+  return rank_children_t(parents, n, offsets, moves, rec, P, tables, K, lines, history, ext, s);
 }
 
 // Position keys (chess.h position_key), a lane per board.  GATE: a caller's boards through the
@@ -1319,17 +1354,24 @@ hipError_t launch_position_keys(const gn_board *boards, size_t n, bool gate, con
 // bits, the other fields one bit higher: (value + 32768) << 35 | (0xFFFF - move) << 19 |
 // reply << 3 | draw << 2 | no-moves << 1 | in-check.  A child without a reply to show (none, or
 // drawn) has reply 0, a legal reply's encoding is never 0: plies is reply ? 2 : 1.
-template <class Parent, class Off, class... History>
+//
+// Extended variant (EXT; include/gpu_nnue.h at gn_line2, "check-extended"): a second optional
+// trailing RankExtension over the grandchildren.  A grandchild that has a legal move, is not drawn by
+// rule and whose ext entry is not GN_NOT_EXTENDED takes that entry as V1; the searched bit rides in
+// the reply key above the draw bit, (V + 32768) << 18 | (0xFFFF - reply) << 2 | searched << 1 | draw,
+// and the chosen reply's bit in the child key above the draw bit's place: (value + 32768) << 36 |
+// (0xFFFF - move) << 20 | reply << 4 | searched << 3 | draw << 2 | no-moves << 1 | in-check.
+template <class Parent, class Off, class... Extra>
 __global__ void __launch_bounds__(RANK_WG)
     rank_lines2_kernel(const Parent *__restrict__ parents, size_t n, const Off *__restrict__ offsets,
                        const gn_board *__restrict__ children, const gn_eval *__restrict__ rec,
                        const uint16_t *__restrict__ moves, const Off *__restrict__ goffsets,
                        const uint16_t *__restrict__ gmoves, const gn_eval *__restrict__ grec, gn_eval_params P,
-                       const Tables *__restrict__ tables, int K, gn_line2 *__restrict__ lines, History... history) {
-  static_assert(sizeof...(History) <= 1, "nothing, or one RankHistory");
-  constexpr bool HIST = sizeof...(History) != 0;
-  using Reply = ReplyKey<HIST>;
-  using Child = ChildKey<HIST>;
+                       const Tables *__restrict__ tables, int K, gn_line2 *__restrict__ lines, Extra... extra) {
+  constexpr bool HIST = has_arg<RankHistory, Extra...>, EXT = has_arg<RankExtension, Extra...>;
+  static_assert(sizeof...(Extra) == (HIST ? 1 : 0) + (EXT ? 1 : 0), "nothing, a RankHistory, a RankExtension, or both");
+  using Reply = ReplyKey<HIST, EXT>;
+  using Child = ChildKey<HIST, EXT>;
   __shared__ Tables T;
   __shared__ uint64_t merge[RANK_WG / 32 * GN_MAX_LINES]; // each group's top 8
   load_tables(T, tables);
@@ -1343,7 +1385,7 @@ __global__ void __launch_bounds__(RANK_WG)
     }
     uint64_t top = 0; // lane k: this group's k-th best child key so far (0: none)
     HistWindow hw = {0, 0}; // HIST: the parent's game so far (len 0: no history)
-    if constexpr (HIST) hw = hist_window((history, ...), p);
+    if constexpr (HIST) hw = hist_window(arg_of<RankHistory>(extra...), p);
     const uint32_t glen = hw.len ? hw.len + 1 : 0u; // the window as a grandchild counts it, a ply further on
     for (uint64_t cb = c0; cb < c1; cb += GROUPS) {
       const uint64_t c = cb + q;
@@ -1369,7 +1411,7 @@ __global__ void __launch_bounds__(RANK_WG)
               seen = 2;
             } else if (lim >= 4) {
               const uint64_t ck = position_key(C);
-              const uint64_t *const at = (history.keys, ...) + ((size_t)hw.self + 1);
+              const uint64_t *const at = arg_of<RankHistory>(extra...).keys + ((size_t)hw.self + 1);
               for (uint32_t d = 4 + 2 * (uint32_t)lane; d <= lim; d += 2 * W) seen += *(at - d) == ck ? 1u : 0u;
             }
           }
@@ -1382,13 +1424,17 @@ __global__ void __launch_bounds__(RANK_WG)
             const gn_eval r = grec[g + lane];
             const Board G = do_move(C, (uint16_t)gm, nullptr);
             int32_t v1 = (r.flags & GN_FLAG_IN_CHECK) ? -VALUE_MATE : 0;
-            uint32_t draw = 0;
+            uint32_t draw = 0, searched = 0;
             if (any_legal(G, T)) {
               if constexpr (HIST)
-                draw = drawn_by_rule(G, (history.keys, ...) + ((size_t)hw.self + 2), glen);
+                draw = drawn_by_rule(G, arg_of<RankHistory>(extra...).keys + ((size_t)hw.self + 2), glen);
               v1 = draw ? 0 : r.final_v;
+              if constexpr (EXT) {
+                const int32_t e = arg_of<RankExtension>(extra...).ext[g + lane];
+                if (!draw && e != GN_NOT_EXTENDED) v1 = e, searched = REPLY_SEARCHED;
+              }
             }
-            const uint64_t k = Reply::pack(negate_ply(v1), 0xFFFFu - gm, draw);
+            const uint64_t k = Reply::pack(negate_ply(v1), 0xFFFFu - gm, searched | draw);
             best = k > best ? k : best;
           }
         }
@@ -1399,8 +1445,9 @@ __global__ void __launch_bounds__(RANK_WG)
         const bool leaf = none || cdraw; // the line ends at the child
         const int32_t R = none ? (check ? -VALUE_MATE : 0) : cdraw ? 0 : Reply::value(best);
         const uint32_t reply = leaf ? 0u : 0xFFFFu - Reply::payload(best);
-        const uint32_t draw = none ? 0u : cdraw ? KEY_DRAW : Reply::flags(best) ? KEY_DRAW : 0u;
-        key = Child::pack(negate_ply(R), (uint64_t)(0xFFFFu - mv) << 16 | reply, draw | none | check);
+        const uint32_t draw = none ? 0u : cdraw ? KEY_DRAW : (Reply::flags(best) & REPLY_DRAW) ? KEY_DRAW : 0u;
+        const uint32_t searched = !leaf && (Reply::flags(best) & REPLY_SEARCHED) ? KEY_SEARCHED : 0u;
+        key = Child::pack(negate_ply(R), (uint64_t)(0xFFFFu - mv) << 16 | reply, searched | draw | none | check);
       }
       // sorted insert: lane k takes the key if it beats top[k] but not top[k - 1], the neighbour's
       // old value if it beats both
@@ -1432,20 +1479,127 @@ __global__ void __launch_bounds__(RANK_WG)
   }
 }
 
-// (history: keys / n_keys / hist of the history variant, or nullptr: the plain kernel)
+// (history: keys / n_keys / hist of the history variant, or nullptr: the plain kernel; gext: the
+// grandchildren's check extensions, or nullptr: today's instantiations)
 hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t *offsets, const gn_board *children,
                               const gn_eval *rec, const uint16_t *moves, const uint32_t *goffsets,
                               const uint16_t *gmoves, const gn_eval *grec, const gn_eval_params &P,
                               const Tables *tables, int K, gn_line2 *lines, const RankHistory *history,
-                              hipStream_t s) {
+                              const int32_t *gext, hipStream_t s) {
   if (!n) return hipSuccess;
   const size_t blocks = std::min<size_t>(n, 8192);
-  if (history)
+  if (history && gext)
+    hipLaunchKernelGGL((rank_lines2_kernel<gn_board, uint32_t, RankHistory, RankExtension>), dim3(blocks), dim3(RANK_WG), 0,
+                       s, parents, n, offsets, children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines, *history,
+                       RankExtension{gext});
+  else if (gext)
+    hipLaunchKernelGGL((rank_lines2_kernel<gn_board, uint32_t, RankExtension>), dim3(blocks), dim3(RANK_WG), 0, s, parents,
+                       n, offsets, children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines, RankExtension{gext});
+  else if (history)
     hipLaunchKernelGGL((rank_lines2_kernel<gn_board, uint32_t, RankHistory>), dim3(blocks), dim3(RANK_WG), 0, s, parents,
                        n, offsets, children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines, *history);
   else
     hipLaunchKernelGGL((rank_lines2_kernel<gn_board, uint32_t>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets,
                        children, rec, moves, goffsets, gmoves, grec, P, tables, K, lines);
+  return hipGetLastError();
+}
+
+// ---- check extension of one expansion level (include/gpu_nnue.h gn_extend_checks_device) ----
+// The leaves in check of an expansion level are valued by the score rule's in-check part instead of
+// their static evaluation (gpu_nnue.hip extend_checks): selected here from their records, their
+// boards made and compacted, evaluated as positions by the path gn_evaluate_device runs, and the
+// values scattered back.
+// sel[j] = 1 for a leaf whose record says in check (a mated one included: the evaluation finds it
+// has no move and leaves it unextended), sel[total] = 0 (the scan's end); ext[j] = GN_NOT_EXTENDED.
+__global__ void extend_select_kernel(const gn_eval *__restrict__ rec, size_t total, uint64_t *__restrict__ sel,
+                                     int32_t *__restrict__ ext) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j > total) return;
+  uint64_t v = 0;
+  if (j < total) {
+    v = (rec[j].flags & GN_FLAG_IN_CHECK) ? 1 : 0;
+    ext[j] = GN_NOT_EXTENDED;
+  }
+  sel[j] = v;
+}
+// The selected leaves' boards, compacted: for k = pos[j], idx[k] = j, sb[k] = the owning parent
+// after moves[j], sv[k] = GN_NOT_EXTENDED (the score rule then writes the extended ones' values).
+// Shaped like rank_children_kernel's outer loop: a 32-lane group per parent, a lane per leaf, a
+// bounded grid, the tables in LDS once per workgroup; the parent is unpacked once (through the gate
+// when it is a caller's board, rank_parent) and only where one of its leaves is selected.
+template <class Parent, class Off>
+__global__ void __launch_bounds__(RANK_WG)
+    extend_boards_kernel(const Parent *__restrict__ parents, size_t n, const Off *__restrict__ offsets,
+                         const uint16_t *__restrict__ moves, const uint64_t *__restrict__ sel,
+                         const uint64_t *__restrict__ pos, size_t total, const Tables *__restrict__ tables,
+                         uint32_t *__restrict__ idx, gn_board *__restrict__ sb, int32_t *__restrict__ sv) {
+  __shared__ Tables T;
+  load_tables(T, tables);
+  constexpr int W = 32;
+  const int lane = threadIdx.x & (W - 1);
+  const size_t stride = (size_t)gridDim.x * (RANK_WG / W);
+  for (size_t p = (size_t)blockIdx.x * (RANK_WG / W) + threadIdx.x / W; p < n; p += stride) {
+    // (clamped to the leaves the selection covers: sel / pos hold total + 1 entries)
+    const uint64_t c1 = std::min<uint64_t>(offsets[p + 1], total), c0 = std::min<uint64_t>(offsets[p], c1);
+    if (c0 >= c1 || pos[c0] == pos[c1]) continue; // no leaf, or none selected (uniform in the group)
+    Board B;
+    if (!rank_parent(parents[p], B, T)) continue;
+    for (uint64_t c = c0 + lane; c < c1; c += W) {
+      if (!sel[c]) continue;
+      const uint64_t k = pos[c];
+      const Board C = do_move(B, moves[c], nullptr);
+      gn_board pb;
+      pack(C, pb);
+      sb[k] = pb;
+      idx[k] = (uint32_t)c;
+      sv[k] = GN_NOT_EXTENDED;
+    }
+  }
+}
+// ext[idx[k]] = sv[k]; *extended += the values that are not GN_NOT_EXTENDED (m is small: one
+// atomic per wave)
+__global__ void extend_scatter_kernel(const uint32_t *__restrict__ idx, const int32_t *__restrict__ sv, size_t m,
+                                      int32_t *__restrict__ ext, unsigned long long *__restrict__ extended) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool is = false;
+  if (k < m) {
+    const int32_t v = sv[k];
+    ext[idx[k]] = v;
+    is = v != GN_NOT_EXTENDED;
+  }
+  const unsigned long long b = __ballot(is);
+  if (b && (threadIdx.x & 63) == 0) atomicAdd(extended, (unsigned long long)__popcll(b));
+}
+
+hipError_t launch_extend_select(const gn_eval *rec, size_t total, uint64_t *sel, int32_t *ext, hipStream_t s) {
+  hipLaunchKernelGGL(extend_select_kernel, dim3(blocks_for(total + 1, 256)), dim3(256), 0, s, rec, total, sel, ext);
+  return hipGetLastError();
+}
+template <class Parent, class Off>
+static hipError_t extend_boards_t(const Parent *parents, size_t n, const Off *offsets, const uint16_t *moves,
+                                  const uint64_t *sel, const uint64_t *pos, size_t total, const Tables *tables,
+                                  uint32_t *idx, gn_board *sb, int32_t *sv, hipStream_t s) {
+  if (!n) return hipSuccess;
+  constexpr size_t per_wg = RANK_WG / 32, max_blocks = 8192;
+  const size_t blocks = std::min<size_t>((n + per_wg - 1) / per_wg, max_blocks);
+  hipLaunchKernelGGL((extend_boards_kernel<Parent, Off>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets, moves,
+                     sel, pos, total, tables, idx, sb, sv);
+  return hipGetLastError();
+}
+hipError_t launch_extend_boards(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
+                                const uint64_t *sel, const uint64_t *pos, size_t total, const Tables *tables,
+                                uint32_t *idx, gn_board *sb, int32_t *sv, hipStream_t s) {
+  return extend_boards_t(unpacked, n, offsets, moves, sel, pos, total, tables, idx, sb, sv, s);
+}
+hipError_t launch_extend_boards(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
+                                const uint64_t *sel, const uint64_t *pos, size_t total, const Tables *tables,
+                                uint32_t *idx, gn_board *sb, int32_t *sv, hipStream_t s) {
+  return extend_boards_t(parents, n, offsets, moves, sel, pos, total, tables, idx, sb, sv, s);
+}
+hipError_t launch_extend_scatter(const uint32_t *idx, const int32_t *sv, size_t m, int32_t *ext,
+                                 unsigned long long *extended, hipStream_t s) {
+  if (!m) return hipSuccess;
+  hipLaunchKernelGGL(extend_scatter_kernel, dim3(blocks_for(m, 256)), dim3(256), 0, s, idx, sv, m, ext, extended);
   return hipGetLastError();
 }
 

@@ -61,13 +61,17 @@ EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_
            "gn_random_games_uci", "gn_rank_children_device", "gn_evaluate_games_lines",
            "gn_rank_lines2_device", "gn_evaluate_lines2", "gn_position_keys", "gn_position_keys_device",
            "gn_rank_children_history_device", "gn_evaluate_games_lines_history",
-           "gn_rank_lines2_history_device", "gn_evaluate_games_lines2", "gn_evaluate_games_lines2_history"]
+           "gn_rank_lines2_history_device", "gn_evaluate_games_lines2", "gn_evaluate_games_lines2_history",
+           "gn_extend_checks_device", "gn_rank_children_extended_device", "gn_rank_lines2_extended_device",
+           "gn_evaluate_lines2_extended", "gn_evaluate_games_lines2_extended", "gn_evaluate_games_lines_extended"]
 OPT_INCREMENTAL_CHILDREN, OPT_XCD_SWIZZLE, OPT_KING_SORT, OPT_CHAIN, OPT_KING_CACHE = 1, 2, 3, 4, 5
 OPT_CHUNK_PARENTS, OPT_COALESCE, OPT_STREAM_SLICES, OPT_FAST_BATCH, OPT_EXPAND_PIPELINE = 6, 7, 8, 9, 10
 STAT_PLAN_NS, STAT_STREAM_NS, STAT_SCRATCH_PADS, STAT_FINISH_NS = 101, 102, 103, 104
 STAT_ZERO_ROW_ENTRIES = 105
 STAT_BATCH_LAUNCHES, STAT_BATCH_CALLS, STAT_FAST_BATCHES, STAT_FAST_FALLBACKS = 117, 118, 119, 120
 STAT_RANK_NS, STAT_RANK2_NS, STAT_KEYS_NS = 121, 122, 123
+STAT_EXTEND_NS, STAT_EXTENDED_LEAVES = 124, 125
+NOT_EXTENDED = -(2 ** 31)  # GN_NOT_EXTENDED: a d_ext entry of a leaf the check extension does not value
 HOST_STAGES = {"parse": 110, "upload": 111, "replay": 112, "compute": 113, "download": 114, "tail": 115, "total": 116}
 EXPAND_STAGES = ["count_scan", "total_readback", "write_children", "classify", "small_net", "big_net", "finalize",
                  "score"]
@@ -193,6 +197,12 @@ def lib():
         "gn_rank_lines2_history_device": [vp, i32, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, i32, vp, vp],
         "gn_evaluate_games_lines2": [vp, vp, sz, i32, i32, vp, vp, vp, sz, vp],
         "gn_evaluate_games_lines2_history": [vp, vp, sz, i32, i32, vp, vp, vp, sz, vp],
+        "gn_extend_checks_device": [vp, i32, vp, sz, vp, vp, vp, sz, i32, vp, C.POINTER(sz), vp],
+        "gn_rank_children_extended_device": [vp, i32, vp, sz, vp, vp, vp, vp, sz, vp, vp, i32, vp, vp],
+        "gn_rank_lines2_extended_device": [vp, i32, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, i32, vp, vp],
+        "gn_evaluate_lines2_extended": [vp, vp, sz, i32, i32, vp, vp],
+        "gn_evaluate_games_lines2_extended": [vp, vp, sz, i32, i32, i32, vp, vp, vp, sz, vp],
+        "gn_evaluate_games_lines_extended": [vp, vp, sz, i32, i32, i32, vp, vp, vp, sz, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -537,18 +547,36 @@ class GpuNnue:
             return offs, status, pos[:p], lines[:p]
         raise GnError(E_CAPACITY, "capacity retry failed")
 
+    def evaluate_games_lines_extended(self, games, n_lines, mode=MODE_FULL, cap=None, history=False):
+        """gn_evaluate_games_lines_extended: evaluate_games_lines whose leaves in check take their check
+        extension (FLAG_SEARCHED); history: with the game-history draws as well."""
+        f = lib().gn_evaluate_games_lines_extended
+        call = lambda h, arr, ng, mode, K, *rest: f(h, arr, ng, mode, K, int(bool(history)), *rest)
+        return self._games_lines(call, LINE_DTYPE, games, n_lines, mode, cap)
+
+    def evaluate_games_lines2_extended(self, games, n_lines, mode=MODE_FULL, cap=None, history=False):
+        """gn_evaluate_games_lines2_extended: evaluate_games_lines2 whose grandchildren in check take
+        their check extension (FLAG_SEARCHED when the chosen reply's was); history: with the draws."""
+        f = lib().gn_evaluate_games_lines2_extended
+        call = lambda h, arr, ng, mode, K, *rest: f(h, arr, ng, mode, K, int(bool(history)), *rest)
+        return self._games_lines(call, LINE2_DTYPE, games, n_lines, mode, cap)
+
+    def evaluate_lines2_extended(self, fens, n_lines, mode=MODE_FULL):
+        """gn_evaluate_lines2_extended: evaluate_lines2 with check-extended grandchildren."""
+        return self.evaluate_lines2(fens, n_lines, mode, call=lib().gn_evaluate_lines2_extended)
+
     def evaluate_games_lines_history(self, games, n_lines, mode=MODE_FULL, cap=None):
         """gn_evaluate_games_lines_history: evaluate_games_lines with each game's history."""
         return self.evaluate_games_lines(games, n_lines, mode, cap, history=True)
 
-    def evaluate_lines2(self, fens, n_lines, mode=MODE_FULL):
+    def evaluate_lines2(self, fens, n_lines, mode=MODE_FULL, call=None):
         """gn_evaluate_lines2: (positions[EVAL_DTYPE], lines[positions, n_lines] as LINE2_DTYPE): the
         best n_lines two-ply lines (move, best reply, minimax value) of every FEN."""
         n = len(fens)
         arr, _keep = _fen_array(fens)
         out = np.zeros(n, dtype=EVAL_DTYPE)
         lines = np.zeros((n, max(n_lines, 1)), dtype=LINE2_DTYPE)
-        _check(lib().gn_evaluate_lines2(self.h, arr, n, mode, n_lines, out.ctypes.data, lines.ctypes.data))
+        _check((call or lib().gn_evaluate_lines2)(self.h, arr, n, mode, n_lines, out.ctypes.data, lines.ctypes.data))
         return out, lines
 
     def host_stages(self):
@@ -655,6 +683,37 @@ class GpuNnue:
         _check(lib().gn_rank_lines2_history_device(self.h, slot, d_parents.ptr, n, p("off"), p("ch"), p("co"), p("mv"),
                                                    p("goff"), p("gmv"), p("gco"), d_keys.ptr if d_keys else None,
                                                    n_keys, d_hist.ptr, n_lines, d_lines.ptr, stream))
+
+    def extend_checks_device(self, d_parents, n, d_offsets, d_moves, d_rec, total, mode, d_ext, stream=None, slot=0):
+        """gn_extend_checks_device: d_ext[total] (int32) = the check extension of each leaf of a preceding
+        expansion level (NOT_EXTENDED where it keeps its static value).  Returns the number of extended
+        leaves.  Blocking.  The buffers may be None when total is 0."""
+        ne = C.c_size_t()
+        p = lambda b: b.ptr if b is not None else None
+        _check(lib().gn_extend_checks_device(self.h, slot, p(d_parents), n, p(d_offsets), p(d_moves), p(d_rec), total,
+                                             mode, p(d_ext), C.byref(ne), stream))
+        return ne.value
+
+    def rank_children_extended_device(self, d_parents, n, d_offsets, d_moves, d_child_out, d_ext, n_lines, d_lines,
+                                      d_keys=None, n_keys=0, d_hist=None, stream=None, slot=0):
+        """gn_rank_children_extended_device: rank_children_device with check-extended leaves (d_ext from
+        extend_checks_device); d_hist (with d_keys / n_keys): the game-history draws as well, None: no
+        history at all.  Asynchronous."""
+        p = lambda b: b.ptr if b is not None else None
+        _check(lib().gn_rank_children_extended_device(self.h, slot, d_parents.ptr, n, d_offsets.ptr, p(d_moves),
+                                                      p(d_child_out), p(d_keys), n_keys, p(d_hist), p(d_ext), n_lines,
+                                                      d_lines.ptr, stream))
+
+    def rank_lines2_extended_device(self, d_parents, n, out, d_gext, n_lines, d_lines, d_keys=None, n_keys=0,
+                                    d_hist=None, stream=None, slot=0):
+        """gn_rank_lines2_extended_device: rank_lines2_device with check-extended grandchildren (d_gext
+        from extend_checks_device over the children as parents); d_hist: the draws as well, None: no
+        history at all.  Asynchronous."""
+        p = lambda k: out[k].ptr if out.get(k) is not None else None
+        q = lambda b: b.ptr if b is not None else None
+        _check(lib().gn_rank_lines2_extended_device(self.h, slot, d_parents.ptr, n, p("off"), p("ch"), p("co"), p("mv"),
+                                                    p("goff"), p("gmv"), p("gco"), q(d_keys), n_keys, q(d_hist),
+                                                    q(d_gext), n_lines, d_lines.ptr, stream))
 
     def expand2_device(self, d_parents, n, mode, out, stream=None, slot=0):
         """Depth 2 (gn_expand2_device).  out: DeviceBuffers po, off, ch (child boards), mv, co,

@@ -193,6 +193,13 @@ extern "C" {
                                          the last gn_evaluate_games_lines2_history, summed
                                          over its chunks (the slowest device; 0 after any
                                          other host-buffer call)                           */
+#define GN_STAT_EXTEND_NS 124         /* the check extension (gn_line "check-extended") in the
+                                         last gn_evaluate_lines2_extended or
+                                         gn_evaluate_games_lines[2]_extended, summed over its
+                                         chunks (the slowest device; 0 after any other
+                                         host-buffer call) ...                             */
+#define GN_STAT_EXTENDED_LEAVES 125   /* ... and the leaves it extended, summed over the
+                                         devices (0 after any other host-buffer call)      */
 #define GN_STAT_BATCH_LAUNCHES 117    /* merged gn_evaluate_batch launches since load ...   */
 #define GN_STAT_BATCH_CALLS 118       /* ... and the calls they served (GN_OPT_COALESCE)    */
 #define GN_STAT_FAST_BATCHES 119      /* evaluations run by the captured small-batch graphs
@@ -211,7 +218,9 @@ extern "C" {
 #define GN_FLAG_MATE 32u    /* score is a mate distance (UCI `score mate <score>`)  */
 #define GN_FLAG_NO_SCORE 64u /* no score: skipped / bad position, or a child record */
 #define GN_FLAG_SEARCHED 128u /* score from the in-check rule over the legal replies
-                                 (best_move set), not from the static evaluation   */
+                                 (best_move set), not from the static evaluation; on
+                                 gn_line.flags / gn_line2.flags of the check-extended
+                                 calls only: the line's leaf is valued by that rule  */
 #define GN_FLAG_NO_MOVES 256u /* no legal move: checkmate (with IN_CHECK) or stalemate */
 #define GN_FLAG_DRAW 512u /* gn_line.flags and gn_line2.flags of the history calls only: the
                              line ends in a position drawn by rule (threefold repetition or
@@ -286,7 +295,34 @@ typedef struct gn_child {
  * Line 1 and gn_eval.score: for a position in check, line 1's score / move / GN_FLAG_MATE equal
  * that position's gn_eval.score / best_move / GN_FLAG_MATE whenever none of its replies is
  * itself in check with a legal move; otherwise they may differ, the score rule going one level
- * deeper at such a reply. */
+ * deeper at such a reply.
+ *
+ * Check-extended lines (gn_extend_checks_device, gn_rank_children_extended_device,
+ * gn_rank_lines2_extended_device, gn_evaluate_lines2_extended, gn_evaluate_games_lines_extended,
+ * gn_evaluate_games_lines2_extended).  The calls above value a leaf in check by a static number
+ * Stockfish never computes.  The extended calls value every leaf exactly as the library would
+ * score that position if it were handed to gn_evaluate_batch_mode: leaf value E(x), in this order
+ * of precedence:
+ *   1. x has no legal move: -VALUE_MATE when in check, else 0, GN_FLAG_NO_MOVES (unchanged);
+ *   2. the history forms only: x is drawn by rule (gn_history below): 0 with GN_FLAG_DRAW; the
+ *      extension is not consulted (Stockfish tests the draw at node entry);
+ *   3. x is in check with a legal move: E(x) = value(x, 2) of the gn_eval.score rule in the call's
+ *      mode -- the maximum over the legal replies of negate_ply, a reply in check with a legal move
+ *      going one level down, any reply at depth 0 taking its static final_v, ties to the smaller
+ *      move -- and the line carries GN_FLAG_SEARCHED.  The extension knows no history, as
+ *      gn_eval.score knows none;
+ *   4. otherwise x's static final_v.
+ * A gn_line uses V(c) := E(c).  A gn_line2 uses V1(g) := E(g); the child c stays an interior node,
+ * searched through all its replies, its own value never used, and GN_FLAG_SEARCHED is set exactly
+ * when the chosen reply's grandchild was extended (as GN_FLAG_DRAW is).  move, reply, plies (1 or 2:
+ * the extension's own replies are not reported), negate_ply, rule_score, the order, the ties and
+ * the empty lines are unchanged.  Consequences: for an extended leaf x, rule_score(E(x), x's
+ * material) and the mate flag are what gn_evaluate_batch_mode returns for x in the same mode; a
+ * position none of whose leaves is in check with a legal move has byte-equal lines from the plain
+ * and the extended call; for a child with a reply, (R(c), reply) is line 1 of the extended one-ply
+ * ranking over the children as parents; and mate values can appear on lines through a check
+ * (`mate -1` for a check that allows a mating reply, `mate 2`, ...). */
+#define GN_NOT_EXTENDED INT32_MIN /* a d_ext entry of a leaf the extension does not value */
 #define GN_MAX_LINES 8 /* lichess sends multipv <= 5 */
 typedef struct gn_line {
   int32_t value;  /* the rule value, p's side-to-move POV, Stockfish units              */
@@ -296,7 +332,8 @@ typedef struct gn_line {
   uint16_t flags; /* GN_FLAG_MATE; GN_FLAG_IN_CHECK: the move gives check;
                      GN_FLAG_NO_MOVES: the move ends the game (mate or stalemate);
                      GN_FLAG_NO_SCORE: an empty line; GN_FLAG_DRAW: the history calls
-                     only (gn_history below)                                             */
+                     only (gn_history below); GN_FLAG_SEARCHED: the check-extended
+                     calls only (above)                                                  */
 } gn_line;
 
 /* Game-history draws in ranked lines (gn_rank_children_history_device,
@@ -398,7 +435,8 @@ typedef struct gn_line2 { /* 16 bytes */
   uint16_t reply; /* the opponent's best reply to it; 0 when the move ends the game        */
   uint16_t flags; /* GN_FLAG_MATE; GN_FLAG_IN_CHECK: the move gives check; GN_FLAG_NO_MOVES:
                      the move ends the game; GN_FLAG_NO_SCORE: an empty line; GN_FLAG_DRAW:
-                     the history calls only                                                */
+                     the history calls only; GN_FLAG_SEARCHED: the check-extended calls only
+                     (at gn_line): the chosen reply's grandchild was extended              */
   uint16_t plies; /* moves in the PV: 2, or 1 when the move ends the game (or, in the history
                      calls, reaches a position drawn by rule), 0 for an empty line         */
 } gn_line2;
@@ -645,6 +683,30 @@ GN_API int gn_evaluate_games_lines2_history(gn_ctx *ctx, const gn_game *games, s
 GN_API int gn_evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines,
                               gn_eval *out, gn_line2 *lines); /* lines[n * n_lines] */
 
+/* gn_evaluate_lines2 with check-extended leaves (the rule at gn_line, "check-extended"): after each
+ * chunk's depth-2 expansion the grandchildren in check are extended on the device, then ranked.
+ * out is byte-equal to gn_evaluate_lines2's, and so are the lines of every position none of whose
+ * grandchildren is in check with a legal move.  Results are identical for every chunk size and
+ * device count.  GN_STAT_EXTEND_NS / GN_STAT_EXTENDED_LEAVES: the extension's time and count. */
+GN_API int gn_evaluate_lines2_extended(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines,
+                                       gn_eval *out, gn_line2 *lines); /* lines[n * n_lines] */
+/* gn_evaluate_games_lines2 (history == 0) or gn_evaluate_games_lines2_history (history != 0) with
+ * check-extended leaves.  position_offsets, game_status, position_out and the GN_E_CAPACITY
+ * behaviour are byte-equal to those calls'. */
+GN_API int gn_evaluate_games_lines2_extended(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                             int history, uint32_t *position_offsets, int32_t *game_status,
+                                             gn_eval *position_out, size_t position_cap, gn_line2 *lines);
+/* gn_evaluate_games_lines (history == 0) or gn_evaluate_games_lines_history (history != 0) with
+ * check-extended leaves: each chunk's children in check are extended before the ranking.  This
+ * call runs its chunks one after another, as GN_OPT_EXPAND_PIPELINE 0 does (the extension is a
+ * blocking multi-launch stage on per-device buffers); the drain thread, the slots and the chunking
+ * are gn_evaluate_games_lines'.  position_offsets, game_status, position_out and the
+ * GN_E_CAPACITY behaviour are byte-equal to those calls'; results are identical for every
+ * GN_OPT_CHUNK_PARENTS, GN_OPT_EXPAND_PIPELINE and device count. */
+GN_API int gn_evaluate_games_lines_extended(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                            int history, uint32_t *position_offsets, int32_t *game_status,
+                                            gn_eval *position_out, size_t position_cap, gn_line *lines);
+
 /* The partitioner the library uses to shard work over the devices of a context and
  * that multi-process callers use to shard over ranks: contiguous ranges of n_items
  * items, bounds[k] = first item of shard k, bounds[n_shards] = n_items; shard k
@@ -746,6 +808,38 @@ GN_API int gn_rank_lines2_history_device(gn_ctx *ctx, int device_slot, const gn_
                                          const uint32_t *d_goffsets, const uint16_t *d_gmoves,
                                          const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
                                          const gn_history *d_hist, int n_lines, gn_line2 *d_lines, void *stream);
+/* The check extension of one expansion level (the rule at gn_line, "check-extended"): the leaves
+ * are those a preceding gn_expand_device left on the device (d_parents, n, d_offsets, d_moves,
+ * d_rec = d_child_out, total), or level 2 of gn_expand2_device with the children as parents
+ * (d_children, total, d_goffsets, d_gmoves, d_grand_out, gtotal).  d_ext[j] (total entries) = E of
+ * leaf j where it is in check with a legal move, GN_NOT_EXTENDED everywhere else (a mated leaf
+ * included: the ranking values it); *extended = the number of extended leaves.  The leaves'
+ * boards are made on the device and evaluated as positions by the path gn_evaluate_device runs, in
+ * records the library owns: d_rec is only read.  Blocking, like gn_evaluate_device (its counts size
+ * the next launches).  total == 0: GN_OK, nothing is read and the buffers may be NULL.
+ * GN_E_NONET as elsewhere. */
+GN_API int gn_extend_checks_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                   const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_rec,
+                                   size_t total, int mode, int32_t *d_ext, size_t *extended, void *stream);
+/* gn_rank_children_history_device with check-extended leaves: d_ext as gn_extend_checks_device
+ * wrote it for the same expansion (NULL: nothing is extended).  d_hist == NULL selects no history
+ * at all (not even the fifty-move part; d_keys / n_keys are then ignored): the plain rule plus the
+ * extension.  Asynchronous, no read-back. */
+GN_API int gn_rank_children_extended_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                            const uint32_t *d_offsets, const uint16_t *d_moves,
+                                            const gn_eval *d_child_out, const uint64_t *d_keys, size_t n_keys,
+                                            const gn_history *d_hist, const int32_t *d_ext, int n_lines,
+                                            gn_line *d_lines, void *stream);
+/* gn_rank_lines2_history_device with check-extended leaves: d_gext as gn_extend_checks_device wrote
+ * it for the grandchild level (NULL: nothing is extended); d_hist == NULL: no history at all.
+ * Asynchronous, no read-back. */
+GN_API int gn_rank_lines2_extended_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                          const uint32_t *d_offsets, const gn_board *d_children,
+                                          const gn_eval *d_child_out, const uint16_t *d_moves,
+                                          const uint32_t *d_goffsets, const uint16_t *d_gmoves,
+                                          const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
+                                          const gn_history *d_hist, const int32_t *d_gext, int n_lines,
+                                          gn_line2 *d_lines, void *stream);
 /* Time `iters` complete expansions of device-resident parents (child count +
  * scan + child generation with deltas + evaluation of parents and children in
  * `mode` + the parents' score rule).  Outputs go to the caller's device buffers when given (d_parent_out[n],

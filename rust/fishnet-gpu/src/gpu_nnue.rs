@@ -237,6 +237,72 @@ impl GpuNnue {
         Ok((evals, lines))
     }
 
+    /// evaluate_lines2 with check-extended leaves (gn_evaluate_lines2_extended; include/gpu_nnue.h at
+    /// gn_line, "check-extended"): a grandchild in check with a legal move is valued as
+    /// evaluate_batch would score it, by the in-check rule over its replies, instead of by a static
+    /// number Stockfish never computes.  A line whose chosen reply reaches such a grandchild carries
+    /// GN_FLAG_SEARCHED and may be a mate score.  The records equal evaluate_lines2's.
+    pub fn evaluate_lines2_extended(&self, fens: &[Fen], n_lines: usize)
+                                    -> Result<(Vec<GpuEval>, Vec<GpuLine2>), GpuError> {
+        let owned: Vec<CString> = fens.iter().map(|f| CString::new(f.to_string()).unwrap()).collect();
+        let ptrs: Vec<*const std::os::raw::c_char> = owned.iter().map(|c| c.as_ptr()).collect();
+        let mut evals = vec![GpuEval::default(); fens.len()];
+        let mut lines = vec![GpuLine2::default(); fens.len() * n_lines];
+        // SAFETY: ptrs / evals have fens.len() elements, lines fens.len() * n_lines; the call
+        // checks n_lines before it writes.
+        check(unsafe {
+            sys::gn_evaluate_lines2_extended(self.0, ptrs.as_ptr(), ptrs.len(), sys::GN_MODE_FULL, n_lines as i32,
+                                             evals.as_mut_ptr(), lines.as_mut_ptr())
+        })?;
+        Ok((evals, lines))
+    }
+
+    /// evaluate_games_lines with check-extended leaves (gn_evaluate_games_lines_extended with the
+    /// game's history): a move that gives check is valued by the in-check rule over the replies
+    /// (GN_FLAG_SEARCHED), unless its child is drawn by rule (GN_FLAG_DRAW comes first).
+    #[allow(clippy::type_complexity)]
+    pub fn evaluate_games_lines_extended(&self, games: &[(CString, CString, Vec<u32>)], n_lines: usize)
+                                         -> Result<(Vec<u32>, Vec<i32>, Vec<GpuEval>, Vec<GpuLine>), GpuError> {
+        let (gs, cap) = games_and_capacity(games);
+        let mut offsets = vec![0u32; games.len() + 1];
+        let mut status = vec![0i32; games.len()];
+        let mut evals = vec![GpuEval::default(); cap];
+        let mut lines = vec![GpuLine::default(); cap * n_lines];
+        // SAFETY: offsets / status have games.len() (+ 1) elements, evals `cap` and lines
+        // cap * n_lines; the call checks n_lines and the capacity before it writes.
+        check(unsafe {
+            sys::gn_evaluate_games_lines_extended(self.0, gs.as_ptr(), gs.len(), sys::GN_MODE_FULL, n_lines as i32, 1,
+                                                  offsets.as_mut_ptr(), status.as_mut_ptr(), evals.as_mut_ptr(), cap,
+                                                  lines.as_mut_ptr())
+        })?;
+        let total = offsets[games.len()] as usize;
+        evals.truncate(total);
+        lines.truncate(total * n_lines);
+        Ok((offsets, status, evals, lines))
+    }
+
+    /// evaluate_games_lines2 with check-extended leaves (gn_evaluate_games_lines2_extended with the
+    /// game's history): the grandchildren in check are valued by the in-check rule.
+    #[allow(clippy::type_complexity)]
+    pub fn evaluate_games_lines2_extended(&self, games: &[(CString, CString, Vec<u32>)], n_lines: usize)
+                                          -> Result<(Vec<u32>, Vec<i32>, Vec<GpuEval>, Vec<GpuLine2>), GpuError> {
+        let (gs, cap) = games_and_capacity(games);
+        let mut offsets = vec![0u32; games.len() + 1];
+        let mut status = vec![0i32; games.len()];
+        let mut evals = vec![GpuEval::default(); cap];
+        let mut lines = vec![GpuLine2::default(); cap * n_lines];
+        // SAFETY: as evaluate_games_lines_extended.
+        check(unsafe {
+            sys::gn_evaluate_games_lines2_extended(self.0, gs.as_ptr(), gs.len(), sys::GN_MODE_FULL, n_lines as i32, 1,
+                                                   offsets.as_mut_ptr(), status.as_mut_ptr(), evals.as_mut_ptr(), cap,
+                                                   lines.as_mut_ptr())
+        })?;
+        let total = offsets[games.len()] as usize;
+        evals.truncate(total);
+        lines.truncate(total * n_lines);
+        Ok((offsets, status, evals, lines))
+    }
+
     /// Whole acquired batches: replay root FEN + UCI moves (skipPositions honoured) and
     /// evaluate every position and every legal child; buffers grow on GN_E_CAPACITY.
     pub fn evaluate_games(&self, games: &[(CString, CString, Vec<u32>)], mode: i32) -> Result<GamesResult, GpuError> {
@@ -283,6 +349,22 @@ impl GpuNnue {
             return Ok(r);
         }
     }
+}
+
+/// The games as the C-ABI takes them (borrowing the strings and skip lists) and the position
+/// capacity they need: a game has at most one position per move token and one for the root.
+fn games_and_capacity(games: &[(CString, CString, Vec<u32>)]) -> (Vec<sys::gn_game>, usize) {
+    let gs = games
+        .iter()
+        .map(|(root, moves, skip)| sys::gn_game {
+            root_fen: root.as_ptr(),
+            uci_moves: moves.as_ptr(),
+            skip_positions: if skip.is_empty() { ptr::null() } else { skip.as_ptr() },
+            n_skip: skip.len(),
+        })
+        .collect();
+    let cap = games.iter().map(|(_, m, _)| m.as_bytes().split(|&b| b == b' ').filter(|t| !t.is_empty()).count() + 1).sum();
+    (gs, cap)
 }
 
 /// A move in Stockfish's 16-bit encoding (gn_eval.best_move, child_moves) as the Chess960 UCI

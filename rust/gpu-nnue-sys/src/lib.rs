@@ -58,6 +58,10 @@ pub const GN_STAT_FAST_FALLBACKS: c_int = 120;
 pub const GN_STAT_RANK_NS: c_int = 121;
 pub const GN_STAT_RANK2_NS: c_int = 122;
 pub const GN_STAT_KEYS_NS: c_int = 123;
+pub const GN_STAT_EXTEND_NS: c_int = 124;
+pub const GN_STAT_EXTENDED_LEAVES: c_int = 125;
+/// A d_ext entry of a leaf the check extension does not value (gn_extend_checks_device).
+pub const GN_NOT_EXTENDED: i32 = i32::MIN;
 
 // per-position flags
 pub const GN_FLAG_IN_CHECK: u16 = 1;
@@ -248,6 +252,16 @@ extern "C" {
                                             -> c_int;
     pub fn gn_evaluate_lines2(ctx: *mut gn_ctx, fens: *const *const c_char, n: usize, mode: c_int, n_lines: c_int,
                               out: *mut gn_eval, lines: *mut gn_line2) -> c_int;
+    pub fn gn_evaluate_lines2_extended(ctx: *mut gn_ctx, fens: *const *const c_char, n: usize, mode: c_int,
+                                       n_lines: c_int, out: *mut gn_eval, lines: *mut gn_line2) -> c_int;
+    pub fn gn_evaluate_games_lines2_extended(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
+                                             n_lines: c_int, history: c_int, position_offsets: *mut u32,
+                                             game_status: *mut i32, position_out: *mut gn_eval, position_cap: usize,
+                                             lines: *mut gn_line2) -> c_int;
+    pub fn gn_evaluate_games_lines_extended(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
+                                            n_lines: c_int, history: c_int, position_offsets: *mut u32,
+                                            game_status: *mut i32, position_out: *mut gn_eval, position_cap: usize,
+                                            lines: *mut gn_line) -> c_int;
     pub fn gn_partition(weights: *const u32, n_items: usize, n_shards: c_int, bounds: *mut usize) -> c_int;
     pub fn gn_perft(ctx: *mut gn_ctx, fen: *const c_char, depth: c_int, nodes: *mut u64) -> c_int;
     pub fn gn_pack_fens(fens: *const *const c_char, n: usize, out: *mut gn_board, ok: *mut u8) -> c_int;
@@ -286,6 +300,20 @@ extern "C" {
                                          d_gmoves: *const u16, d_grand_out: *const gn_eval, d_keys: *const u64,
                                          n_keys: usize, d_hist: *const gn_history, n_lines: c_int,
                                          d_lines: *mut gn_line2, stream: *mut c_void) -> c_int;
+    pub fn gn_extend_checks_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                                   d_offsets: *const u32, d_moves: *const u16, d_rec: *const gn_eval, total: usize,
+                                   mode: c_int, d_ext: *mut i32, extended: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn gn_rank_children_extended_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                                            d_offsets: *const u32, d_moves: *const u16, d_child_out: *const gn_eval,
+                                            d_keys: *const u64, n_keys: usize, d_hist: *const gn_history,
+                                            d_ext: *const i32, n_lines: c_int, d_lines: *mut gn_line,
+                                            stream: *mut c_void) -> c_int;
+    pub fn gn_rank_lines2_extended_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                                          d_offsets: *const u32, d_children: *const gn_board,
+                                          d_child_out: *const gn_eval, d_moves: *const u16, d_goffsets: *const u32,
+                                          d_gmoves: *const u16, d_grand_out: *const gn_eval, d_keys: *const u64,
+                                          n_keys: usize, d_hist: *const gn_history, d_gext: *const i32, n_lines: c_int,
+                                          d_lines: *mut gn_line2, stream: *mut c_void) -> c_int;
     pub fn gn_expand2_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize, mode: c_int,
                              d_parent_out: *mut gn_eval, d_offsets: *mut u32, d_children: *mut gn_board,
                              d_moves: *mut u16, d_child_out: *mut gn_eval, cap: usize, d_goffsets: *mut u32,
