@@ -3201,6 +3201,7 @@ int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parent
 int gn_checksum_device(gn_ctx *ctx, int device_slot, const void *d_ptr, size_t bytes, uint64_t *sum) {
   Dev *d = slot(ctx, device_slot);
   if (!d || !sum || (bytes && !d_ptr)) return fail(GN_E_INVALID, "bad argument");
+  if ((uintptr_t)d_ptr & 7) return fail(GN_E_INVALID, "d_ptr is not 8-byte aligned"); // the kernel loads 8-byte words
   DevCall call(*d);
   if (call.rc) return call.rc;
   HIP_TRY(d->sum.ensure(2));

@@ -859,7 +859,12 @@ GN_API int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d
                                  gn_eval *d_child_out, size_t cap);
 /* *sum = position-sensitive 64-bit checksum of `bytes` bytes at device pointer d_ptr
  * (sum over 8-byte words w_i of splitmix64(w_i ^ i * 0x9E3779B97F4A7C15), wrapping):
- * compares large device-resident results without a download. */
+ * compares large device-resident results without a download.  The words are
+ * little-endian, word i at byte 8 * i; a tail of bytes % 8 bytes is zero-padded into a
+ * last word; 0 bytes give 0.  splitmix64(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31.  d_ptr must be 8-byte aligned
+ * (the kernel loads whole words): GN_E_INVALID otherwise, checked on the host before
+ * anything is launched. */
 GN_API int gn_checksum_device(gn_ctx *ctx, int device_slot, const void *d_ptr, size_t bytes, uint64_t *sum);
 /* n_games random games of `plies` plies (xoshiro256**, seed + game index) on
  * the GPU: d_out[g * (plies + 1) + k] = position after k plies of game g (a
