@@ -24,7 +24,8 @@ FAULT_DEFINES = ("-DGN_FAULT_PLAN_BLOCK=1",)
 ODD_LIB = os.path.join(LIBDIR, "libgpu_nnue_d5.so")
 ODD_DEFINES = ("-DGN_SMALL_DEPTH=5",)
 SOURCES = ["gpu_nnue.hip", "kernels.hip", "stream.hip"]
-HEADERS = ["chess.h", "host_board.h", "nnue.h", "kernels.h", "sha256.h", "device_util.h", "archive.h"]
+HEADERS = ["chess.h", "host_board.h", "nnue.h", "kernels.h", "sha256.h", "device_util.h", "archive.h",
+           "plan_snapshot.h"]
 ARCH = "gfx950"
 
 

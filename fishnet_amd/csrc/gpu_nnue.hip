@@ -24,6 +24,7 @@
 #include "archive.h"
 #include "host_board.h"
 #include "kernels.h"
+#include "plan_snapshot.h"
 #include "sha256.h"
 
 using namespace gn;
@@ -315,12 +316,19 @@ struct ExpSet {
   // for the row stream (GN_OPT_EXPAND_PIPELINE 2) waits for it before it overwrites the set
   Event scored;
   DevBuf<uint32_t> perr;            // the planned expansion's error word ...
-  DevBuf<unsigned long long> pstat; // ... and its counts: [0] pads, [1] zero-row entries (each expansion of the pipeline its own)
+  // ... and its counts: [0] pads, [1] zero-row entries (each expansion of the pipeline its own), [2] the
+  // plan's FT rows when no caller counts them (expand_level; gn_debug_plan_snapshot reads all three)
+  DevBuf<unsigned long long> pstat;
   // the plan's output the row stream reads (GN_OPT_EXPAND_PIPELINE 2: the next plan runs beside
   // this expansion's row stream)
   DevBuf<uint64_t> ent, eoff;
   DevBuf<TileDesc> tiles;
   DevBuf<uint32_t> btiles, border;
+  // what the last plan in this set was launched with (gn_debug_plan_snapshot, plan_snapshot.h);
+  // plan_geo.nblk == 0: none since the set's last child generation
+  PlanGeometry plan_geo;
+  size_t plan_n = 0, plan_total = 0;
+  bool plan_ordered = false;
 };
 
 struct Dev {
@@ -664,7 +672,7 @@ static int create(const uint8_t *big, size_t big_len, const uint8_t *small, size
     HIP_TRY(d.tables.ensure(1));
     for (ExpSet *x : {&d.cur, &d.alt}) { // the planned expansion's error word and pad count
       HIP_TRY(x->perr.ensure(1));
-      HIP_TRY(x->pstat.ensure(2));
+      HIP_TRY(x->pstat.ensure(3));
     }
     HIP_TRY(hipMemset(d.alt.perr.p, 0, sizeof(uint32_t)));
     HIP_TRY(hipMemcpy(d.tables.p, &host_tables(), sizeof(Tables), hipMemcpyHostToDevice));
@@ -883,9 +891,10 @@ static int generate_children(Dev &d, const gn_board *parents, size_t n, gn_board
   ExpSet &x = d.cur;
   x.chain_k = o.deltas ? o.chain_k : 1;
   x.planned = o.deltas && o.plan;
+  x.plan_geo = PlanGeometry{};
   if (x.planned) { // a stale error bit of an earlier expansion must not fail this one
     HIP_TRY(hipMemsetAsync(x.perr.p, 0, sizeof(uint32_t), s));
-    HIP_TRY(hipMemsetAsync(x.pstat.p, 0, 2 * sizeof(unsigned long long), s));
+    HIP_TRY(hipMemsetAsync(x.pstat.p, 0, 3 * sizeof(unsigned long long), s));
   }
   if (x.chain_k > 1) HIP_TRY(d.nslot.ensure(n));
   HIP_TRY(x.counts.ensure(n + 1));
@@ -1052,6 +1061,8 @@ static int expand_evaluate(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t 
                             x.sort_tmp.p, x.sort_tmp.cap, s));
       }
       HIP_TRY(launch_plan_stream(d.net[BIG], plan_args(), PLAN_PHASE, s));
+      x.plan_geo = plan_geometry(d.net[BIG], plan_args());
+      x.plan_n = n, x.plan_total = total, x.plan_ordered = ordered;
       HIP_TRY(mark(&ExpEvents::plan_done));
     }
   }
@@ -1233,6 +1244,7 @@ static int expand_level(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t n, 
   }
   EvalOpts e;
   e.score_parents = o.score_parents;
+  if (d.cur.planned) e.rows = d.cur.pstat.p + 2; // (zeroed by generate_children)
   rc = expand_evaluate(ctx, d, parents, n, o.children ? o.children : d.cur.children.p, t, mode, parent_out, child_out, s,
                        e);
   const Replies rp{child_out, d_moves}; // the replies this level evaluated
@@ -3542,6 +3554,67 @@ int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {
   }
   HIP_TRY(hipStreamSynchronize(s));
   *nodes = sum;
+  return GN_OK;
+}
+
+// plan_snapshot.h (internal, for the tests): the current set's plan copied to host memory.
+int gn_debug_plan_snapshot(gn_ctx *ctx, int device_slot, gn_plan_snapshot_header *header,
+                           const gn_plan_snapshot_bufs *bufs) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d || !header) return fail(GN_E_INVALID, "bad argument");
+  DevCall call(*d);
+  if (call.rc) return call.rc;
+  HIP_TRY(hipStreamSynchronize(call.s));
+  const ExpSet &x = d->cur;
+  const PlanGeometry &g = x.plan_geo;
+  if (!x.planned || !g.nblk || !x.plan_n)
+    return fail(GN_E_INVALID, "the device slot's last expansion was not planned: no plan to copy");
+  const size_t n = x.plan_n, K = g.K, nblk = g.nblk;
+  std::vector<uint64_t> off(n + 1);
+  std::vector<uint32_t> bt(nblk);
+  HIP_TRY(hipMemcpy(off.data(), x.offsets.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(bt.data(), x.btiles.p, nblk * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  unsigned long long st[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpy(st, x.pstat.p, sizeof(st), hipMemcpyDeviceToHost));
+  const size_t last = (nblk - 1) * K; // the last block's first parent
+  gn_plan_snapshot_header h = {};
+  h.header_bytes = (uint32_t)sizeof(h), h.tile_bytes = (uint32_t)sizeof(TileDesc);
+  h.l1 = (uint32_t)d->net[BIG].L1, h.row_stride = ft_row_stride(h.l1);
+  h.ft_rows = FT_ROWS, h.ft_bias_row = FT_BIAS_ROW, h.zero_row = ZERO_ROW, h.scr_rows = SCR_ROWS;
+  h.ent_spare = ENT_SPARE, h.scr_gap = GN_SCR_GAP, h.ring = GN_RING, h.slice_ring = GN_SLICE_RING;
+  h.np = (uint32_t)n, h.k = g.K, h.nblk = g.nblk, h.slices = g.sliced ? 3 : 1, h.xu = g.xu, h.hu = g.hu;
+  h.kc = (uint32_t)g.kc, h.ordered = x.plan_ordered ? 1 : 0;
+  h.npos = n + x.plan_total;
+  h.n_ent = x.etot + (uint64_t)ENT_SPARE * nblk;
+  // (the descriptors stay inside the allocation even where a broken plan's btiles does not)
+  h.n_tiles = std::min<uint64_t>((last + off[last]) / 16 + (K + 2) * (nblk - 1) + bt[nblk - 1], x.tiles.cap);
+  h.n_pinfo = g.sliced ? h.npos : 0;
+  h.pads = st[0], h.zero_row_entries = st[1], h.rows = st[2];
+  if (off[n] != x.plan_total) return fail(GN_E_INVALID, "the set's offsets are not the planned expansion's");
+  *header = h;
+  if (!bufs) return GN_OK;
+  const struct {
+    const char *name;
+    void *dst;
+    size_t cap, need, size;
+    const void *src;
+  } copies[] = {
+      {"eoff", bufs->eoff, bufs->eoff_cap, n + 1, sizeof(uint64_t), x.eoff.p},
+      {"ent", bufs->ent, bufs->ent_cap, (size_t)h.n_ent, sizeof(uint64_t), x.ent.p},
+      {"tiles", bufs->tiles, bufs->tiles_cap, (size_t)h.n_tiles, sizeof(TileDesc), x.tiles.p},
+      {"btiles", bufs->btiles, bufs->btiles_cap, nblk, sizeof(uint32_t), x.btiles.p},
+      {"order", bufs->order, bufs->order_cap, nblk, sizeof(uint32_t), x.plan_ordered ? x.border.p : nullptr},
+      {"pinfo", bufs->pinfo, bufs->pinfo_cap, (size_t)h.n_pinfo, 2 * sizeof(int32_t), x.pinfo.p},
+      {"offsets", bufs->offsets, bufs->offsets_cap, n + 1, sizeof(uint64_t), x.offsets.p},
+  };
+  for (const auto &c : copies) {
+    if (!c.need) continue;
+    if (!c.dst || c.cap < c.need)
+      return fail(GN_E_INVALID, "plan snapshot: buffer %s holds %zu elements, %zu needed", c.name, c.dst ? c.cap : 0, c.need);
+    if (c.src) HIP_TRY(hipMemcpy(c.dst, c.src, c.need * c.size, hipMemcpyDeviceToHost));
+    else
+      for (size_t i = 0; i < c.need; ++i) static_cast<uint32_t *>(c.dst)[i] = (uint32_t)i; // (order: as they come)
+  }
   return GN_OK;
 }
 

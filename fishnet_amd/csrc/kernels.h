@@ -95,10 +95,13 @@ hipError_t launch_expand_net(const NetDevice &net, const gn_board *parents, size
 // Planned expansion (stream.hip): one descriptor per tile of <= 16 consecutive slots of a
 // block (slots = [parent, its children, next parent, ...] of the block's consecutive
 // parents) with <= 2 buckets among its evaluated slots.  e_end: list 0 / list 1 entries
-// of the block up to the end of this tile (padded to a multiple of 4); p_first: the
+// of the block up to the end of this tile (any length: the lists are not padded at a tile's end
+// since the stream's ring runs across tiles); p_first: the
 // parent owning slot 0; first: the block-relative index of slot 0; meta[t]: bit 0
 // evaluated (clear for a chained parent: it has no entries, its result is that of the child
-// that is its position), bits 1-3 bucket, bit 4 a parent slot, bit 5 the slot's side to move,
+// that is its position; also clear for a parent the big net does not evaluate, which keeps its refresh
+// entries, LAST | PAR_E, whenever one of its children is evaluated: they start from it -- no other
+// unevaluated slot has entries), bits 1-3 bucket, bit 4 a parent slot, bit 5 the slot's side to move,
 // bit 6 (META_NEXT_PARENT) a child that is the next parent's position and whose result is that
 // parent's too (the whole-row streams store it to both; the sliced stream's finish: PINFO_ALIAS);
 // psq[t][side]: the slot's PSQT accumulators at its bucket (side 0: the perspective to move).
@@ -146,7 +149,10 @@ struct PlanStreamArgs {
   // bit 0 entry overflow, bit 1 no scratch slot, bit 2 a king-cache load closer than GN_SCR_GAP
   // entries to its list's last store to scratch
   uint32_t *err = nullptr;
-  unsigned long long *rows_out = nullptr; // += FT rows the stream gathers (bias, carry and king-cache rows included)
+  // += FT rows the stream gathers: every entry with a multiplier (bias and king-cache loads included),
+  // and one more for each parent slot whose refresh is stored to the king cache (a child's store is
+  // not counted; tests/plan_replay.py holds the plan to exactly this)
+  unsigned long long *rows_out = nullptr;
   // (optional, 2 words) [0] += no-op entries the plan inserted to keep GN_SCR_GAP, [1] += entries put on
   // the zero row (they move no row and add nothing)
   unsigned long long *pads_out = nullptr;
@@ -163,6 +169,17 @@ struct PlanStreamArgs {
   int swz = 0;
 };
 hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int phases, hipStream_t s);
+// What launch_plan_stream derives from its arguments and hands to plan_kernel: the block length and
+// count, whether the king cache runs (chained blocks only), whether the stream is column-sliced, and
+// the units of an entry's tile field (stream.hip: hi[31:22] = slot * xu + side * hu).  nblk == 0: the
+// net has no planned kernels (L1 other than 3072 / 1024) or there are no parents.
+struct PlanGeometry {
+  uint32_t K = 1, nblk = 0;
+  int kc = 0;
+  bool sliced = false;
+  uint32_t xu = 0, hu = 0;
+};
+PlanGeometry plan_geometry(const NetDevice &net, const PlanStreamArgs &a);
 // GN_MODE_FULL preparation: need_small = valid && |simple_eval| > threshold,
 // need_big = valid && !need_small.
 hipError_t launch_classify(const gn_board *boards, size_t n, const gn_eval_params &P, uint8_t *need_small,

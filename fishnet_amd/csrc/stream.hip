@@ -1483,19 +1483,33 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
 #endif
 }
 
+PlanGeometry plan_geometry(const NetDevice &net, const PlanStreamArgs &a) {
+  PlanGeometry g;
+  if (!a.n || a.n >= 0x80000000ull || (net.L1 != 3072 && net.L1 != 1024)) return g;
+  g.K = a.chain_k > 1 && a.next_slot ? (uint32_t)a.chain_k : 1u;
+  g.kc = g.K > 1 ? a.kc : 0;
+  g.nblk = (uint32_t)((a.n + g.K - 1) / g.K); // every block of the n parents
+  g.sliced = net.L1 == 3072 && a.slices == 3 && a.part && a.pinfo;
+  const int sl = g.sliced ? 3 : 1;
+  g.xu = net.L1 == 3072 ? ps::field_xu(3072, sl) : ps::field_xu(1024, 1);
+  g.hu = net.L1 == 3072 ? ps::field_hu(3072, sl) : ps::field_hu(1024, 1);
+  return g;
+}
+
 hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int phases, hipStream_t s) {
   const size_t n = a.n;
   if (!n) return hipSuccess;
   const bool do_plan = phases & PLAN_PHASE, do_stream = phases & STREAM_PHASE;
   if (n >= 0x80000000ull) return hipErrorInvalidValue; // 32-bit parent indices in the kernels
-  const uint32_t K = a.chain_k > 1 && a.next_slot ? (uint32_t)a.chain_k : 1u;
+  const PlanGeometry geo = plan_geometry(net, a);
+  const uint32_t K = geo.K;
   const uint8_t *next_slot = K > 1 ? a.next_slot : nullptr;
-  const int kc = K > 1 ? a.kc : 0;
+  const int kc = geo.kc;
   const int scr = K > 1 && a.kc; // the king cache's rows (the chained walk itself needs no scratch)
   const uint32_t nb = (uint32_t)((n + K - 1) / K), B0 = 0, B1 = nb; // every block of the n parents
   const unsigned pg = (nb + PLAN_WAVES - 1) / PLAN_WAVES, g = a.swz == 1 ? 8 * ((nb + 7) / 8) : nb + nb / 16 + 8; // (stream_eval_kernel: claims)
   if (net.L1 == 3072) {
-    const bool sliced = a.slices == 3 && a.part && a.pinfo;
+    const bool sliced = geo.sliced;
     if (do_plan) {
       if (sliced) { // (positions the big net does not evaluate keep pinfo.y < 0; the plan writes the rest)
         hipError_t e = hipMemsetAsync(a.pinfo, 0xFF, a.npos * sizeof(int2), s);
@@ -1503,8 +1517,7 @@ hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int
       }
       hipLaunchKernelGGL((plan_kernel<3072>), dim3(pg), dim3(GN_FRONT_WG), 0, s, net, a.parents, a.offsets, a.deltas,
                          a.need_parent, a.need_child, next_slot, (uint32_t)n, K, B0, B1, kc, a.eoff, a.ent, a.tiles,
-                         a.btiles, a.rows_out, a.pads_out, a.err, sliced ? a.pinfo : nullptr,
-                         sliced ? ps::field_xu(3072, 3) : ps::field_xu(3072, 1), sliced ? ps::field_hu(3072, 3) : ps::field_hu(3072, 1));
+                         a.btiles, a.rows_out, a.pads_out, a.err, sliced ? a.pinfo : nullptr, geo.xu, geo.hu);
     }
     if (!do_stream) {
     } else if (sliced) { // three launches over 1,024 columns each (claim counters pool[64 + 8 slice ..]);
@@ -1522,7 +1535,7 @@ hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int
     if (do_plan) {
       hipLaunchKernelGGL((plan_kernel<1024>), dim3(pg), dim3(GN_FRONT_WG), 0, s, net, a.parents, a.offsets, a.deltas,
                          a.need_parent, a.need_child, next_slot, (uint32_t)n, K, B0, B1, kc, a.eoff, a.ent, a.tiles,
-                         a.btiles, a.rows_out, a.pads_out, a.err, nullptr, ps::field_xu(1024, 1), ps::field_hu(1024, 1));
+                         a.btiles, a.rows_out, a.pads_out, a.err, nullptr, geo.xu, geo.hu);
     }
     if (do_stream) {
       hipLaunchKernelGGL((stream_eval_kernel<1024>), dim3(g), dim3(128), 0, s, net, a.offsets, (uint32_t)n, K, B0, B1,

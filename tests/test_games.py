@@ -306,6 +306,20 @@ def test_king_walk_games_vs_oracle(gpu_ctx, oracle_nets, oracle_lib):
     assert most > 4  # (a parent with more than four king-move jobs)
 
 
+# (root, moves) of test_chained_links_of_special_moves_vs_oracle; the castling games from index
+# CASTLING_GAMES_FROM on (tests/test_gpu_plan_replay.py replays their plans)
+SPECIAL_MOVE_GAMES = [(START, "e2e4 a7a6 e4e5 d7d5 e5d6 c7d6 g2g4 h7h5 g4h5 g7g5 h5g6 a6a5 g6g7 a5a4 g7h8n"),
+                      (START, "b2b4 a7a5 b4a5 b7b5 a5b6 c7c5 b6b7 c5c4 b7a8r c4c3 a8b8 d8a5 b8c8 a5d8"),
+                      ("8/P6k/8/8/8/8/p6K/8 w - - 0 1", "a7a8b a2a1n a8b7 a1b3"),
+                      (C960_CASTLE, "e1g1 e8b8"), (C960_CASTLE, "e1b1 e8g8"),
+                      ("6kr/8/8/8/8/8/8/6KR w Hh - 0 1", "g1h1 g8h8"),       # the king stays
+                      ("k7/8/8/8/8/8/8/4KR2 w F - 0 1", "e1f1 a8b8"),        # the rook stays
+                      ("k7/8/8/8/8/8/8/5KR1 w G - 0 1", "f1g1 a8a7"),        # king and rook swap
+                      ("r3k2r/8/8/8/8/8/8/R3K2R w KQkq - 0 1", "e1c1 e8g8"),
+                      ("r3k2r/8/8/8/8/8/8/R3K2R w KQkq - 0 1", "e1a1 e8h8")]
+CASTLING_GAMES_FROM = 3
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("chain", [-81, -2])
 def test_chained_links_of_special_moves_vs_oracle(gpu_ctx, oracle_nets, oracle_lib, chain):
@@ -318,15 +332,7 @@ def test_chained_links_of_special_moves_vs_oracle(gpu_ctx, oracle_nets, oracle_l
     the oracle (a wrong link starts the next position from the wrong accumulators)."""
     from fishnet_amd import gpu_nnue as G
     big, small = oracle_nets
-    games = [(START, "e2e4 a7a6 e4e5 d7d5 e5d6 c7d6 g2g4 h7h5 g4h5 g7g5 h5g6 a6a5 g6g7 a5a4 g7h8n"),
-             (START, "b2b4 a7a5 b4a5 b7b5 a5b6 c7c5 b6b7 c5c4 b7a8r c4c3 a8b8 d8a5 b8c8 a5d8"),
-             ("8/P6k/8/8/8/8/p6K/8 w - - 0 1", "a7a8b a2a1n a8b7 a1b3"),
-             (C960_CASTLE, "e1g1 e8b8"), (C960_CASTLE, "e1b1 e8g8"),
-             ("6kr/8/8/8/8/8/8/6KR w Hh - 0 1", "g1h1 g8h8"),       # the king stays
-             ("k7/8/8/8/8/8/8/4KR2 w F - 0 1", "e1f1 a8b8"),        # the rook stays
-             ("k7/8/8/8/8/8/8/5KR1 w G - 0 1", "f1g1 a8a7"),        # king and rook swap
-             ("r3k2r/8/8/8/8/8/8/R3K2R w KQkq - 0 1", "e1c1 e8g8"),
-             ("r3k2r/8/8/8/8/8/8/R3K2R w KQkq - 0 1", "e1a1 e8h8")]
+    games = SPECIAL_MOVE_GAMES
     gpu_ctx.set_option(G.OPT_CHAIN, chain)
     try:
         out = gpu_ctx.evaluate_games([(r, m, []) for r, m in games], 0, children=True)
