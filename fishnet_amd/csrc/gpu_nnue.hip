@@ -409,6 +409,27 @@ struct Dev {
     DevBuf<unsigned long long> count;
   } ex;
   DevBuf<int32_t> ext;
+  // the capture quiescence of one expansion level (quiesce): level 0 (the searched leaves) lives in
+  // ex; lv[k] holds level k's searched-move counts and their scan and, for k >= 1, its boards,
+  // position records and values; moves / owner: the level being made
+  struct Quiesce {
+    struct Level {
+      DevBuf<gn_board> boards;
+      DevBuf<gn_eval> rec;
+      DevBuf<int32_t> val;
+      DevBuf<uint64_t> counts, offsets;
+    } lv[GN_MAX_QUIESCE_DEPTH + 1];
+    DevBuf<uint16_t> moves;
+    DevBuf<uint32_t> owner;
+    DevBuf<uint32_t> lcnt; // every leaf's searched moves, from the selection pass
+    void release() {
+      for (Level &l : lv) l.boards.release(), l.rec.release(), l.val.release(), l.counts.release(), l.offsets.release();
+      moves.release(), owner.release(), lcnt.release();
+    }
+  } q;
+  double t_quiesce = 0;     // the quiescence stage of the last host-buffer call (GN_STAT_QUIESCE_NS), ms
+  uint64_t n_qleaves = 0;   // ... the leaves it searched (GN_STAT_QUIESCE_LEAVES)
+  uint64_t n_qnodes = 0;    // ... and the nodes it evaluated below them (GN_STAT_QUIESCE_NODES)
   double t_extend = 0;     // the extension stage of the last host-buffer call (GN_STAT_EXTEND_NS), ms
   uint64_t n_extended = 0; // ... and the leaves it extended (GN_STAT_EXTENDED_LEAVES)
   DevBuf<gn_board> roots, rboards, par;
@@ -706,6 +727,34 @@ struct EvalEvents {
   hipEvent_t begun, sorted, small_done, big_done, finalized;
   hipError_t create(Events &from) { return from.make({&begun, &sorted, &small_done, &big_done, &finalized}); }
 };
+// Every device allocation of one evaluate_on over n positions, in two parts: the net outputs and
+// selections of the mode (in B), and the king sort's keys, permutation and temporary storage.
+// evaluate_on calls both itself; a caller that has to report a failed allocation as its own (quiesce)
+// calls them first, after which evaluate_on allocates nothing.
+static hipError_t reserve_eval_outputs(EvalBufs &B, size_t n, int mode) {
+  hipError_t e = hipSuccess;
+  if (mode != GN_MODE_BIG && (e = B.osm.ensure(n)) != hipSuccess) return e;
+  if (mode != GN_MODE_SMALL && (e = B.obg.ensure(n)) != hipSuccess) return e;
+  if (mode == GN_MODE_FULL) {
+    if ((e = B.nsm.ensure(n)) != hipSuccess) return e;
+    if ((e = B.nbg.ensure(n)) != hipSuccess) return e;
+  }
+  return e;
+}
+static hipError_t reserve_king_sort_buffers(Dev &d, size_t n, int mode) {
+  hipError_t e;
+  if ((e = d.kkeys.ensure(n)) != hipSuccess) return e;
+  if ((e = d.kkeys2.ensure(n)) != hipSuccess) return e;
+  if ((e = d.kidx.ensure(n)) != hipSuccess) return e;
+  if ((e = d.kperm.ensure(n)) != hipSuccess) return e;
+  return reserve_king_sort(n, mode != GN_MODE_SMALL, d.cur.sort_tmp.p, d.cur.sort_tmp.cap);
+}
+// evaluate_on sorts by king squares (default options): a small batch gains nothing from the order and
+// would pay the sort's launches on its latency (bench.py secondary.dropin)
+constexpr size_t KING_SORT_MIN = 1024;
+static bool king_sorted(const gn_ctx *ctx, size_t n) {
+  return ctx->king_sort == 2 || (ctx->king_sort == 1 && n >= KING_SORT_MIN);
+}
 // evaluate_on's optional arguments.
 struct EvalOnOpts {
   EvalEvents *ev = nullptr;           // recorded between the stages
@@ -729,25 +778,14 @@ static int evaluate_on(gn_ctx *ctx, Dev &d, const gn_board *b, size_t n, int mod
   EvalBufs &B = o.eb ? *o.eb : d.cur.eb;
   DevBuf<int2> &osm = B.osm, &obg = B.obg;
   DevBuf<uint8_t> &nsm = B.nsm, &nbg = B.nbg;
-  if (mode != GN_MODE_BIG) HIP_TRY(osm.ensure(n));
-  if (mode != GN_MODE_SMALL) HIP_TRY(obg.ensure(n));
-  if (mode == GN_MODE_FULL) {
-    HIP_TRY(nsm.ensure(n));
-    HIP_TRY(nbg.ensure(n));
-  }
+  HIP_TRY(reserve_eval_outputs(B, n, mode));
   auto mark = [&](hipEvent_t EvalEvents::*m) { return o.ev ? hipEventRecord(o.ev->*m, s) : hipSuccess; };
   const gn_eval_params &P = ctx->P;
   HIP_TRY(mark(&EvalEvents::begun)); // (mode FULL's selection runs inside the small net's launch: launch_eval_net cls)
   const uint32_t *perm = nullptr;
-  // a small batch (one game, a handful of in-check replies) gains nothing from the order and
-  // would pay the sort's launches on its latency (bench.py secondary.dropin)
-  constexpr size_t KING_SORT_MIN = 1024;
-  if (o.sort && (ctx->king_sort == 2 || (ctx->king_sort == 1 && n >= KING_SORT_MIN))) {
+  if (o.sort && king_sorted(ctx, n)) {
     if (n > 0x7FFFFFFFull) return fail(GN_E_INVALID, "king sort supports < 2^31 positions per call");
-    HIP_TRY(d.kkeys.ensure(n));
-    HIP_TRY(d.kkeys2.ensure(n));
-    HIP_TRY(d.kidx.ensure(n));
-    HIP_TRY(d.kperm.ensure(n));
+    HIP_TRY(reserve_king_sort_buffers(d, n, mode));
     HIP_TRY(king_sort(b, n, d.kkeys.p, d.kidx.p, d.kkeys2.p, d.kperm.p, mode != GN_MODE_SMALL, d.cur.sort_tmp.p,
                       d.cur.sort_tmp.cap, s));
     perm = d.kperm.p;
@@ -779,6 +817,12 @@ static Dev *slot(gn_ctx *ctx, int s) {
 // the lines calls' K
 static int check_n_lines(int n_lines) {
   if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
+  return GN_OK;
+}
+// the quiescent calls' depth
+static int check_quiesce_depth(int depth) {
+  if (depth < 1 || depth > GN_MAX_QUIESCE_DEPTH)
+    return fail(GN_E_INVALID, "quiescence depth %d outside 1..%d", depth, GN_MAX_QUIESCE_DEPTH);
   return GN_OK;
 }
 
@@ -1214,6 +1258,138 @@ static int extend_checks(gn_ctx *ctx, Dev &d, const Parent *parents, size_t n, c
   *extended = (size_t)cnt;
   return GN_OK;
 }
+// -------------------------------------------------- capture quiescence ----
+// The capture quiescence of one expansion level (include/gpu_nnue.h, gn_quiesce_device), the leaves
+// given as to extend_checks.  ext[j] = Q(leaf j, depth) where leaf j is searched (it has a legal move
+// and is in check, or it has a noisy legal move), GN_NOT_EXTENDED elsewhere; *searched = how many,
+// *nodes = the positions evaluated below them.  Level 0, the searched leaves, is selected by
+// quiesce_select_kernel, which also counts every leaf's searched moves (level 0's counts, once
+// compacted), and compacted by extend_boards_kernel into the extension's buffers; its
+// statics are rec's.  Level k + 1 is made from level k's compacted boards: the searched moves counted,
+// scanned, the level's size read back, its boards written and evaluated as positions by evaluate_on
+// (whose records carry the in-check and no-legal-move bits the rule needs).  Then one reduction per
+// level, bottom-up, and level 0's values scattered to ext.  Synchronous; every buffer is sized from
+// a read-back count before anything is queued on it and the kernels clamp their offsets to those
+// counts.  A level of 2^31 nodes fails the call with GN_E_CAPACITY, a failed allocation with
+// GN_E_NOMEM: every allocation of the stage goes through Q_ALLOC, those of the scans and of
+// evaluate_on included, which are reserved before the call that would make them (reserve_scan_u64,
+// reserve_eval_outputs, reserve_king_sort_buffers), and on failure the quiescence's level buffers and
+// level 0's share of the extension's are given back and the HIP error is cleared.  The stream is idle
+// on every return.  d.mu
+// held, inside a sequence on s, no expansion in flight on d.cur.
+static int quiesce_nomem(Dev &d, int level, size_t count, int depth) {
+  (void)hipGetLastError(); // (the failed allocation's error is not a later call's)
+  d.q.release();
+  Dev::Extend &X = d.ex; // level 0's share of the extension's buffers
+  X.sel.release(), X.pos.release(), X.idx.release(), X.boards.release(), X.rec.release(), X.sv.release();
+  return fail(GN_E_NOMEM,
+              "quiescence: no device memory for level %d (%zu nodes); lower GN_OPT_CHUNK_PARENTS or depth (%d)", level,
+              count, depth);
+}
+template <class Parent, class Off>
+static int quiesce_levels(gn_ctx *ctx, Dev &d, const Parent *parents, size_t n, const Off *offsets,
+                          const uint16_t *moves, const gn_eval *rec, size_t total, int mode, int depth, int32_t *ext,
+                          size_t *searched, size_t *nodes, hipStream_t s) {
+#define Q_ALLOC(level, count, expr)                                                                 \
+  do {                                                                                              \
+    if ((expr) != hipSuccess) return quiesce_nomem(d, (level), (count), depth);                     \
+  } while (0)
+  constexpr uint64_t LIMIT = 0x7FFFFFFFull;
+  if (total > LIMIT)
+    return fail(GN_E_CAPACITY, "quiescence: %zu leaves, a level holds < 2^31; lower GN_OPT_CHUNK_PARENTS (depth %d)", total,
+                depth);
+  Dev::Extend &X = d.ex;
+  Dev::Quiesce &Q = d.q;
+  Q_ALLOC(0, total, X.sel.ensure(total + 1));
+  Q_ALLOC(0, total, X.pos.ensure(total + 1));
+  Q_ALLOC(0, total, Q.lcnt.ensure(total));
+  Q_ALLOC(0, total, reserve_scan_u64(total + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap)); // (the scan then allocates nothing)
+  HIP_TRY(hipMemsetAsync(X.sel.p, 0, (total + 1) * sizeof(uint64_t), s));
+  HIP_TRY(launch_quiesce_select(parents, n, offsets, moves, total, d.tables.p, X.sel.p, Q.lcnt.p, ext, s));
+  HIP_TRY(exclusive_scan_u64(X.sel.p, X.pos.p, total + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap, s));
+  uint64_t m = 0;
+  HIP_TRY(hipMemcpyAsync(&m, X.pos.p + total, sizeof(m), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (!m) return GN_OK;
+  if (m > total) return fail(GN_E_HIP, "quiescence: %zu selected of %zu leaves", (size_t)m, total);
+  Q_ALLOC(0, m, X.idx.ensure(m));
+  Q_ALLOC(0, m, X.boards.ensure(m));
+  Q_ALLOC(0, m, X.sv.ensure(m));
+  Q_ALLOC(0, m, X.count.ensure(1));
+  HIP_TRY(launch_extend_boards(parents, n, offsets, moves, X.sel.p, X.pos.p, total, d.tables.p, X.idx.p, X.boards.p, X.sv.p,
+                               s));
+  // the levels, top-down: cnt[k] nodes at level k; top: the deepest level whose children were counted
+  size_t cnt[GN_MAX_QUIESCE_DEPTH + 2] = {m};
+  const gn_board *boards = X.boards.p;
+  size_t below = 0;
+  int top = depth - 1;
+  for (int k = 0; k < depth; ++k) {
+    Dev::Quiesce::Level &L = Q.lv[k];
+    Q_ALLOC(k, cnt[k], L.counts.ensure(cnt[k] + 1));
+    Q_ALLOC(k, cnt[k], L.offsets.ensure(cnt[k] + 1));
+    Q_ALLOC(k, cnt[k], reserve_scan_u64(cnt[k] + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap));
+    if (k) HIP_TRY(launch_quiesce_count(boards, cnt[k], d.tables.p, L.counts.p, s));
+    else HIP_TRY(launch_quiesce_level0_counts(X.sel.p, X.pos.p, Q.lcnt.p, total, L.counts.p, s)); // (counted by the selection)
+    HIP_TRY(exclusive_scan_u64(L.counts.p, L.offsets.p, cnt[k] + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap, s));
+    uint64_t t = 0;
+    HIP_TRY(hipMemcpyAsync(&t, L.offsets.p + cnt[k], sizeof(t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (t > LIMIT)
+      return fail(GN_E_CAPACITY,
+                  "quiescence: level %d holds %llu nodes, the limit is 2^31 - 1; lower GN_OPT_CHUNK_PARENTS or depth (%d)",
+                  k + 1, (unsigned long long)t, depth);
+    cnt[k + 1] = (size_t)t;
+    if (!t) { // no deeper level: every node of level k is valued by itself
+      top = k;
+      break;
+    }
+    Dev::Quiesce::Level &N = Q.lv[k + 1];
+    Q_ALLOC(k + 1, t, N.boards.ensure(t));
+    Q_ALLOC(k + 1, t, N.rec.ensure(t));
+    if (k + 1 < depth) Q_ALLOC(k + 1, t, N.val.ensure(t));
+    Q_ALLOC(k + 1, t, Q.moves.ensure(t));
+    Q_ALLOC(k + 1, t, Q.owner.ensure(t));
+    // (everything evaluate_on would allocate for the level: it then allocates nothing, so that no
+    // allocation of the stage can fail as anything but GN_E_NOMEM)
+    Q_ALLOC(k + 1, t, reserve_eval_outputs(d.cur.eb, t, mode));
+    if (king_sorted(ctx, t)) Q_ALLOC(k + 1, t, reserve_king_sort_buffers(d, t, mode));
+    HIP_TRY(launch_quiesce_children(boards, cnt[k], d.tables.p, L.offsets.p, t, Q.moves.p, Q.owner.p, N.boards.p, s));
+    if (int rc = evaluate_on(ctx, d, N.boards.p, t, mode, N.rec.p, s)) return rc;
+    below += t;
+    boards = N.boards.p;
+  }
+  // the reduction, bottom-up; level 0's records are the caller's, through idx
+  for (int k = top; k >= 0; --k) {
+    const size_t nc = cnt[k + 1];
+    const bool last = k + 1 == depth || !nc; // the children are valued statically (or there are none)
+    HIP_TRY(launch_quiesce_reduce(k ? Q.lv[k].rec.p : rec, k ? nullptr : X.idx.p, cnt[k], Q.lv[k].offsets.p, nc,
+                                  nc ? Q.lv[k + 1].rec.p : nullptr, last ? nullptr : Q.lv[k + 1].val.p,
+                                  k ? Q.lv[k].val.p : X.sv.p, s));
+  }
+  HIP_TRY(hipMemsetAsync(X.count.p, 0, sizeof(unsigned long long), s));
+  HIP_TRY(launch_extend_scatter(X.idx.p, X.sv.p, m, ext, X.count.p, s));
+  unsigned long long c = 0;
+  HIP_TRY(hipMemcpyAsync(&c, X.count.p, sizeof(c), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *searched = (size_t)c, *nodes = below;
+  return GN_OK;
+#undef Q_ALLOC
+}
+template <class Parent, class Off>
+static int quiesce(gn_ctx *ctx, Dev &d, const Parent *parents, size_t n, const Off *offsets, const uint16_t *moves,
+                   const gn_eval *rec, size_t total, int mode, int depth, int32_t *ext, size_t *searched, size_t *nodes,
+                   hipStream_t s) {
+  *searched = *nodes = 0;
+  if (depth < 1 || depth > GN_MAX_QUIESCE_DEPTH)
+    return fail(GN_E_INVALID, "bad quiescence depth %d (1..%d)", depth, GN_MAX_QUIESCE_DEPTH);
+  if (mode < GN_MODE_FULL || mode > GN_MODE_SMALL) return fail(GN_E_INVALID, "bad mode %d", mode);
+  if ((mode != GN_MODE_SMALL && !d.has[BIG]) || (mode != GN_MODE_BIG && !d.has[SMALL]))
+    return fail(GN_E_NONET, "mode %d needs a network that is not loaded", mode);
+  if (!total || !n) return GN_OK;
+  const int rc = quiesce_levels(ctx, d, parents, n, offsets, moves, rec, total, mode, depth, ext, searched, nodes, s);
+  if (rc) (void)hipStreamSynchronize(s); // (idle on every way out)
+  return rc;
+}
 // ------------------------------------------------------- one level -------
 // expand_level's optional arguments.
 struct LevelOpts {
@@ -1544,10 +1720,20 @@ static double ms_since(Clock::time_point t) {
 
 // The check extension (extend_checks) as a stage of a host-buffer call: its time and count into the
 // device's statistics
+// leaf (LEAF_CHECKS, or a quiescence depth 1..GN_MAX_QUIESCE_DEPTH): which of the two values the
+// leaves: the quiescent calls run quiesce here instead, into their own statistics.
+constexpr int LEAF_CHECKS = -1;
 template <class Parent, class Off>
 static int extend_stage(gn_ctx *ctx, Dev &d, const Parent *parents, size_t n, const Off *offsets,
-                        const uint16_t *moves, const gn_eval *rec, size_t total, int mode, int32_t *ext, hipStream_t s) {
+                        const uint16_t *moves, const gn_eval *rec, size_t total, int mode, int32_t *ext, hipStream_t s,
+                        int leaf) {
   const auto t0 = Clock::now();
+  if (leaf != LEAF_CHECKS) {
+    size_t ns = 0, nn = 0;
+    const int rc = quiesce(ctx, d, parents, n, offsets, moves, rec, total, mode, leaf, ext, &ns, &nn, s);
+    d.t_quiesce += ms_since(t0), d.n_qleaves += ns, d.n_qnodes += nn;
+    return rc;
+  }
   size_t ne = 0;
   const int rc = extend_checks(ctx, d, parents, n, offsets, moves, rec, total, mode, ext, &ne, s);
   d.t_extend += ms_since(t0), d.n_extended += ne;
@@ -1587,7 +1773,7 @@ static int run_shards(gn_ctx *ctx, const std::vector<size_t> &b, F &&f) {
 }
 
 static void reset_host_stats(gn_ctx *ctx) {
-  for (auto &dp : ctx->devs) dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = dp->t_keys = dp->t_extend = 0, dp->n_extended = 0;
+  for (auto &dp : ctx->devs) dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = dp->t_keys = dp->t_extend = dp->t_quiesce = 0, dp->n_extended = dp->n_qleaves = dp->n_qnodes = 0;
 }
 
 // Chunk bounds of a shard's m parents: cut only where `starts` allows (the first parent of each
@@ -1776,8 +1962,9 @@ struct ExpandOut {
   // parent of the shard (device; chunk c's at hist + chunks[c]); hist NULL: the plain ranking
   RankHistory history = NO_HISTORY;
   // gn_evaluate_games_lines_extended: each chunk's children in check are extended before the
-  // ranking (extend_stage), and the chunks run one after another
-  bool extend = false;
+  // ranking (extend_stage), and the chunks run one after another.  LEAF_CHECKS, or the quiescent
+  // call's depth (0: a plain call)
+  int extend = 0;
 };
 // Pass 2 of a shard (see above).  off: the shard's child offsets from pass 1.
 static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m, int mode,
@@ -1863,7 +2050,7 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
           // extension evaluates in the current set's and the score levels' buffers; t == 0: no entry
           // is read)
           if (o.extend)
-            if (int r = extend_stage(ctx, d, d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, t, mode, d.ext.p, s))
+            if (int r = extend_stage(ctx, d, d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, t, mode, d.ext.p, s, o.extend))
               return r;
           HIP_TRY(hipEventRecord(d.rev[0], s));
           HIP_TRY(launch_rank_children(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P, d.tables.p,
@@ -1885,7 +2072,7 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
         drain_chunk(k, pa, mp, t, cb);
         return GN_OK;
       },
-      o.extend);
+      o.extend != 0);
   const auto tt = Clock::now();
   for (int k = 0; k < 2; ++k) {
     const int r = join(k);
@@ -2115,7 +2302,8 @@ struct GamesCall {
   uint64_t total = 0;            // positions
   bool all_in_place = true;
   std::string last_err;          // the last failed game's message (gn_last_error after GN_OK)
-  bool extend = false;           // the _extended calls: the lines' leaves in check take their check extension
+  int extend = 0;                // the _extended calls: LEAF_CHECKS, the lines' leaves in check take their check
+                                 // extension; the _quiescent calls: their depth (extend_stage)
 };
 
 // host: root FENs parsed, UCI moves tokenized (the wire form, AcquireResponseBody.moves); games
@@ -2452,7 +2640,7 @@ int gn_evaluate_games_lines_history(gn_ctx *ctx, const gn_game *games, size_t n_
 
 static int evaluate_games_lines2(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines, bool history,
                                  uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
-                                 size_t position_cap, gn_line2 *lines, bool extend = false) {
+                                 size_t position_cap, gn_line2 *lines, int extend = 0) {
   if (int rc = check_n_lines(n_lines)) return rc;
   GamesCall c{ctx, games, n_games, mode, 0, n_lines, history, position_offsets, nullptr, game_status,
               position_out, position_cap, 0, nullptr, nullptr, nullptr, lines};
@@ -2464,7 +2652,15 @@ int gn_evaluate_games_lines2_extended(gn_ctx *ctx, const gn_game *games, size_t 
                                       int history, uint32_t *position_offsets, int32_t *game_status,
                                       gn_eval *position_out, size_t position_cap, gn_line2 *lines) {
   return evaluate_games_lines2(ctx, games, n_games, mode, n_lines, history != 0, position_offsets, game_status,
-                               position_out, position_cap, lines, true);
+                               position_out, position_cap, lines, LEAF_CHECKS);
+}
+
+int gn_evaluate_games_lines2_quiescent(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                       int history, int depth, uint32_t *position_offsets, int32_t *game_status,
+                                       gn_eval *position_out, size_t position_cap, gn_line2 *lines) {
+  if (int rc = check_quiesce_depth(depth)) return rc;
+  return evaluate_games_lines2(ctx, games, n_games, mode, n_lines, history != 0, position_offsets, game_status,
+                               position_out, position_cap, lines, depth);
 }
 
 int gn_evaluate_games_lines_extended(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
@@ -2473,7 +2669,18 @@ int gn_evaluate_games_lines_extended(gn_ctx *ctx, const gn_game *games, size_t n
   if (int rc = check_n_lines(n_lines)) return rc;
   GamesCall c{ctx, games, n_games, mode, 1, n_lines, history != 0, position_offsets, nullptr, game_status,
               position_out, position_cap, 0, nullptr, nullptr, lines};
-  c.extend = true;
+  c.extend = LEAF_CHECKS;
+  return evaluate_games(std::move(c));
+}
+
+int gn_evaluate_games_lines_quiescent(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                      int history, int depth, uint32_t *position_offsets, int32_t *game_status,
+                                      gn_eval *position_out, size_t position_cap, gn_line *lines) {
+  if (int rc = check_n_lines(n_lines)) return rc;
+  if (int rc = check_quiesce_depth(depth)) return rc;
+  GamesCall c{ctx, games, n_games, mode, 1, n_lines, history != 0, position_offsets, nullptr, game_status,
+              position_out, position_cap, 0, nullptr, nullptr, lines};
+  c.extend = depth;
   return evaluate_games(std::move(c));
 }
 
@@ -2972,6 +3179,22 @@ int gn_extend_checks_device(gn_ctx *ctx, int device_slot, const gn_board *d_pare
   return GN_OK;
 }
 
+int gn_quiesce_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
+                      const uint16_t *d_moves, const gn_eval *d_rec, size_t total, int mode, int depth, int32_t *d_ext,
+                      size_t *searched, size_t *nodes, void *stream) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d || !searched || !nodes) return fail(GN_E_INVALID, "bad argument");
+  *searched = *nodes = 0;
+  if (total && (!n || !d_parents || !d_offsets || !d_moves || !d_rec || !d_ext)) return fail(GN_E_INVALID, "NULL buffer");
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  const int rc = quiesce(ctx, *d, d_parents, n, d_offsets, d_moves, d_rec, total, mode, depth, d_ext, searched, nodes,
+                         call.s);
+  if (rc) return rc;
+  HIP_TRY(call.sg->finish()); // blocking (gpu_nnue.h): d_ext is written when the call returns
+  return GN_OK;
+}
+
 int gn_rank_children_extended_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
                                      const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out,
                                      const uint64_t *d_keys, size_t n_keys, const gn_history *d_hist,
@@ -3372,6 +3595,19 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
     *value = (int64_t)(m * 1e6);
     return GN_OK;
   }
+  case GN_STAT_QUIESCE_NS: { // the last host-buffer call's quiescence, the slowest device
+    double m = 0;
+    for (auto &dp : ctx->devs) m = std::max(m, dp->t_quiesce);
+    *value = (int64_t)(m * 1e6);
+    return GN_OK;
+  }
+  case GN_STAT_QUIESCE_LEAVES:  // ... its searched leaves
+  case GN_STAT_QUIESCE_NODES: { // ... and the nodes it evaluated, summed over the devices
+    int64_t sum = 0;
+    for (auto &dp : ctx->devs) sum += (int64_t)(option == GN_STAT_QUIESCE_LEAVES ? dp->n_qleaves : dp->n_qnodes);
+    *value = sum;
+    return GN_OK;
+  }
   case GN_STAT_EXTENDED_LEAVES: { // ... and its extended leaves, summed over the devices
     int64_t sum = 0;
     for (auto &dp : ctx->devs) sum += (int64_t)dp->n_extended;
@@ -3419,9 +3655,10 @@ int gn_expand_and_evaluate(gn_ctx *ctx, const char *const *parent_fens, size_t n
 // lines into out / lines (the shard's first parent's).  The chunks need no cut at game starts: the
 // keys are the whole shard's.
 // extend: the grandchildren in check are extended after the expansion (extend_stage; the children
-// as parents, the library's own boards), and the ranking takes their values.
+// as parents, the library's own boards), and the ranking takes their values; LEAF_CHECKS, or the
+// quiescent calls' depth (0: a plain call).
 static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m, int mode, int K, gn_eval *out,
-                         gn_line2 *lines, const RankHistory &history, bool extend) {
+                         gn_line2 *lines, const RankHistory &history, int extend) {
   hipStream_t s = d.stream;
   Dev::Lines2 &x = d.l2;
   // 1,024 parents are ~1 M grandchildren: a few hundred MB of records, boards and partial sums
@@ -3452,7 +3689,7 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
     const RankHistory h = {history.keys, history.n_keys, history.hist ? history.hist + a : nullptr};
     if (extend) { // (t == 0 or g == 0: nothing is read)
       HIP_TRY(x.gext.ensure(std::max<size_t>(g, 1)));
-      if ((rc = extend_stage(ctx, d, x.ch.p, t, x.goff.p, x.gmv.p, x.gco.p, g, mode, x.gext.p, s)) != GN_OK) return rc;
+      if ((rc = extend_stage(ctx, d, x.ch.p, t, x.goff.p, x.gmv.p, x.gco.p, g, mode, x.gext.p, s, extend)) != GN_OK) return rc;
     }
     HIP_TRY(hipEventRecord(d.rev[0], s));
     HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables.p, K,
@@ -3474,7 +3711,7 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
 // gn_evaluate_lines2: the boards sharded equally over the devices, each shard uploaded and run
 // through lines2_chunks
 static int lines2_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int mode, int K, gn_eval *out,
-                              gn_line2 *lines, bool extend) {
+                              gn_line2 *lines, int extend) {
   const size_t nd = ctx->devs.size();
   std::vector<size_t> b(nd + 1);
   partition(nullptr, n, (int)nd, b.data());
@@ -3500,7 +3737,7 @@ static int games_lines2(const GamesCall &c, GameShard &sh, Dev &d) {
 }
 
 static int evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,
-                           gn_line2 *lines, bool extend) {
+                           gn_line2 *lines, int extend) {
   if (!slot(ctx, 0)) return fail(GN_E_INVALID, "bad context");
   if (int rc = check_n_lines(n_lines)) return rc;
   if (n && (!fens || !out || !lines)) return fail(GN_E_INVALID, "NULL argument");
@@ -3512,12 +3749,18 @@ static int evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int m
 
 int gn_evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,
                        gn_line2 *lines) {
-  return evaluate_lines2(ctx, fens, n, mode, n_lines, out, lines, false);
+  return evaluate_lines2(ctx, fens, n, mode, n_lines, out, lines, 0);
 }
 
 int gn_evaluate_lines2_extended(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,
                                 gn_line2 *lines) {
-  return evaluate_lines2(ctx, fens, n, mode, n_lines, out, lines, true);
+  return evaluate_lines2(ctx, fens, n, mode, n_lines, out, lines, LEAF_CHECKS);
+}
+
+int gn_evaluate_lines2_quiescent(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, int depth,
+                                 gn_eval *out, gn_line2 *lines) {
+  if (int rc = check_quiesce_depth(depth)) return rc;
+  return evaluate_lines2(ctx, fens, n, mode, n_lines, out, lines, depth);
 }
 
 int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {

@@ -328,6 +328,32 @@ hipError_t launch_extend_boards(const gn_board *parents, size_t n, const uint32_
                                 uint32_t *idx, gn_board *sb, int32_t *sv, hipStream_t s);
 hipError_t launch_extend_scatter(const uint32_t *idx, const int32_t *sv, size_t m, int32_t *ext,
                                  unsigned long long *extended, hipStream_t s);
+// Capture quiescence of one expansion level (gpu_nnue.hip quiesce; the rule in include/gpu_nnue.h at
+// gn_quiesce_device).  select: ext[j] = GN_NOT_EXTENDED for all j < total and sel[c] = 1 where leaf c is searched
+// (sel zeroed by the caller, total + 1 entries; parents as for launch_extend_boards, which then makes
+// the selected leaves' boards; lcnt[c] = leaf c's searched moves, total entries).  count: counts[i] = the searched moves of node i (all legal moves in
+// check, the noisy legal ones otherwise; the library's own boards), counts[n] = 0.  children: those
+// moves, their owners and boards at offsets (the scan of counts), at most nc.  reduce: val[i] of the
+// m nodes from their records (rec[idx[i]] with idx: level 0's child records) and their children's
+// values cval, or with cval NULL the children's static part from their position records crec.
+hipError_t launch_quiesce_select(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
+                                 size_t total, const Tables *tables, uint64_t *sel, uint32_t *lcnt, int32_t *ext,
+                                 hipStream_t s);
+hipError_t launch_quiesce_select(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
+                                 size_t total, const Tables *tables, uint64_t *sel, uint32_t *lcnt, int32_t *ext,
+                                 hipStream_t s);
+// level 0's counts (m + 1, m = pos[total]) compacted from the selection pass's per-leaf lcnt
+hipError_t launch_quiesce_level0_counts(const uint64_t *sel, const uint64_t *pos, const uint32_t *lcnt, size_t total,
+                                        uint64_t *counts, hipStream_t s);
+hipError_t launch_quiesce_count(const gn_board *boards, size_t n, const Tables *tables, uint64_t *counts, hipStream_t s);
+hipError_t launch_quiesce_children(const gn_board *boards, size_t n, const Tables *tables, const uint64_t *offsets,
+                                   size_t nc, uint16_t *moves, uint32_t *owner, gn_board *children, hipStream_t s);
+hipError_t launch_quiesce_reduce(const gn_eval *rec, const uint32_t *idx, size_t m, const uint64_t *off, size_t nc,
+                                 const gn_eval *crec, const int32_t *cval, int32_t *val, hipStream_t s);
+// exclusive_scan_u64's / king_sort's temporary storage for n1 counts / n boards grown now, so that
+// the call itself does not allocate (a caller that reports a failed allocation as its own)
+hipError_t reserve_scan_u64(size_t n1, void *&temp, size_t &temp_bytes);
+hipError_t reserve_king_sort(size_t n, bool placement, void *&temp, size_t &temp_bytes);
 // narrowing copy of offsets for the C-ABI
 hipError_t launch_offsets_u32(const uint64_t *in, size_t n, uint32_t *out, hipStream_t s);
 // exclusive scan of n + 1 counts (counts[n] must be 0); temp grows on demand

@@ -2152,6 +2152,191 @@ hipError_t launch_write_children(const gn_board *boards, size_t n, const Tables 
   return hipGetLastError();
 }
 
+// ---- capture quiescence of one expansion level (include/gpu_nnue.h gn_quiesce_device) ----
+// Q(x, d) of the header's rule, level by level (gpu_nnue.hip quiesce): level 0 are the searched
+// leaves, level k + 1 the searched moves' children of level k's nodes.  Siblings of the movegen
+// kernels above with the rule's filter on gen_legal's moves, so those keep their code and registers.
+//
+// A noisy move of B: a capture (never castling, which is encoded king-takes-own-rook), an
+// en-passant capture, or a promotion to a queen.
+__device__ __forceinline__ bool noisy_move(const Board &B, uint16_t m) {
+  const int type = move_type(m);
+  if (type == MT_CASTLING) return false;
+  if (type == MT_EN_PASSANT) return true;
+  if (color_bb(B, B.stm ^ 1) & sqbb(move_to(m))) return true;
+  return type == MT_PROMOTION && move_promo(m) == QUEEN;
+}
+// The moves the quiescence searches from B: every legal move when B is in check, the noisy legal
+// ones otherwise; emit as gen_legal's.
+template <class F>
+__device__ __forceinline__ void gen_searched(const Board &B, const Tables &T, F &&emit) {
+  const bool check = in_check(B, T);
+  gen_legal(B, T, [&](uint16_t m) {
+    if (check || noisy_move(B, m)) return emit_stop(emit, m);
+    return false;
+  });
+}
+
+// Level 0's selection, shaped like extend_boards_kernel: a 32-lane group per parent, a lane per
+// leaf, the parent unpacked once (through the gate when it is a caller's board).  ext[j] =
+// GN_NOT_EXTENDED for every j < total (grid-strided before the parents' loop, so also where the
+// caller's offsets cover fewer than total leaves; no lane reads ext); sel[c] = 1 where leaf c is
+// searched: it has a legal move and is in check, or it has a noisy legal move; lcnt[c] = its
+// searched moves, which are level 0's counts once compacted (quiesce_level0_counts_kernel), so a
+// leaf's moves are generated once here.  sel is zeroed by the caller: a rejected parent's leaves
+// and sel[total] stay 0, and their lcnt is never read.
+template <class Parent, class Off>
+__global__ void __launch_bounds__(RANK_WG)
+    quiesce_select_kernel(const Parent *__restrict__ parents, size_t n, const Off *__restrict__ offsets,
+                          const uint16_t *__restrict__ moves, size_t total, const Tables *__restrict__ tables,
+                          uint64_t *__restrict__ sel, uint32_t *__restrict__ lcnt, int32_t *__restrict__ ext) {
+  __shared__ Tables T;
+  load_tables(T, tables);
+  constexpr int W = 32;
+  const int lane = threadIdx.x & (W - 1);
+  const size_t stride = (size_t)gridDim.x * (RANK_WG / W);
+  for (size_t j = (size_t)blockIdx.x * RANK_WG + threadIdx.x; j < total; j += (size_t)gridDim.x * RANK_WG)
+    ext[j] = GN_NOT_EXTENDED;
+  for (size_t p = (size_t)blockIdx.x * (RANK_WG / W) + threadIdx.x / W; p < n; p += stride) {
+    // (clamped to the leaves the call covers: sel holds total + 1 entries)
+    const uint64_t c1 = std::min<uint64_t>(offsets[p + 1], total), c0 = std::min<uint64_t>(offsets[p], c1);
+    if (c0 >= c1) continue;
+    Board B;
+    if (!rank_parent(parents[p], B, T)) continue;
+    for (uint64_t c = c0 + lane; c < c1; c += W) {
+      const Board C = do_move(B, moves[c], nullptr);
+      uint32_t k = 0;
+      gen_searched(C, T, [&](uint16_t) { ++k; });
+      lcnt[c] = k;
+      if (k) sel[c] = 1;
+    }
+  }
+}
+// level 0's counts from the selection pass: counts[pos[c]] = lcnt[c] for a selected leaf c,
+// counts[pos[total]] = 0 (the scan's end)
+__global__ void quiesce_level0_counts_kernel(const uint64_t *__restrict__ sel, const uint64_t *__restrict__ pos,
+                                             const uint32_t *__restrict__ lcnt, size_t total,
+                                             uint64_t *__restrict__ counts) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c > total) return;
+  if (c == total) counts[pos[total]] = 0;
+  else if (sel[c]) counts[pos[c]] = lcnt[c];
+}
+
+// counts[i] = the searched moves of node i of a level (the library's own compacted boards: no
+// gate), counts[n] = 0 for the scan
+__global__ void quiesce_count_kernel(const gn_board *__restrict__ boards, size_t n, const Tables *__restrict__ tables,
+                                     uint64_t *__restrict__ counts) {
+  __shared__ Tables T;
+  load_tables(T, tables);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  uint64_t c = 0;
+  Board B;
+  if (i < n && unpack_fields(boards[i], B)) gen_searched(B, T, [&](uint16_t) { ++c; });
+  counts[i] = c;
+}
+
+// ... and their moves and owners at offsets[i] (the scan of counts), clamped to the nc children the
+// next level was sized for; child_boards_kernel then makes the boards.
+__global__ void quiesce_moves_kernel(const gn_board *__restrict__ boards, size_t n, const Tables *__restrict__ tables,
+                                     const uint64_t *__restrict__ offsets, size_t nc, uint16_t *__restrict__ moves,
+                                     uint32_t *__restrict__ owner) {
+  __shared__ Tables T;
+  load_tables(T, tables);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Board B;
+  if (!unpack_fields(boards[i], B)) return;
+  uint64_t k = offsets[i];
+  gen_searched(B, T, [&](uint16_t m) {
+    if (k < nc) moves[k] = m, owner[k] = (uint32_t)i;
+    ++k;
+  });
+}
+
+// One level of the reduction, a lane per node i (rules 1 to 4): its record r (rec[idx[i]] with idx,
+// level 0's, whose nodes all have a legal move and whose child records carry no no-moves flag; else
+// rec[i], a position record of evaluate_on), its children [off[i], off[i + 1]) clamped to nc.  A
+// child's value is cval[c], or with cval NULL (the children are the last level, d == 0) its static
+// part: mate / stalemate, else final_v.  val[i] = mate / 0 without a legal move; in check the maximum
+// over the children of negate_ply; otherwise the maximum of final_v and those.
+__global__ void quiesce_reduce_kernel(const gn_eval *__restrict__ rec, const uint32_t *__restrict__ idx, size_t m,
+                                      const uint64_t *__restrict__ off, size_t nc, const gn_eval *__restrict__ crec,
+                                      const int32_t *__restrict__ cval, int32_t *__restrict__ val) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const gn_eval r = rec[idx ? idx[i] : i];
+  const bool check = (r.flags & GN_FLAG_IN_CHECK) != 0;
+  int32_t best;
+  if (!idx && (r.flags & GN_FLAG_NO_MOVES)) {
+    best = check ? -VALUE_MATE : 0;
+  } else {
+    best = check ? INT32_MIN : r.final_v;
+    const uint64_t c1 = std::min<uint64_t>(off[i + 1], nc);
+    for (uint64_t c = std::min<uint64_t>(off[i], c1); c < c1; ++c) {
+      int32_t v;
+      if (cval) v = cval[c];
+      else {
+        const gn_eval k = crec[c];
+        v = (k.flags & GN_FLAG_NO_MOVES) ? ((k.flags & GN_FLAG_IN_CHECK) ? -VALUE_MATE : 0) : k.final_v;
+      }
+      v = negate_ply(v);
+      best = v > best ? v : best;
+    }
+    if (best == INT32_MIN) best = r.final_v; // (unreachable: a node in check with a move has children)
+  }
+  val[i] = best;
+}
+
+template <class Parent, class Off>
+static hipError_t quiesce_select_t(const Parent *parents, size_t n, const Off *offsets, const uint16_t *moves, size_t total,
+                                   const Tables *tables, uint64_t *sel, uint32_t *lcnt, int32_t *ext, hipStream_t s) {
+  if (!n) return hipSuccess;
+  constexpr size_t per_wg = RANK_WG / 32, max_blocks = 8192;
+  const size_t blocks = std::min<size_t>((n + per_wg - 1) / per_wg, max_blocks);
+  hipLaunchKernelGGL((quiesce_select_kernel<Parent, Off>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets, moves,
+                     total, tables, sel, lcnt, ext);
+  return hipGetLastError();
+}
+hipError_t launch_quiesce_select(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
+                                 size_t total, const Tables *tables, uint64_t *sel, uint32_t *lcnt, int32_t *ext,
+                                 hipStream_t s) {
+  return quiesce_select_t(unpacked, n, offsets, moves, total, tables, sel, lcnt, ext, s);
+}
+hipError_t launch_quiesce_select(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
+                                 size_t total, const Tables *tables, uint64_t *sel, uint32_t *lcnt, int32_t *ext,
+                                 hipStream_t s) {
+  return quiesce_select_t(parents, n, offsets, moves, total, tables, sel, lcnt, ext, s);
+}
+hipError_t launch_quiesce_level0_counts(const uint64_t *sel, const uint64_t *pos, const uint32_t *lcnt, size_t total,
+                                        uint64_t *counts, hipStream_t s) {
+  hipLaunchKernelGGL(quiesce_level0_counts_kernel, dim3(blocks_for(total + 1, 256)), dim3(256), 0, s, sel, pos, lcnt, total,
+                     counts);
+  return hipGetLastError();
+}
+hipError_t launch_quiesce_count(const gn_board *boards, size_t n, const Tables *tables, uint64_t *counts, hipStream_t s) {
+  hipLaunchKernelGGL(quiesce_count_kernel, dim3(blocks_for(n + 1, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, n, tables,
+                     counts);
+  return hipGetLastError();
+}
+hipError_t launch_quiesce_children(const gn_board *boards, size_t n, const Tables *tables, const uint64_t *offsets,
+                                   size_t nc, uint16_t *moves, uint32_t *owner, gn_board *children, hipStream_t s) {
+  if (!n || !nc) return hipSuccess;
+  hipLaunchKernelGGL(quiesce_moves_kernel, dim3(blocks_for(n, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, n, tables,
+                     offsets, nc, moves, owner);
+  hipLaunchKernelGGL(child_boards_kernel, dim3(blocks_for(nc, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, (size_t)0, nc,
+                     moves, owner, children, (ChildDelta *)nullptr, (unsigned long long *)nullptr, (const Board *)nullptr);
+  return hipGetLastError();
+}
+hipError_t launch_quiesce_reduce(const gn_eval *rec, const uint32_t *idx, size_t m, const uint64_t *off, size_t nc,
+                                 const gn_eval *crec, const int32_t *cval, int32_t *val, hipStream_t s) {
+  if (!m) return hipSuccess;
+  hipLaunchKernelGGL(quiesce_reduce_kernel, dim3(blocks_for(m, 256)), dim3(256), 0, s, rec, idx, m, off, nc, crec, cval,
+                     val);
+  return hipGetLastError();
+}
+
 hipError_t launch_count_sum(const gn_board *boards, size_t n, const Tables *tables, unsigned long long *total,
                             hipStream_t s) {
   if (!n) return hipSuccess;
@@ -2282,6 +2467,36 @@ hipError_t exclusive_scan_u64(const uint64_t *counts, uint64_t *offsets, size_t 
     temp_bytes = need;
   }
   return hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, counts, offsets, n1, s);
+}
+
+// The temporary storage exclusive_scan_u64 (n1 counts) and king_sort (n boards) would grow on demand,
+// grown now: a caller that must report a failed allocation as its own (gpu_nnue.hip quiesce) reserves
+// first, after which neither allocates.  The queries read no memory and launch nothing.
+static hipError_t reserve_temp(size_t need, void *&temp, size_t &temp_bytes) {
+  if (need <= temp_bytes) return hipSuccess;
+  if (temp) (void)hipFree(temp);
+  temp = nullptr;
+  temp_bytes = 0;
+  const hipError_t e = hipMalloc(&temp, need);
+  if (e == hipSuccess) temp_bytes = need;
+  return e;
+}
+hipError_t reserve_scan_u64(size_t n1, void *&temp, size_t &temp_bytes) {
+  size_t need = 0;
+  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, (const uint64_t *)nullptr, (uint64_t *)nullptr, n1,
+                                                        (hipStream_t) nullptr);
+  return e != hipSuccess ? e : reserve_temp(need, temp, temp_bytes);
+}
+template <class Key>
+static hipError_t king_sort_need(size_t n, size_t &need) {
+  return hipcub::DeviceRadixSort::SortPairs(nullptr, need, (const Key *)nullptr, (Key *)nullptr, (const uint32_t *)nullptr,
+                                            (uint32_t *)nullptr, (int)n, 0, (int)(8 * sizeof(Key)), (hipStream_t) nullptr);
+}
+hipError_t reserve_king_sort(size_t n, bool placement, void *&temp, size_t &temp_bytes) {
+  if (!n) return hipSuccess;
+  size_t need = 0;
+  const hipError_t e = placement ? king_sort_need<uint64_t>(n, need) : king_sort_need<uint16_t>(n, need);
+  return e != hipSuccess ? e : reserve_temp(need, temp, temp_bytes);
 }
 
 hipError_t launch_expand_net(const NetDevice &net, const gn_board *parents, size_t n, const uint64_t *offsets,

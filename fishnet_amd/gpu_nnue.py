@@ -63,7 +63,9 @@ EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_
            "gn_rank_children_history_device", "gn_evaluate_games_lines_history",
            "gn_rank_lines2_history_device", "gn_evaluate_games_lines2", "gn_evaluate_games_lines2_history",
            "gn_extend_checks_device", "gn_rank_children_extended_device", "gn_rank_lines2_extended_device",
-           "gn_evaluate_lines2_extended", "gn_evaluate_games_lines2_extended", "gn_evaluate_games_lines_extended"]
+           "gn_evaluate_lines2_extended", "gn_evaluate_games_lines2_extended", "gn_evaluate_games_lines_extended",
+           "gn_quiesce_device", "gn_evaluate_lines2_quiescent", "gn_evaluate_games_lines2_quiescent",
+           "gn_evaluate_games_lines_quiescent"]
 OPT_INCREMENTAL_CHILDREN, OPT_XCD_SWIZZLE, OPT_KING_SORT, OPT_CHAIN, OPT_KING_CACHE = 1, 2, 3, 4, 5
 OPT_CHUNK_PARENTS, OPT_COALESCE, OPT_STREAM_SLICES, OPT_FAST_BATCH, OPT_EXPAND_PIPELINE = 6, 7, 8, 9, 10
 STAT_PLAN_NS, STAT_STREAM_NS, STAT_SCRATCH_PADS, STAT_FINISH_NS = 101, 102, 103, 104
@@ -71,6 +73,8 @@ STAT_ZERO_ROW_ENTRIES = 105
 STAT_BATCH_LAUNCHES, STAT_BATCH_CALLS, STAT_FAST_BATCHES, STAT_FAST_FALLBACKS = 117, 118, 119, 120
 STAT_RANK_NS, STAT_RANK2_NS, STAT_KEYS_NS = 121, 122, 123
 STAT_EXTEND_NS, STAT_EXTENDED_LEAVES = 124, 125
+STAT_QUIESCE_NS, STAT_QUIESCE_LEAVES, STAT_QUIESCE_NODES = 126, 127, 128
+MAX_QUIESCE_DEPTH = 4  # GN_MAX_QUIESCE_DEPTH
 NOT_EXTENDED = -(2 ** 31)  # GN_NOT_EXTENDED: a d_ext entry of a leaf the check extension does not value
 HOST_STAGES = {"parse": 110, "upload": 111, "replay": 112, "compute": 113, "download": 114, "tail": 115, "total": 116}
 EXPAND_STAGES = ["count_scan", "total_readback", "write_children", "classify", "small_net", "big_net", "finalize",
@@ -203,6 +207,10 @@ def lib():
         "gn_evaluate_lines2_extended": [vp, vp, sz, i32, i32, vp, vp],
         "gn_evaluate_games_lines2_extended": [vp, vp, sz, i32, i32, i32, vp, vp, vp, sz, vp],
         "gn_evaluate_games_lines_extended": [vp, vp, sz, i32, i32, i32, vp, vp, vp, sz, vp],
+        "gn_quiesce_device": [vp, i32, vp, sz, vp, vp, vp, sz, i32, i32, vp, C.POINTER(sz), C.POINTER(sz), vp],
+        "gn_evaluate_lines2_quiescent": [vp, vp, sz, i32, i32, i32, vp, vp],
+        "gn_evaluate_games_lines2_quiescent": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp],
+        "gn_evaluate_games_lines_quiescent": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -565,6 +573,27 @@ class GpuNnue:
         """gn_evaluate_lines2_extended: evaluate_lines2 with check-extended grandchildren."""
         return self.evaluate_lines2(fens, n_lines, mode, call=lib().gn_evaluate_lines2_extended)
 
+    def evaluate_games_lines_quiescent(self, games, n_lines, depth, mode=MODE_FULL, cap=None, history=False):
+        """gn_evaluate_games_lines_quiescent: evaluate_games_lines whose searched leaves (in check, or with
+        a noisy move) take the capture quiescence Q(leaf, depth) (FLAG_SEARCHED); history: with the
+        game-history draws as well."""
+        f = lib().gn_evaluate_games_lines_quiescent
+        call = lambda h, arr, ng, mode, K, *rest: f(h, arr, ng, mode, K, int(bool(history)), depth, *rest)
+        return self._games_lines(call, LINE_DTYPE, games, n_lines, mode, cap)
+
+    def evaluate_games_lines2_quiescent(self, games, n_lines, depth, mode=MODE_FULL, cap=None, history=False):
+        """gn_evaluate_games_lines2_quiescent: evaluate_games_lines2 whose searched grandchildren take
+        Q(grandchild, depth) (FLAG_SEARCHED when the chosen reply's was); history: with the draws."""
+        f = lib().gn_evaluate_games_lines2_quiescent
+        call = lambda h, arr, ng, mode, K, *rest: f(h, arr, ng, mode, K, int(bool(history)), depth, *rest)
+        return self._games_lines(call, LINE2_DTYPE, games, n_lines, mode, cap)
+
+    def evaluate_lines2_quiescent(self, fens, n_lines, depth, mode=MODE_FULL):
+        """gn_evaluate_lines2_quiescent: evaluate_lines2 with quiescent grandchildren."""
+        f = lib().gn_evaluate_lines2_quiescent
+        call = lambda h, arr, n, mode, K, *rest: f(h, arr, n, mode, K, depth, *rest)
+        return self.evaluate_lines2(fens, n_lines, mode, call=call)
+
     def evaluate_games_lines_history(self, games, n_lines, mode=MODE_FULL, cap=None):
         """gn_evaluate_games_lines_history: evaluate_games_lines with each game's history."""
         return self.evaluate_games_lines(games, n_lines, mode, cap, history=True)
@@ -693,6 +722,16 @@ class GpuNnue:
         _check(lib().gn_extend_checks_device(self.h, slot, p(d_parents), n, p(d_offsets), p(d_moves), p(d_rec), total,
                                              mode, p(d_ext), C.byref(ne), stream))
         return ne.value
+
+    def quiesce_device(self, d_parents, n, d_offsets, d_moves, d_rec, total, mode, depth, d_ext, stream=None, slot=0):
+        """gn_quiesce_device: d_ext[total] (int32) = Q(leaf, depth) of each searched leaf of a preceding
+        expansion level (NOT_EXTENDED elsewhere), for the extended ranking calls.  Returns (searched
+        leaves, nodes evaluated below them).  Blocking.  The buffers may be None when total is 0."""
+        ns, nn = C.c_size_t(), C.c_size_t()
+        p = lambda b: b.ptr if b is not None else None
+        _check(lib().gn_quiesce_device(self.h, slot, p(d_parents), n, p(d_offsets), p(d_moves), p(d_rec), total, mode,
+                                       depth, p(d_ext), C.byref(ns), C.byref(nn), stream))
+        return ns.value, nn.value
 
     def rank_children_extended_device(self, d_parents, n, d_offsets, d_moves, d_child_out, d_ext, n_lines, d_lines,
                                       d_keys=None, n_keys=0, d_hist=None, stream=None, slot=0):

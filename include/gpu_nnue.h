@@ -200,6 +200,14 @@ extern "C" {
                                          host-buffer call) ...                             */
 #define GN_STAT_EXTENDED_LEAVES 125   /* ... and the leaves it extended, summed over the
                                          devices (0 after any other host-buffer call)      */
+#define GN_STAT_QUIESCE_NS 126        /* the capture quiescence (gn_line "quiescent") in the last
+                                         gn_evaluate_lines2_quiescent or
+                                         gn_evaluate_games_lines[2]_quiescent, summed over its
+                                         chunks (the slowest device; 0 after any other
+                                         host-buffer call) ...                             */
+#define GN_STAT_QUIESCE_LEAVES 127    /* ... the leaves it searched, summed over the devices */
+#define GN_STAT_QUIESCE_NODES 128     /* ... and the positions it evaluated below them (both
+                                         0 after any other host-buffer call)               */
 #define GN_STAT_BATCH_LAUNCHES 117    /* merged gn_evaluate_batch launches since load ...   */
 #define GN_STAT_BATCH_CALLS 118       /* ... and the calls they served (GN_OPT_COALESCE)    */
 #define GN_STAT_FAST_BATCHES 119      /* evaluations run by the captured small-batch graphs
@@ -220,7 +228,8 @@ extern "C" {
 #define GN_FLAG_SEARCHED 128u /* score from the in-check rule over the legal replies
                                  (best_move set), not from the static evaluation; on
                                  gn_line.flags / gn_line2.flags of the check-extended
-                                 calls only: the line's leaf is valued by that rule  */
+                                 calls only: the line's leaf is valued by that rule;
+                                 of the quiescent calls: by the quiescence Q(x, depth) */
 #define GN_FLAG_NO_MOVES 256u /* no legal move: checkmate (with IN_CHECK) or stalemate */
 #define GN_FLAG_DRAW 512u /* gn_line.flags and gn_line2.flags of the history calls only: the
                              line ends in a position drawn by rule (threefold repetition or
@@ -321,8 +330,36 @@ typedef struct gn_child {
  * position none of whose leaves is in check with a legal move has byte-equal lines from the plain
  * and the extended call; for a child with a reply, (R(c), reply) is line 1 of the extended one-ply
  * ranking over the children as parents; and mate values can appear on lines through a check
- * (`mate -1` for a check that allows a mating reply, `mate 2`, ...). */
-#define GN_NOT_EXTENDED INT32_MIN /* a d_ext entry of a leaf the extension does not value */
+ * (`mate -1` for a check that allows a mating reply, `mate 2`, ...).
+ *
+ * Quiescent lines (gn_quiesce_device, gn_evaluate_lines2_quiescent,
+ * gn_evaluate_games_lines_quiescent, gn_evaluate_games_lines2_quiescent).  The calls above value a
+ * leaf that is not in check by its static final_v even when the side to move can take a queen or
+ * the leaf sits in the middle of an exchange.  The quiescent calls value a non-quiet leaf by a
+ * capture search to a fixed depth, on the device.
+ * Noisy moves.  A legal move is noisy when it is a capture (the destination holds an enemy piece
+ * and the move is not castling: castling is encoded king-takes-own-rook and is never noisy, Chess960
+ * included), an en-passant capture, or a promotion to a queen, capturing or not.  An underpromotion
+ * is noisy only when it captures.
+ * Q(x, d), self-contained (it does not call the score rule):
+ *   1. x has no legal move: -VALUE_MATE when in check, else 0;
+ *   2. d == 0: x's static final_v in the call's mode (in check too, as the score rule at depth 0);
+ *   3. x is in check: the maximum over ALL legal moves of negate_ply(Q(child, d - 1)); no stand pat;
+ *   4. otherwise max(final_v(x), the maximum over the noisy legal moves of negate_ply(Q(child, d - 1))).
+ * The leaf value, depth in 1..GN_MAX_QUIESCE_DEPTH: a leaf x of a line is searched when it has a
+ * legal move and is in check, or has a legal move and at least one noisy legal move.  A searched
+ * leaf's value is Q(x, depth) and its line carries GN_FLAG_SEARCHED; every other leaf keeps
+ * GN_NOT_EXTENDED and the ranking values it as the plain calls do: mate, stalemate or static.  The
+ * precedence in the ranking is the extended calls': no legal move, then (history forms) drawn by
+ * rule, then the d_ext override, then static.  The quiescence knows no history and no fifty-move
+ * rule inside its tree, as the extension knows none, and its own moves are not reported (plies stays
+ * 1 or 2).  The quiescent calls do not also run the check extension: rule 3 is how they treat a leaf
+ * in check.  Consequences: for a leaf in check, Q(x, 1) equals the score rule's value(x, 1); for a
+ * searched leaf not in check, Q(x, d) >= final_v(x); a position none of whose leaves is searched has
+ * byte-equal lines from the plain and the quiescent call; and mate values can appear on a line
+ * through a capture. */
+#define GN_NOT_EXTENDED INT32_MIN /* a d_ext entry of a leaf the extension / quiescence does not value */
+#define GN_MAX_QUIESCE_DEPTH 4    /* the quiescent calls' depth is 1..GN_MAX_QUIESCE_DEPTH */
 #define GN_MAX_LINES 8 /* lichess sends multipv <= 5 */
 typedef struct gn_line {
   int32_t value;  /* the rule value, p's side-to-move POV, Stockfish units              */
@@ -333,7 +370,7 @@ typedef struct gn_line {
                      GN_FLAG_NO_MOVES: the move ends the game (mate or stalemate);
                      GN_FLAG_NO_SCORE: an empty line; GN_FLAG_DRAW: the history calls
                      only (gn_history below); GN_FLAG_SEARCHED: the check-extended
-                     calls only (above)                                                  */
+                     and the quiescent calls only (above)                                */
 } gn_line;
 
 /* Game-history draws in ranked lines (gn_rank_children_history_device,
@@ -707,6 +744,28 @@ GN_API int gn_evaluate_games_lines_extended(gn_ctx *ctx, const gn_game *games, s
                                             int history, uint32_t *position_offsets, int32_t *game_status,
                                             gn_eval *position_out, size_t position_cap, gn_line *lines);
 
+/* The three calls above with quiescent leaves (the rule at gn_line, "quiescent") instead of
+ * check-extended ones: the same drivers, the leaves valued by the capture quiescence to `depth`
+ * (1..GN_MAX_QUIESCE_DEPTH, else GN_E_INVALID) after each chunk's expansion; the check extension
+ * does not run.  out / position_offsets, game_status, position_out and the GN_E_CAPACITY behaviour
+ * are byte-equal to the plain calls', and so are the lines of every position none of whose leaves is
+ * searched.  The one-ply games call runs its chunks one after another, as
+ * gn_evaluate_games_lines_extended does.  Results are identical for every GN_OPT_CHUNK_PARENTS,
+ * GN_OPT_EXPAND_PIPELINE and device count.  The quiescence's levels live in device memory sized
+ * from their counts: a level of 2^31 nodes or more fails the call with GN_E_CAPACITY, a failed
+ * device allocation of the stage (its levels, its scans and its evaluations alike) with GN_E_NOMEM
+ * after the stage's buffers are given back; the message names GN_OPT_CHUNK_PARENTS and depth, the
+ * two handles on the size, and the context stays usable.  GN_STAT_QUIESCE_NS / GN_STAT_QUIESCE_LEAVES /
+ * GN_STAT_QUIESCE_NODES: the quiescence's time, searched leaves and evaluated nodes. */
+GN_API int gn_evaluate_lines2_quiescent(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines,
+                                        int depth, gn_eval *out, gn_line2 *lines); /* lines[n * n_lines] */
+GN_API int gn_evaluate_games_lines2_quiescent(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                              int history, int depth, uint32_t *position_offsets, int32_t *game_status,
+                                              gn_eval *position_out, size_t position_cap, gn_line2 *lines);
+GN_API int gn_evaluate_games_lines_quiescent(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                             int history, int depth, uint32_t *position_offsets, int32_t *game_status,
+                                             gn_eval *position_out, size_t position_cap, gn_line *lines);
+
 /* The partitioner the library uses to shard work over the devices of a context and
  * that multi-process callers use to shard over ranks: contiguous ranges of n_items
  * items, bounds[k] = first item of shard k, bounds[n_shards] = n_items; shard k
@@ -821,7 +880,23 @@ GN_API int gn_rank_lines2_history_device(gn_ctx *ctx, int device_slot, const gn_
 GN_API int gn_extend_checks_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
                                    const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_rec,
                                    size_t total, int mode, int32_t *d_ext, size_t *extended, void *stream);
-/* gn_rank_children_history_device with check-extended leaves: d_ext as gn_extend_checks_device
+/* The capture quiescence of one expansion level (the rule at gn_line, "quiescent"): inputs and
+ * contract as gn_extend_checks_device -- one level of gn_expand_device, or level 2 of
+ * gn_expand2_device with the children as parents.  d_ext[j] (total entries) = Q(leaf j, depth) where
+ * leaf j is searched, GN_NOT_EXTENDED everywhere else (entries no parent's offsets cover included);
+ * *searched = the number of searched leaves,
+ * *nodes = the positions evaluated below them (the searched moves' children, level by level down
+ * to depth).  There is no ranking call of its own: gn_rank_children_extended_device and
+ * gn_rank_lines2_extended_device take this d_ext as they take the extension's.  d_rec is only read
+ * (the leaves' statics).  Blocking.  total == 0: GN_OK, nothing is read and the buffers may be NULL.
+ * depth outside 1..GN_MAX_QUIESCE_DEPTH: GN_E_INVALID.  GN_E_CAPACITY / GN_E_NOMEM as for the
+ * host-buffer quiescent calls: the stream is idle on return and the context usable afterwards.
+ * GN_E_NONET as elsewhere. */
+GN_API int gn_quiesce_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                             const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_rec, size_t total,
+                             int mode, int depth, int32_t *d_ext, size_t *searched, size_t *nodes, void *stream);
+/* gn_rank_children_history_device with check-extended (or quiescent) leaves: d_ext as
+ * gn_extend_checks_device (or gn_quiesce_device)
  * wrote it for the same expansion (NULL: nothing is extended).  d_hist == NULL selects no history
  * at all (not even the fifty-move part; d_keys / n_keys are then ignored): the plain rule plus the
  * extension.  Asynchronous, no read-back. */

@@ -303,6 +303,73 @@ impl GpuNnue {
         Ok((offsets, status, evals, lines))
     }
 
+    /// evaluate_lines2 with quiescent leaves (gn_evaluate_lines2_quiescent; include/gpu_nnue.h at
+    /// gn_line, "quiescent"): a grandchild in check, or with a capture, an en-passant capture or a
+    /// queen promotion to play, is valued by the capture search Q(x, depth) on the device instead of
+    /// by its static evaluation; depth is 1..=sys::MAX_QUIESCE_DEPTH.  A line whose chosen reply
+    /// reaches such a grandchild carries GN_FLAG_SEARCHED.  The records equal evaluate_lines2's.
+    pub fn evaluate_lines2_quiescent(&self, fens: &[Fen], n_lines: usize, depth: i32, mode: i32)
+                                     -> Result<(Vec<GpuEval>, Vec<GpuLine2>), GpuError> {
+        let owned: Vec<CString> = fens.iter().map(|f| CString::new(f.to_string()).unwrap()).collect();
+        let ptrs: Vec<*const std::os::raw::c_char> = owned.iter().map(|c| c.as_ptr()).collect();
+        let mut evals = vec![GpuEval::default(); fens.len()];
+        let mut lines = vec![GpuLine2::default(); fens.len() * n_lines];
+        // SAFETY: ptrs / evals have fens.len() elements, lines fens.len() * n_lines; the call
+        // checks n_lines and depth before it writes.
+        check(unsafe {
+            sys::gn_evaluate_lines2_quiescent(self.0, ptrs.as_ptr(), ptrs.len(), mode, n_lines as i32, depth,
+                                              evals.as_mut_ptr(), lines.as_mut_ptr())
+        })?;
+        Ok((evals, lines))
+    }
+
+    /// evaluate_games_lines with quiescent leaves (gn_evaluate_games_lines_quiescent): a move whose
+    /// child is searched is valued by Q(child, depth) (GN_FLAG_SEARCHED).  history: with the game's
+    /// history, where a child drawn by rule comes first (GN_FLAG_DRAW, not searched); mode: GN_MODE_*.
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn evaluate_games_lines_quiescent(&self, games: &[(CString, CString, Vec<u32>)], n_lines: usize, depth: i32,
+                                          history: bool, mode: i32)
+                                          -> Result<(Vec<u32>, Vec<i32>, Vec<GpuEval>, Vec<GpuLine>), GpuError> {
+        let (gs, cap) = games_and_capacity(games);
+        let mut offsets = vec![0u32; games.len() + 1];
+        let mut status = vec![0i32; games.len()];
+        let mut evals = vec![GpuEval::default(); cap];
+        let mut lines = vec![GpuLine::default(); cap * n_lines];
+        // SAFETY: as evaluate_games_lines_extended; depth is checked before anything is written.
+        check(unsafe {
+            sys::gn_evaluate_games_lines_quiescent(self.0, gs.as_ptr(), gs.len(), mode, n_lines as i32, history as i32,
+                                                   depth, offsets.as_mut_ptr(), status.as_mut_ptr(), evals.as_mut_ptr(),
+                                                   cap, lines.as_mut_ptr())
+        })?;
+        let total = offsets[games.len()] as usize;
+        evals.truncate(total);
+        lines.truncate(total * n_lines);
+        Ok((offsets, status, evals, lines))
+    }
+
+    /// evaluate_games_lines2 with quiescent leaves (gn_evaluate_games_lines2_quiescent): the searched
+    /// grandchildren are valued by Q(grandchild, depth); history and mode as above.
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn evaluate_games_lines2_quiescent(&self, games: &[(CString, CString, Vec<u32>)], n_lines: usize, depth: i32,
+                                           history: bool, mode: i32)
+                                           -> Result<(Vec<u32>, Vec<i32>, Vec<GpuEval>, Vec<GpuLine2>), GpuError> {
+        let (gs, cap) = games_and_capacity(games);
+        let mut offsets = vec![0u32; games.len() + 1];
+        let mut status = vec![0i32; games.len()];
+        let mut evals = vec![GpuEval::default(); cap];
+        let mut lines = vec![GpuLine2::default(); cap * n_lines];
+        // SAFETY: as evaluate_games_lines_quiescent.
+        check(unsafe {
+            sys::gn_evaluate_games_lines2_quiescent(self.0, gs.as_ptr(), gs.len(), mode, n_lines as i32, history as i32,
+                                                    depth, offsets.as_mut_ptr(), status.as_mut_ptr(), evals.as_mut_ptr(),
+                                                    cap, lines.as_mut_ptr())
+        })?;
+        let total = offsets[games.len()] as usize;
+        evals.truncate(total);
+        lines.truncate(total * n_lines);
+        Ok((offsets, status, evals, lines))
+    }
+
     /// Whole acquired batches: replay root FEN + UCI moves (skipPositions honoured) and
     /// evaluate every position and every legal child; buffers grow on GN_E_CAPACITY.
     pub fn evaluate_games(&self, games: &[(CString, CString, Vec<u32>)], mode: i32) -> Result<GamesResult, GpuError> {

@@ -62,6 +62,9 @@ pub const GN_STAT_EXTEND_NS: c_int = 124;
 pub const GN_STAT_EXTENDED_LEAVES: c_int = 125;
 /// A d_ext entry of a leaf the check extension does not value (gn_extend_checks_device).
 pub const GN_NOT_EXTENDED: i32 = i32::MIN;
+pub const GN_STAT_QUIESCE_NS: c_int = 126;
+pub const GN_STAT_QUIESCE_LEAVES: c_int = 127;
+pub const GN_STAT_QUIESCE_NODES: c_int = 128;
 
 // per-position flags
 pub const GN_FLAG_IN_CHECK: u16 = 1;
@@ -114,6 +117,8 @@ impl gn_child {
 
 /// The header's GN_MAX_LINES: the most lines per position the ranking calls return.
 pub const MAX_LINES: usize = 8;
+/// The header's GN_MAX_QUIESCE_DEPTH: the quiescent calls' depth is 1..=MAX_QUIESCE_DEPTH.
+pub const MAX_QUIESCE_DEPTH: c_int = 4;
 
 /// One ranked line of a position (MultiPV, 12 bytes): the rule value of a legal move, its score
 /// (`cp`, or the mate distance with GN_FLAG_MATE), the move and its flags (GN_FLAG_IN_CHECK: the
@@ -262,6 +267,18 @@ extern "C" {
                                             n_lines: c_int, history: c_int, position_offsets: *mut u32,
                                             game_status: *mut i32, position_out: *mut gn_eval, position_cap: usize,
                                             lines: *mut gn_line) -> c_int;
+    pub fn gn_evaluate_lines2_quiescent(ctx: *mut gn_ctx, fens: *const *const c_char, n: usize, mode: c_int,
+                                        n_lines: c_int, depth: c_int, out: *mut gn_eval, lines: *mut gn_line2)
+                                        -> c_int;
+    pub fn gn_evaluate_games_lines2_quiescent(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
+                                              n_lines: c_int, history: c_int, depth: c_int,
+                                              position_offsets: *mut u32, game_status: *mut i32,
+                                              position_out: *mut gn_eval, position_cap: usize, lines: *mut gn_line2)
+                                              -> c_int;
+    pub fn gn_evaluate_games_lines_quiescent(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
+                                             n_lines: c_int, history: c_int, depth: c_int, position_offsets: *mut u32,
+                                             game_status: *mut i32, position_out: *mut gn_eval, position_cap: usize,
+                                             lines: *mut gn_line) -> c_int;
     pub fn gn_partition(weights: *const u32, n_items: usize, n_shards: c_int, bounds: *mut usize) -> c_int;
     pub fn gn_perft(ctx: *mut gn_ctx, fen: *const c_char, depth: c_int, nodes: *mut u64) -> c_int;
     pub fn gn_pack_fens(fens: *const *const c_char, n: usize, out: *mut gn_board, ok: *mut u8) -> c_int;
@@ -303,6 +320,10 @@ extern "C" {
     pub fn gn_extend_checks_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
                                    d_offsets: *const u32, d_moves: *const u16, d_rec: *const gn_eval, total: usize,
                                    mode: c_int, d_ext: *mut i32, extended: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn gn_quiesce_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                             d_offsets: *const u32, d_moves: *const u16, d_rec: *const gn_eval, total: usize,
+                             mode: c_int, depth: c_int, d_ext: *mut i32, searched: *mut usize, nodes: *mut usize,
+                             stream: *mut c_void) -> c_int;
     pub fn gn_rank_children_extended_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
                                             d_offsets: *const u32, d_moves: *const u16, d_child_out: *const gn_eval,
                                             d_keys: *const u64, n_keys: usize, d_hist: *const gn_history,
