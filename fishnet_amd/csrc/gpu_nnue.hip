@@ -249,6 +249,20 @@ struct EvalBufs {
   DevBuf<uint8_t> nsm, nbg;
 };
 
+// How a ranked-lines call values its lines' leaves: by their static records (the plain calls); the
+// leaves in check by the score rule (the _extended calls); or the searched leaves by the capture
+// quiescence to `depth` plies, 1..GN_MAX_QUIESCE_DEPTH (the _quiescent calls; check_leaf_rule).
+struct LeafRule {
+  enum Kind { STATIC, CHECKS, QUIESCE } kind = STATIC;
+  int depth = 0; // QUIESCE alone
+  static LeafRule checks() { return {CHECKS, 0}; }
+  static LeafRule quiesce(int depth) { return {QUIESCE, depth}; }
+  bool extends() const { return kind != STATIC; } // the call runs the leaf stage, and its ranking takes ext
+};
+struct LeafCount { // one run of the leaf stage: the leaves it valued, the positions evaluated below them
+  size_t leaves = 0, nodes = 0;
+};
+
 // ---- the drop-in's small batches ------------------------------------
 // fishnet's GPU backend sends one game per gn_evaluate_batch (/root/reference/src/stockfish.rs:
 // 36-47, src/main.rs:306-338: a chunk per worker call), ~80 positions, a few of them in check.
@@ -395,24 +409,21 @@ struct Dev {
     DevBuf<gn_board> ch;
     DevBuf<uint16_t> mv, gmv;
     DevBuf<gn_line2> ln;
-    DevBuf<int32_t> gext; // the extended calls: the grandchildren's check extensions
+    DevBuf<int32_t> gext; // a rule that extends: the grandchildren's values from the leaf stage
   } l2;
-  // the check extension of one expansion level (extend_checks): the selection and its scan, the
-  // selected leaves' indices, boards, records and rule values, the count of extended ones; ext:
-  // the one-ply extended games call's per-chunk extensions
-  struct Extend {
+  // the leaf stage of one expansion level (value_leaves).  The selected leaves (level 0): the
+  // selection and its scan, their indices, boards and values, the count of valued ones; rec: the
+  // check extension's own records of them; ext: the one-ply games calls' per-chunk leaf values.
+  // The quiescence's levels: lv[k] holds level k's searched-move counts and their scan and, for
+  // k >= 1, its boards, position records and values; moves / owner: the level being made
+  struct LeafStage {
     DevBuf<uint64_t> sel, pos;
     DevBuf<uint32_t> idx;
     DevBuf<gn_board> boards;
     DevBuf<gn_eval> rec;
     DevBuf<int32_t> sv;
     DevBuf<unsigned long long> count;
-  } ex;
-  DevBuf<int32_t> ext;
-  // the capture quiescence of one expansion level (quiesce): level 0 (the searched leaves) lives in
-  // ex; lv[k] holds level k's searched-move counts and their scan and, for k >= 1, its boards,
-  // position records and values; moves / owner: the level being made
-  struct Quiesce {
+    DevBuf<int32_t> ext;
     struct Level {
       DevBuf<gn_board> boards;
       DevBuf<gn_eval> rec;
@@ -421,17 +432,19 @@ struct Dev {
     } lv[GN_MAX_QUIESCE_DEPTH + 1];
     DevBuf<uint16_t> moves;
     DevBuf<uint32_t> owner;
-    DevBuf<uint32_t> lcnt; // every leaf's searched moves, from the selection pass
-    void release() {
+    DevBuf<uint32_t> lcnt; // every leaf's searched moves, from the quiescence's selection pass
+    void release() { // (a quiescent call's failed allocation: the levels, and what of level 0 grows with the leaves)
       for (Level &l : lv) l.boards.release(), l.rec.release(), l.val.release(), l.counts.release(), l.offsets.release();
       moves.release(), owner.release(), lcnt.release();
+      sel.release(), pos.release(), idx.release(), boards.release(), rec.release(), sv.release();
     }
-  } q;
-  double t_quiesce = 0;     // the quiescence stage of the last host-buffer call (GN_STAT_QUIESCE_NS), ms
-  uint64_t n_qleaves = 0;   // ... the leaves it searched (GN_STAT_QUIESCE_LEAVES)
-  uint64_t n_qnodes = 0;    // ... and the nodes it evaluated below them (GN_STAT_QUIESCE_NODES)
-  double t_extend = 0;     // the extension stage of the last host-buffer call (GN_STAT_EXTEND_NS), ms
-  uint64_t n_extended = 0; // ... and the leaves it extended (GN_STAT_EXTENDED_LEAVES)
+    // the stage in the last host-buffer call, by the rule's kind (extend_stage): GN_STAT_EXTEND_NS /
+    // _QUIESCE_NS in ms, GN_STAT_EXTENDED_LEAVES / _QUIESCE_LEAVES, GN_STAT_QUIESCE_NODES
+    struct Stats {
+      double ms = 0;
+      uint64_t leaves = 0, nodes = 0;
+    } stats[3];
+  } leaf;
   DevBuf<gn_board> roots, rboards, par;
   DevBuf<uint64_t> moff;
   DevBuf<uint16_t> codes, smoves;
@@ -819,10 +832,10 @@ static int check_n_lines(int n_lines) {
   if (n_lines < 1 || n_lines > GN_MAX_LINES) return fail(GN_E_INVALID, "n_lines %d outside 1..%d", n_lines, GN_MAX_LINES);
   return GN_OK;
 }
-// the quiescent calls' depth
-static int check_quiesce_depth(int depth) {
-  if (depth < 1 || depth > GN_MAX_QUIESCE_DEPTH)
-    return fail(GN_E_INVALID, "quiescence depth %d outside 1..%d", depth, GN_MAX_QUIESCE_DEPTH);
+// ... and their leaf rule: the quiescent calls' depth
+static int check_leaf_rule(LeafRule rule) {
+  if (rule.kind == LeafRule::QUIESCE && (rule.depth < 1 || rule.depth > GN_MAX_QUIESCE_DEPTH))
+    return fail(GN_E_INVALID, "quiescence depth %d outside 1..%d", rule.depth, GN_MAX_QUIESCE_DEPTH);
   return GN_OK;
 }
 
@@ -886,6 +899,15 @@ static int finalize_all(gn_ctx *ctx, Dev &d, const gn_board *parents, const gn_b
   return GN_OK;
 }
 
+// The exclusive scan of counts[0, n] (counts[n] == 0) into offsets (the current set's temporary
+// storage), and *total = offsets[n] read back: synchronous, the stream is idle on success.
+static hipError_t scan_total(Dev &d, const uint64_t *counts, uint64_t *offsets, size_t n, hipStream_t s, uint64_t *total) {
+  *total = 0;
+  hipError_t e = exclusive_scan_u64(counts, offsets, n + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(total, offsets + n, sizeof(*total), hipMemcpyDeviceToHost, s);
+  return e == hipSuccess ? hipStreamSynchronize(s) : e;
+}
+
 // Legal-child count of n boards (a capacity query), synchronously.
 static hipError_t count_children(Dev &d, const gn_board *parents, size_t n, hipStream_t s, size_t *total) {
   ExpSet &x = d.cur;
@@ -893,10 +915,8 @@ static hipError_t count_children(Dev &d, const gn_board *parents, size_t n, hipS
   if ((e = x.counts.ensure(n + 1)) != hipSuccess || (e = x.offsets.ensure(n + 1)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(x.counts.p + n, 0, sizeof(uint64_t), s)) != hipSuccess) return e;
   if ((e = launch_count_children(parents, n, d.tables.p, x.counts.p, s)) != hipSuccess) return e;
-  if ((e = exclusive_scan_u64(x.counts.p, x.offsets.p, n + 1, x.scan_tmp.p, x.scan_tmp.cap, s)) != hipSuccess) return e;
   uint64_t t = 0;
-  if ((e = hipMemcpyAsync(&t, x.offsets.p + n, sizeof(t), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+  if ((e = scan_total(d, x.counts.p, x.offsets.p, n, s, &t)) != hipSuccess) return e;
   *total = (size_t)t;
   return hipSuccess;
 }
@@ -1161,10 +1181,8 @@ static int resolve_scores(gn_ctx *ctx, Dev &d, const gn_board *boards, size_t n,
   HIP_TRY(L.sel.ensure(n + 1));
   HIP_TRY(L.pos.ensure(n + 1));
   HIP_TRY(launch_score_select(out, n, L.sel.p, s));
-  HIP_TRY(exclusive_scan_u64(L.sel.p, L.pos.p, n + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap, s));
-  uint64_t m = 0;
-  HIP_TRY(hipMemcpyAsync(&m, L.pos.p + n, sizeof(m), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  uint64_t m = 0, t = 0; // the positions in check with a legal move, and their replies
+  HIP_TRY(scan_total(d, L.sel.p, L.pos.p, n, s, &m));
   if (!m) return GN_OK;
   HIP_TRY(L.idx.ensure(m));
   HIP_TRY(L.boards.ensure(m));
@@ -1172,169 +1190,105 @@ static int resolve_scores(gn_ctx *ctx, Dev &d, const gn_board *boards, size_t n,
   HIP_TRY(L.offsets.ensure(m + 1));
   HIP_TRY(launch_score_gather(boards, L.sel.p, L.pos.p, n, replies ? nullptr : d.tables.p, L.idx.p, L.boards.p, s));
   if (replies) {
-    uint64_t t = 0;
     HIP_TRY(launch_score_replies(L.idx.p, m, d.cur.offsets.p, L.counts.p, L.offsets.p, d.cur.scan_tmp.p,
                                  d.cur.scan_tmp.cap, &t, s));
-    HIP_TRY(L.moves.ensure(std::max<uint64_t>(t, 1)));
-    HIP_TRY(L.children.ensure(std::max<uint64_t>(t, 1)));
-    HIP_TRY(L.ce.ensure(std::max<uint64_t>(t, 1)));
-    HIP_TRY(L.sv.ensure(std::max<uint64_t>(t, 1)));
+  } else {
+    HIP_TRY(hipMemsetAsync(L.counts.p + m, 0, sizeof(uint64_t), s));
+    HIP_TRY(launch_count_children(L.boards.p, m, d.tables.p, L.counts.p, s));
+    HIP_TRY(scan_total(d, L.counts.p, L.offsets.p, m, s, &t));
+  }
+  const uint64_t cap = std::max<uint64_t>(t, 1);
+  HIP_TRY(L.moves.ensure(cap));
+  HIP_TRY(L.children.ensure(cap));
+  HIP_TRY(L.ce.ensure(cap));
+  HIP_TRY(L.sv.ensure(cap));
+  if (replies) { // copied from the expansion's records
     HIP_TRY(launch_score_replies_fill(L.idx.p, m, d.cur.offsets.p, L.offsets.p, replies->rec, replies->moves,
                                       d.cur.unpacked.p, d.tables.p, L.ce.p, L.children.p, L.moves.p, s));
-    int rc = resolve_scores(ctx, d, L.children.p, t, mode, L.ce.p, L.sv.p, s, depth - 1);
-    if (rc) return rc;
-    HIP_TRY(launch_score_reduce(L.boards.p, m, L.idx.p, L.offsets.p, L.moves.p, L.ce.p, L.sv.p, ctx->P, out, sv_out,
-                                s));
-    return GN_OK;
+  } else { // generated and evaluated as positions
+    HIP_TRY(L.owner.ensure(cap));
+    HIP_TRY(launch_write_children(L.boards.p, m, d.tables.p, L.offsets.p, 0, t, L.children.p, L.moves.p, L.owner.p,
+                                  nullptr, nullptr, 1, nullptr, s));
+    if (int rc = evaluate_on(ctx, d, L.children.p, t, mode, L.ce.p, s)) return rc;
   }
-  HIP_TRY(hipMemsetAsync(L.counts.p + m, 0, sizeof(uint64_t), s));
-  HIP_TRY(launch_count_children(L.boards.p, m, d.tables.p, L.counts.p, s));
-  HIP_TRY(exclusive_scan_u64(L.counts.p, L.offsets.p, m + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap, s));
-  uint64_t t = 0;
-  HIP_TRY(hipMemcpyAsync(&t, L.offsets.p + m, sizeof(t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(L.moves.ensure(std::max<uint64_t>(t, 1)));
-  HIP_TRY(L.owner.ensure(std::max<uint64_t>(t, 1)));
-  HIP_TRY(L.children.ensure(std::max<uint64_t>(t, 1)));
-  HIP_TRY(L.ce.ensure(std::max<uint64_t>(t, 1)));
-  HIP_TRY(L.sv.ensure(std::max<uint64_t>(t, 1)));
-  HIP_TRY(launch_write_children(L.boards.p, m, d.tables.p, L.offsets.p, 0, t, L.children.p, L.moves.p, L.owner.p,
-                                nullptr, nullptr, 1, nullptr, s));
-  int rc = evaluate_on(ctx, d, L.children.p, t, mode, L.ce.p, s);
-  if (rc) return rc;
-  if ((rc = resolve_scores(ctx, d, L.children.p, t, mode, L.ce.p, L.sv.p, s, depth - 1)) != GN_OK) return rc;
+  if (int rc = resolve_scores(ctx, d, L.children.p, t, mode, L.ce.p, L.sv.p, s, depth - 1)) return rc;
   HIP_TRY(launch_score_reduce(L.boards.p, m, L.idx.p, L.offsets.p, L.moves.p, L.ce.p, L.sv.p, ctx->P, out, sv_out, s));
   return GN_OK;
 }
 
-// ---------------------------------------------------- check extension ----
-// The check extension of one expansion level (include/gpu_nnue.h, gn_extend_checks_device): the
-// leaves [offsets[i], offsets[i + 1]) of the n parents (moves, records rec; the parents unpacked
-// with 64-bit offsets as write_children left them, or packed with the C-ABI's 32-bit offsets).
-// ext[j] = value(leaf j, 2) of the score rule where leaf j is in check with a legal move,
-// GN_NOT_EXTENDED elsewhere; *extended = how many.  The leaves whose records say in check are
-// selected and their boards made (extend_boards_kernel), then they are positions: evaluate_on and
-// resolve_scores with its sv output, as gn_evaluate_device runs them, on the extension's own
-// records -- resolve_scores rewrites score / flags / best_move of what it is given, so it never
-// sees rec.  A selected leaf without a legal move is no position in check with a move to the score
-// rule: its value stays GN_NOT_EXTENDED.  Synchronous (the counts size the next launches; every
-// buffer is sized from a read-back count before anything is queued on it); the stream is idle on
-// return.  d.mu held, inside a sequence on s, no expansion in flight on d.cur.
+// --------------------------------------------------------- leaf stage ----
+// The leaves of one expansion level: the children [offsets[i], offsets[i + 1]) of the n parents, their
+// moves and records rec, total of them.  The parents are unpacked with 64-bit offsets, as
+// write_children left them in the set, or packed with the C-ABI's 32-bit offsets.
 template <class Parent, class Off>
-static int extend_checks(gn_ctx *ctx, Dev &d, const Parent *parents, size_t n, const Off *offsets,
-                         const uint16_t *moves, const gn_eval *rec, size_t total, int mode, int32_t *ext,
-                         size_t *extended, hipStream_t s) {
-  *extended = 0;
-  if (mode < GN_MODE_FULL || mode > GN_MODE_SMALL) return fail(GN_E_INVALID, "bad mode %d", mode);
-  if ((mode != GN_MODE_SMALL && !d.has[BIG]) || (mode != GN_MODE_BIG && !d.has[SMALL]))
-    return fail(GN_E_NONET, "mode %d needs a network that is not loaded", mode);
-  if (!total || !n) return GN_OK;
-  if (total > 0x7FFFFFFFull) return fail(GN_E_INVALID, "the check extension supports < 2^31 leaves per call");
-  Dev::Extend &X = d.ex;
-  HIP_TRY(X.sel.ensure(total + 1));
-  HIP_TRY(X.pos.ensure(total + 1));
-  HIP_TRY(launch_extend_select(rec, total, X.sel.p, ext, s));
-  HIP_TRY(exclusive_scan_u64(X.sel.p, X.pos.p, total + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap, s));
-  uint64_t m = 0;
-  HIP_TRY(hipMemcpyAsync(&m, X.pos.p + total, sizeof(m), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (!m) return GN_OK;
-  if (m > total) return fail(GN_E_HIP, "check extension: %zu selected of %zu leaves", (size_t)m, total);
-  HIP_TRY(X.idx.ensure(m));
-  HIP_TRY(X.boards.ensure(m));
-  HIP_TRY(X.rec.ensure(m));
-  HIP_TRY(X.sv.ensure(m));
-  HIP_TRY(X.count.ensure(1));
-  HIP_TRY(launch_extend_boards(parents, n, offsets, moves, X.sel.p, X.pos.p, total, d.tables.p, X.idx.p, X.boards.p, X.sv.p,
-                               s));
-  int rc = evaluate_on(ctx, d, X.boards.p, m, mode, X.rec.p, s);
-  if (!rc) rc = resolve_scores(ctx, d, X.boards.p, m, mode, X.rec.p, X.sv.p, s, 2);
-  if (rc) return rc;
-  HIP_TRY(hipMemsetAsync(X.count.p, 0, sizeof(unsigned long long), s));
-  HIP_TRY(launch_extend_scatter(X.idx.p, X.sv.p, m, ext, X.count.p, s));
-  unsigned long long cnt = 0;
-  HIP_TRY(hipMemcpyAsync(&cnt, X.count.p, sizeof(cnt), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  *extended = (size_t)cnt;
-  return GN_OK;
+struct Leaves {
+  const Parent *parents;
+  size_t n;
+  const Off *offsets;
+  const uint16_t *moves;
+  const gn_eval *rec;
+  size_t total;
+};
+using UnpackedLeaves = Leaves<Board, uint64_t>;
+using PackedLeaves = Leaves<gn_board, uint32_t>;
+
+// How the leaf stage reports a failed device allocation, which is the rule's.  The check extension
+// fails with GN_E_HIP, as every other launch sequence does.  A quiescent call fails with GN_E_NOMEM,
+// naming the two handles on its size, after it has given the stage's buffers back and cleared the
+// HIP error (it is not a later call's).
+struct LeafAlloc {
+  Dev &d;
+  LeafRule rule;
+  int check(int level, size_t count, hipError_t e) const {
+    if (e == hipSuccess) return GN_OK;
+    if (rule.kind != LeafRule::QUIESCE)
+      return fail(GN_E_HIP, "check extension: device allocation for %zu leaves failed: %s", count, hipGetErrorString(e));
+    (void)hipGetLastError();
+    d.leaf.release();
+    return fail(GN_E_NOMEM,
+                "quiescence: no device memory for level %d (%zu nodes); lower GN_OPT_CHUNK_PARENTS or depth (%d)", level,
+                count, rule.depth);
+  }
+};
+#define LEAF_ALLOC(level, count, expr) \
+  do { if (int rc_ = alloc.check((level), (count), (expr))) return rc_; } while (0)
+
+// CHECKS values the m selected leaves (d.leaf.boards -> d.leaf.sv) as positions: evaluate_on and
+// resolve_scores with its sv output, as gn_evaluate_device runs them, on the stage's own records --
+// resolve_scores rewrites what it is given, so it never sees the caller's.  A selected leaf without
+// a legal move is no position in check with a move to the score rule: it stays GN_NOT_EXTENDED.
+static int extend_checks(gn_ctx *ctx, Dev &d, size_t m, int mode, const LeafAlloc &alloc, hipStream_t s) {
+  Dev::LeafStage &X = d.leaf;
+  LEAF_ALLOC(0, m, X.rec.ensure(m));
+  if (int rc = evaluate_on(ctx, d, X.boards.p, m, mode, X.rec.p, s)) return rc;
+  return resolve_scores(ctx, d, X.boards.p, m, mode, X.rec.p, X.sv.p, s, 2);
 }
-// -------------------------------------------------- capture quiescence ----
-// The capture quiescence of one expansion level (include/gpu_nnue.h, gn_quiesce_device), the leaves
-// given as to extend_checks.  ext[j] = Q(leaf j, depth) where leaf j is searched (it has a legal move
-// and is in check, or it has a noisy legal move), GN_NOT_EXTENDED elsewhere; *searched = how many,
-// *nodes = the positions evaluated below them.  Level 0, the searched leaves, is selected by
-// quiesce_select_kernel, which also counts every leaf's searched moves (level 0's counts, once
-// compacted), and compacted by extend_boards_kernel into the extension's buffers; its
-// statics are rec's.  Level k + 1 is made from level k's compacted boards: the searched moves counted,
-// scanned, the level's size read back, its boards written and evaluated as positions by evaluate_on
-// (whose records carry the in-check and no-legal-move bits the rule needs).  Then one reduction per
-// level, bottom-up, and level 0's values scattered to ext.  Synchronous; every buffer is sized from
-// a read-back count before anything is queued on it and the kernels clamp their offsets to those
-// counts.  A level of 2^31 nodes fails the call with GN_E_CAPACITY, a failed allocation with
-// GN_E_NOMEM: every allocation of the stage goes through Q_ALLOC, those of the scans and of
-// evaluate_on included, which are reserved before the call that would make them (reserve_scan_u64,
-// reserve_eval_outputs, reserve_king_sort_buffers), and on failure the quiescence's level buffers and
-// level 0's share of the extension's are given back and the HIP error is cleared.  The stream is idle
-// on every return.  d.mu
-// held, inside a sequence on s, no expansion in flight on d.cur.
-static int quiesce_nomem(Dev &d, int level, size_t count, int depth) {
-  (void)hipGetLastError(); // (the failed allocation's error is not a later call's)
-  d.q.release();
-  Dev::Extend &X = d.ex; // level 0's share of the extension's buffers
-  X.sel.release(), X.pos.release(), X.idx.release(), X.boards.release(), X.rec.release(), X.sv.release();
-  return fail(GN_E_NOMEM,
-              "quiescence: no device memory for level %d (%zu nodes); lower GN_OPT_CHUNK_PARENTS or depth (%d)", level,
-              count, depth);
-}
-template <class Parent, class Off>
-static int quiesce_levels(gn_ctx *ctx, Dev &d, const Parent *parents, size_t n, const Off *offsets,
-                          const uint16_t *moves, const gn_eval *rec, size_t total, int mode, int depth, int32_t *ext,
-                          size_t *searched, size_t *nodes, hipStream_t s) {
-#define Q_ALLOC(level, count, expr)                                                                 \
-  do {                                                                                              \
-    if ((expr) != hipSuccess) return quiesce_nomem(d, (level), (count), depth);                     \
-  } while (0)
-  constexpr uint64_t LIMIT = 0x7FFFFFFFull;
-  if (total > LIMIT)
-    return fail(GN_E_CAPACITY, "quiescence: %zu leaves, a level holds < 2^31; lower GN_OPT_CHUNK_PARENTS (depth %d)", total,
-                depth);
-  Dev::Extend &X = d.ex;
-  Dev::Quiesce &Q = d.q;
-  Q_ALLOC(0, total, X.sel.ensure(total + 1));
-  Q_ALLOC(0, total, X.pos.ensure(total + 1));
-  Q_ALLOC(0, total, Q.lcnt.ensure(total));
-  Q_ALLOC(0, total, reserve_scan_u64(total + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap)); // (the scan then allocates nothing)
-  HIP_TRY(hipMemsetAsync(X.sel.p, 0, (total + 1) * sizeof(uint64_t), s));
-  HIP_TRY(launch_quiesce_select(parents, n, offsets, moves, total, d.tables.p, X.sel.p, Q.lcnt.p, ext, s));
-  HIP_TRY(exclusive_scan_u64(X.sel.p, X.pos.p, total + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap, s));
-  uint64_t m = 0;
-  HIP_TRY(hipMemcpyAsync(&m, X.pos.p + total, sizeof(m), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (!m) return GN_OK;
-  if (m > total) return fail(GN_E_HIP, "quiescence: %zu selected of %zu leaves", (size_t)m, total);
-  Q_ALLOC(0, m, X.idx.ensure(m));
-  Q_ALLOC(0, m, X.boards.ensure(m));
-  Q_ALLOC(0, m, X.sv.ensure(m));
-  Q_ALLOC(0, m, X.count.ensure(1));
-  HIP_TRY(launch_extend_boards(parents, n, offsets, moves, X.sel.p, X.pos.p, total, d.tables.p, X.idx.p, X.boards.p, X.sv.p,
-                               s));
+
+// QUIESCE values them: sv[i] = Q(selected leaf i, depth), *nodes = the positions evaluated below.
+// Level 0 are the m selected leaves; their statics are the caller's rec, through idx, and their
+// searched-move counts the selection pass's, compacted.  Level k + 1 is made from level k's boards:
+// the searched moves counted, scanned, the level's size read back, its boards written and evaluated
+// as positions by evaluate_on (whose records carry the in-check and no-legal-move bits the rule
+// needs).  Then one reduction per level, bottom-up.  A level of 2^31 nodes fails the call with
+// GN_E_CAPACITY.  Every allocation goes through alloc, those of the scans and of evaluate_on
+// included: they are reserved before the call that would make them.
+static int quiesce(gn_ctx *ctx, Dev &d, const gn_eval *rec, size_t total, size_t m, int mode, int depth,
+                   const LeafAlloc &alloc, size_t *nodes, hipStream_t s) {
+  Dev::LeafStage &X = d.leaf;
   // the levels, top-down: cnt[k] nodes at level k; top: the deepest level whose children were counted
   size_t cnt[GN_MAX_QUIESCE_DEPTH + 2] = {m};
   const gn_board *boards = X.boards.p;
-  size_t below = 0;
   int top = depth - 1;
   for (int k = 0; k < depth; ++k) {
-    Dev::Quiesce::Level &L = Q.lv[k];
-    Q_ALLOC(k, cnt[k], L.counts.ensure(cnt[k] + 1));
-    Q_ALLOC(k, cnt[k], L.offsets.ensure(cnt[k] + 1));
-    Q_ALLOC(k, cnt[k], reserve_scan_u64(cnt[k] + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap));
+    Dev::LeafStage::Level &L = X.lv[k];
+    LEAF_ALLOC(k, cnt[k], L.counts.ensure(cnt[k] + 1));
+    LEAF_ALLOC(k, cnt[k], L.offsets.ensure(cnt[k] + 1));
+    LEAF_ALLOC(k, cnt[k], reserve_scan_u64(cnt[k] + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap));
     if (k) HIP_TRY(launch_quiesce_count(boards, cnt[k], d.tables.p, L.counts.p, s));
-    else HIP_TRY(launch_quiesce_level0_counts(X.sel.p, X.pos.p, Q.lcnt.p, total, L.counts.p, s)); // (counted by the selection)
-    HIP_TRY(exclusive_scan_u64(L.counts.p, L.offsets.p, cnt[k] + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap, s));
+    else HIP_TRY(launch_quiesce_level0_counts(X.sel.p, X.pos.p, X.lcnt.p, total, L.counts.p, s)); // (counted by the selection)
     uint64_t t = 0;
-    HIP_TRY(hipMemcpyAsync(&t, L.offsets.p + cnt[k], sizeof(t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (t > LIMIT)
+    HIP_TRY(scan_total(d, L.counts.p, L.offsets.p, cnt[k], s, &t));
+    if (t > 0x7FFFFFFFull)
       return fail(GN_E_CAPACITY,
                   "quiescence: level %d holds %llu nodes, the limit is 2^31 - 1; lower GN_OPT_CHUNK_PARENTS or depth (%d)",
                   k + 1, (unsigned long long)t, depth);
@@ -1343,53 +1297,101 @@ static int quiesce_levels(gn_ctx *ctx, Dev &d, const Parent *parents, size_t n, 
       top = k;
       break;
     }
-    Dev::Quiesce::Level &N = Q.lv[k + 1];
-    Q_ALLOC(k + 1, t, N.boards.ensure(t));
-    Q_ALLOC(k + 1, t, N.rec.ensure(t));
-    if (k + 1 < depth) Q_ALLOC(k + 1, t, N.val.ensure(t));
-    Q_ALLOC(k + 1, t, Q.moves.ensure(t));
-    Q_ALLOC(k + 1, t, Q.owner.ensure(t));
+    Dev::LeafStage::Level &N = X.lv[k + 1];
+    LEAF_ALLOC(k + 1, t, N.boards.ensure(t));
+    LEAF_ALLOC(k + 1, t, N.rec.ensure(t));
+    if (k + 1 < depth) LEAF_ALLOC(k + 1, t, N.val.ensure(t));
+    LEAF_ALLOC(k + 1, t, X.moves.ensure(t));
+    LEAF_ALLOC(k + 1, t, X.owner.ensure(t));
     // (everything evaluate_on would allocate for the level: it then allocates nothing, so that no
     // allocation of the stage can fail as anything but GN_E_NOMEM)
-    Q_ALLOC(k + 1, t, reserve_eval_outputs(d.cur.eb, t, mode));
-    if (king_sorted(ctx, t)) Q_ALLOC(k + 1, t, reserve_king_sort_buffers(d, t, mode));
-    HIP_TRY(launch_quiesce_children(boards, cnt[k], d.tables.p, L.offsets.p, t, Q.moves.p, Q.owner.p, N.boards.p, s));
+    LEAF_ALLOC(k + 1, t, reserve_eval_outputs(d.cur.eb, t, mode));
+    if (king_sorted(ctx, t)) LEAF_ALLOC(k + 1, t, reserve_king_sort_buffers(d, t, mode));
+    HIP_TRY(launch_quiesce_children(boards, cnt[k], d.tables.p, L.offsets.p, t, X.moves.p, X.owner.p, N.boards.p, s));
     if (int rc = evaluate_on(ctx, d, N.boards.p, t, mode, N.rec.p, s)) return rc;
-    below += t;
+    *nodes += t;
     boards = N.boards.p;
   }
   // the reduction, bottom-up; level 0's records are the caller's, through idx
   for (int k = top; k >= 0; --k) {
     const size_t nc = cnt[k + 1];
     const bool last = k + 1 == depth || !nc; // the children are valued statically (or there are none)
-    HIP_TRY(launch_quiesce_reduce(k ? Q.lv[k].rec.p : rec, k ? nullptr : X.idx.p, cnt[k], Q.lv[k].offsets.p, nc,
-                                  nc ? Q.lv[k + 1].rec.p : nullptr, last ? nullptr : Q.lv[k + 1].val.p,
-                                  k ? Q.lv[k].val.p : X.sv.p, s));
+    HIP_TRY(launch_quiesce_reduce(k ? X.lv[k].rec.p : rec, k ? nullptr : X.idx.p, cnt[k], X.lv[k].offsets.p, nc,
+                                  nc ? X.lv[k + 1].rec.p : nullptr, last ? nullptr : X.lv[k + 1].val.p,
+                                  k ? X.lv[k].val.p : X.sv.p, s));
   }
-  HIP_TRY(hipMemsetAsync(X.count.p, 0, sizeof(unsigned long long), s));
-  HIP_TRY(launch_extend_scatter(X.idx.p, X.sv.p, m, ext, X.count.p, s));
-  unsigned long long c = 0;
-  HIP_TRY(hipMemcpyAsync(&c, X.count.p, sizeof(c), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  *searched = (size_t)c, *nodes = below;
   return GN_OK;
-#undef Q_ALLOC
 }
+
+// The leaf stage of one expansion level (include/gpu_nnue.h, gn_extend_checks_device and
+// gn_quiesce_device): ext[j] = the rule's value of leaf j where the rule values it -- CHECKS:
+// value(leaf j, 2) of the score rule where the leaf is in check with a legal move; QUIESCE:
+// Q(leaf j, depth) where the leaf is searched, that is, has a legal move and is in check or has a
+// noisy one -- and GN_NOT_EXTENDED elsewhere; *res = how many, and the positions evaluated below them.
+// Level 0: the rule's kernel selects its leaves (the quiescence's makes each leaf's board and so also
+// counts its searched moves) and writes GN_NOT_EXTENDED to all of ext; the selection is scanned, the
+// count m read back, and the selected leaves' boards, indices and GN_NOT_EXTENDED values compacted
+// (extend_boards_kernel).  The rule values them (extend_checks / quiesce); the values are scattered
+// to ext and counted.  Synchronous: every buffer is sized from a read-back count before anything is
+// queued on it, and the kernels clamp their offsets to those counts; the stream is idle on every
+// return.  d.mu held, inside a sequence on s, no expansion in flight on d.cur.
 template <class Parent, class Off>
-static int quiesce(gn_ctx *ctx, Dev &d, const Parent *parents, size_t n, const Off *offsets, const uint16_t *moves,
-                   const gn_eval *rec, size_t total, int mode, int depth, int32_t *ext, size_t *searched, size_t *nodes,
-                   hipStream_t s) {
-  *searched = *nodes = 0;
-  if (depth < 1 || depth > GN_MAX_QUIESCE_DEPTH)
-    return fail(GN_E_INVALID, "bad quiescence depth %d (1..%d)", depth, GN_MAX_QUIESCE_DEPTH);
+static int value_leaves(gn_ctx *ctx, Dev &d, const Leaves<Parent, Off> &lv, int mode, LeafRule rule, int32_t *ext,
+                        LeafCount *res, hipStream_t s) {
+  *res = LeafCount{};
+  if (int rc = check_leaf_rule(rule)) return rc;
   if (mode < GN_MODE_FULL || mode > GN_MODE_SMALL) return fail(GN_E_INVALID, "bad mode %d", mode);
   if ((mode != GN_MODE_SMALL && !d.has[BIG]) || (mode != GN_MODE_BIG && !d.has[SMALL]))
     return fail(GN_E_NONET, "mode %d needs a network that is not loaded", mode);
-  if (!total || !n) return GN_OK;
-  const int rc = quiesce_levels(ctx, d, parents, n, offsets, moves, rec, total, mode, depth, ext, searched, nodes, s);
-  if (rc) (void)hipStreamSynchronize(s); // (idle on every way out)
-  return rc;
+  if (!lv.total || !lv.n) return GN_OK;
+  struct Idle { // a failed call too leaves the stream idle
+    hipStream_t s;
+    bool ok = false;
+    ~Idle() { if (!ok) (void)hipStreamSynchronize(s); }
+  } idle{s};
+  const bool q = rule.kind == LeafRule::QUIESCE;
+  const size_t total = lv.total;
+  if (total > 0x7FFFFFFFull)
+    return q ? fail(GN_E_CAPACITY, "quiescence: %zu leaves, a level holds < 2^31; lower GN_OPT_CHUNK_PARENTS (depth %d)",
+                    total, rule.depth)
+             : fail(GN_E_INVALID, "the check extension supports < 2^31 leaves per call");
+  const LeafAlloc alloc{d, rule};
+  Dev::LeafStage &X = d.leaf;
+  LEAF_ALLOC(0, total, X.sel.ensure(total + 1));
+  LEAF_ALLOC(0, total, X.pos.ensure(total + 1));
+  if (q) {
+    LEAF_ALLOC(0, total, X.lcnt.ensure(total));
+    LEAF_ALLOC(0, total, reserve_scan_u64(total + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap)); // (the scan then allocates nothing)
+    HIP_TRY(hipMemsetAsync(X.sel.p, 0, (total + 1) * sizeof(uint64_t), s));
+    HIP_TRY(launch_quiesce_select(lv.parents, lv.n, lv.offsets, lv.moves, total, d.tables.p, X.sel.p, X.lcnt.p, ext, s));
+  } else {
+    HIP_TRY(launch_extend_select(lv.rec, total, X.sel.p, ext, s));
+  }
+  uint64_t m = 0;
+  HIP_TRY(scan_total(d, X.sel.p, X.pos.p, total, s, &m));
+  if (m > total) return fail(GN_E_HIP, "leaf stage: %zu selected of %zu leaves", (size_t)m, total);
+  size_t below = 0;
+  unsigned long long valued = 0;
+  if (m) {
+    LEAF_ALLOC(0, m, X.idx.ensure(m));
+    LEAF_ALLOC(0, m, X.boards.ensure(m));
+    LEAF_ALLOC(0, m, X.sv.ensure(m));
+    LEAF_ALLOC(0, m, X.count.ensure(1));
+    HIP_TRY(launch_extend_boards(lv.parents, lv.n, lv.offsets, lv.moves, X.sel.p, X.pos.p, total, d.tables.p, X.idx.p,
+                                 X.boards.p, X.sv.p, s));
+    if (int rc = q ? quiesce(ctx, d, lv.rec, total, m, mode, rule.depth, alloc, &below, s)
+                   : extend_checks(ctx, d, m, mode, alloc, s))
+      return rc;
+    HIP_TRY(hipMemsetAsync(X.count.p, 0, sizeof(unsigned long long), s));
+    HIP_TRY(launch_extend_scatter(X.idx.p, X.sv.p, m, ext, X.count.p, s));
+    HIP_TRY(hipMemcpyAsync(&valued, X.count.p, sizeof(valued), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  res->leaves = (size_t)valued, res->nodes = below;
+  return idle.ok = true, GN_OK;
 }
+#undef LEAF_ALLOC
+
 // ------------------------------------------------------- one level -------
 // expand_level's optional arguments.
 struct LevelOpts {
@@ -1718,25 +1720,16 @@ static double ms_since(Clock::time_point t) {
   return std::chrono::duration<double, std::milli>(Clock::now() - t).count();
 }
 
-// The check extension (extend_checks) as a stage of a host-buffer call: its time and count into the
-// device's statistics
-// leaf (LEAF_CHECKS, or a quiescence depth 1..GN_MAX_QUIESCE_DEPTH): which of the two values the
-// leaves: the quiescent calls run quiesce here instead, into their own statistics.
-constexpr int LEAF_CHECKS = -1;
+// The leaf stage (value_leaves) as a stage of a host-buffer call: its host time (the stage blocks)
+// and its counts are added to the device's statistics of the rule's kind, whatever it returns.
 template <class Parent, class Off>
-static int extend_stage(gn_ctx *ctx, Dev &d, const Parent *parents, size_t n, const Off *offsets,
-                        const uint16_t *moves, const gn_eval *rec, size_t total, int mode, int32_t *ext, hipStream_t s,
-                        int leaf) {
+static int extend_stage(gn_ctx *ctx, Dev &d, const Leaves<Parent, Off> &lv, int mode, LeafRule rule, int32_t *ext,
+                        hipStream_t s) {
   const auto t0 = Clock::now();
-  if (leaf != LEAF_CHECKS) {
-    size_t ns = 0, nn = 0;
-    const int rc = quiesce(ctx, d, parents, n, offsets, moves, rec, total, mode, leaf, ext, &ns, &nn, s);
-    d.t_quiesce += ms_since(t0), d.n_qleaves += ns, d.n_qnodes += nn;
-    return rc;
-  }
-  size_t ne = 0;
-  const int rc = extend_checks(ctx, d, parents, n, offsets, moves, rec, total, mode, ext, &ne, s);
-  d.t_extend += ms_since(t0), d.n_extended += ne;
+  LeafCount c;
+  const int rc = value_leaves(ctx, d, lv, mode, rule, ext, &c, s);
+  Dev::LeafStage::Stats &st = d.leaf.stats[rule.kind];
+  st.ms += ms_since(t0), st.leaves += c.leaves, st.nodes += c.nodes;
   return rc;
 }
 
@@ -1773,7 +1766,10 @@ static int run_shards(gn_ctx *ctx, const std::vector<size_t> &b, F &&f) {
 }
 
 static void reset_host_stats(gn_ctx *ctx) {
-  for (auto &dp : ctx->devs) dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = dp->t_keys = dp->t_extend = dp->t_quiesce = 0, dp->n_extended = dp->n_qleaves = dp->n_qnodes = 0;
+  for (auto &dp : ctx->devs) {
+    dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = dp->t_keys = 0;
+    for (auto &st : dp->leaf.stats) st = {};
+  }
 }
 
 // Chunk bounds of a shard's m parents: cut only where `starts` allows (the first parent of each
@@ -1961,10 +1957,9 @@ struct ExpandOut {
   // gn_evaluate_games_lines_history: the shard's keys (device, n_keys of them) and one gn_history per
   // parent of the shard (device; chunk c's at hist + chunks[c]); hist NULL: the plain ranking
   RankHistory history = NO_HISTORY;
-  // gn_evaluate_games_lines_extended: each chunk's children in check are extended before the
-  // ranking (extend_stage), and the chunks run one after another.  LEAF_CHECKS, or the quiescent
-  // call's depth (0: a plain call)
-  int extend = 0;
+  // gn_evaluate_games_lines_extended / _quiescent: each chunk's children are valued by the rule
+  // before the ranking (extend_stage), and the chunks run one after another
+  LeafRule leaf;
 };
 // Pass 2 of a shard (see above).  off: the shard's child offsets from pass 1.
 static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m, int mode,
@@ -1980,7 +1975,7 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
     HIP_TRY(d.co2[k].ensure(maxc));
     if (n_lines) HIP_TRY(d.ln2[k].ensure(maxp * (size_t)n_lines));
     else HIP_TRY(d.cc2[k].ensure(maxc));
-    if (o.extend) HIP_TRY(d.ext.ensure(maxc));
+    if (o.leaf.extends()) HIP_TRY(d.leaf.ext.ensure(maxc));
     HIP_TRY(d.mv2[k].ensure(maxc));
   }
   int drc[2] = {GN_OK, GN_OK};
@@ -2049,12 +2044,13 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
           // (extended: the chunks run serially, so nothing else is queued on the device while the
           // extension evaluates in the current set's and the score levels' buffers; t == 0: no entry
           // is read)
-          if (o.extend)
-            if (int r = extend_stage(ctx, d, d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, t, mode, d.ext.p, s, o.extend))
+          if (o.leaf.extends())
+            if (int r = extend_stage(ctx, d, UnpackedLeaves{d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, t},
+                                     mode, o.leaf, d.leaf.ext.p, s))
               return r;
           HIP_TRY(hipEventRecord(d.rev[0], s));
           HIP_TRY(launch_rank_children(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P, d.tables.p,
-                                       n_lines, d.ln2[k].p, h.hist ? &h : nullptr, o.extend ? d.ext.p : nullptr, s));
+                                       n_lines, d.ln2[k].p, h.hist ? &h : nullptr, o.leaf.extends() ? d.leaf.ext.p : nullptr, s));
           HIP_TRY(hipEventRecord(d.rev[1], s));
         } else {
           HIP_TRY(launch_pack_children(d.co2[k].p, t, d.cc2[k].p, s));
@@ -2072,7 +2068,7 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
         drain_chunk(k, pa, mp, t, cb);
         return GN_OK;
       },
-      o.extend != 0);
+      o.leaf.extends());
   const auto tt = Clock::now();
   for (int k = 0; k < 2; ++k) {
     const int r = join(k);
@@ -2280,21 +2276,30 @@ struct GameShard {
   gn_eval *records_of(gn_eval *position_out) { return in_place ? position_out + p0 : res.data(); }
 };
 
-// A games call: gn_evaluate_games' arguments, and what its phases hand on.
-struct GamesCall {
-  gn_ctx *ctx;
-  const gn_game *games;
-  size_t n_games;
-  int mode, with_children, n_lines;
-  bool history; // gn_evaluate_games_lines_history / _lines2_history: the lines with the game-history draws
-  uint32_t *position_offsets, *child_offsets;
-  int32_t *game_status;
-  gn_eval *position_out;
-  size_t position_cap, child_cap;
-  uint16_t *child_moves;
-  gn_child *child_out;
-  gn_line *lines;
-  gn_line2 *lines2;              // gn_evaluate_games_lines2: two-ply lines instead (lines NULL, no children)
+// A games call's arguments: each call names what it asks for, and what it does not name stays off.
+struct GamesArgs {
+  gn_ctx *ctx = nullptr;
+  const gn_game *games = nullptr;
+  size_t n_games = 0;
+  int mode = GN_MODE_FULL;
+  uint32_t *position_offsets = nullptr;
+  int32_t *game_status = nullptr;
+  gn_eval *position_out = nullptr;
+  size_t position_cap = 0, child_cap = 0;
+  int with_children = 0; // gn_evaluate_games: the children too, into the three arrays below
+  uint32_t *child_offsets = nullptr;
+  uint16_t *child_moves = nullptr;
+  gn_child *child_out = nullptr;
+  int n_lines = 0;            // the lines calls: n_lines lines per position, no child reaches the host
+  gn_line *lines = nullptr;   // ... one-ply (with_children 1: the children ranked on the device)
+  gn_line2 *lines2 = nullptr; // ... or two-ply (with_children 0)
+  bool history = false;       // ... with the game-history draws
+  LeafRule leaf;              // ... their leaves valued by this rule (extend_stage)
+};
+
+// A games call: its arguments, and what its phases hand on.
+struct GamesCall : GamesArgs {
+  explicit GamesCall(const GamesArgs &a) : GamesArgs(a) {}
   std::vector<GamePrep> prep;
   std::vector<size_t> bounds;    // the devices' game ranges
   std::vector<GameShard> shards; // one per device
@@ -2302,8 +2307,6 @@ struct GamesCall {
   uint64_t total = 0;            // positions
   bool all_in_place = true;
   std::string last_err;          // the last failed game's message (gn_last_error after GN_OK)
-  int extend = 0;                // the _extended calls: LEAF_CHECKS, the lines' leaves in check take their check
-                                 // extension; the _quiescent calls: their depth (extend_stage)
 };
 
 // host: root FENs parsed, UCI moves tokenized (the wire form, AcquireResponseBody.moves); games
@@ -2530,7 +2533,7 @@ static int games_expand(const GamesCall &c, GameShard &sh, Dev &d) {
   ExpandOut o = c.n_lines ? ExpandOut{rec, nullptr, nullptr, c.n_lines, ln}
                           : ExpandOut{rec, c.child_moves + sh.child_base, c.child_out + sh.child_base};
   if (c.history) o.history = RankHistory{d.rkeys.p, d.n_rkeys, d.hist.p};
-  o.extend = c.extend;
+  o.leaf = c.leaf;
   return expand_pipelined(c.ctx, d, sh.parents_of(d), sh.m, c.mode, sh.off,
                           chunk_plan(sh.m, sh.starts, c.ctx->chunk_parents), o);
 }
@@ -2563,11 +2566,12 @@ static void games_scatter(const GamesCall &c) {
 // gn_evaluate_lines2)
 static int games_lines2(const GamesCall &c, GameShard &sh, Dev &d);
 
-static int evaluate_games(GamesCall c) {
-  if (!slot(c.ctx, 0)) return fail(GN_E_INVALID, "bad context");
-  if (c.n_games && (!c.games || !c.position_offsets || !c.game_status)) return fail(GN_E_INVALID, "NULL argument");
-  if (c.with_children && !c.n_lines && !c.child_offsets) return fail(GN_E_INVALID, "child_offsets is NULL");
-  if (c.mode < GN_MODE_FULL || c.mode > GN_MODE_SMALL) return fail(GN_E_INVALID, "bad mode %d", c.mode);
+static int evaluate_games(const GamesArgs &a) {
+  if (!slot(a.ctx, 0)) return fail(GN_E_INVALID, "bad context");
+  if (a.n_games && (!a.games || !a.position_offsets || !a.game_status)) return fail(GN_E_INVALID, "NULL argument");
+  if (a.with_children && !a.n_lines && !a.child_offsets) return fail(GN_E_INVALID, "child_offsets is NULL");
+  if (a.mode < GN_MODE_FULL || a.mode > GN_MODE_SMALL) return fail(GN_E_INVALID, "bad mode %d", a.mode);
+  GamesCall c(a);
   return guarded([&]() -> int {
     const auto T0 = Clock::now();
     gn_ctx *const ctx = c.ctx;
@@ -2596,6 +2600,22 @@ static int evaluate_games(GamesCall c) {
   });
 }
 
+// The games calls with lines: one-ply (gn_line: the children ranked on the device) or two-ply
+template <class Line>
+static int evaluate_games_lines(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines, bool history,
+                                LeafRule leaf, uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
+                                size_t position_cap, Line *lines) {
+  if (int rc = check_leaf_rule(leaf)) return rc;
+  if (int rc = check_n_lines(n_lines)) return rc;
+  GamesArgs a;
+  a.ctx = ctx, a.games = games, a.n_games = n_games, a.mode = mode, a.position_offsets = position_offsets;
+  a.game_status = game_status, a.position_out = position_out, a.position_cap = position_cap;
+  a.n_lines = n_lines, a.history = history, a.leaf = leaf;
+  if constexpr (std::is_same<Line, gn_line>::value) a.with_children = 1, a.lines = lines;
+  else a.lines2 = lines;
+  return evaluate_games(a);
+}
+
 // ============================================================ C-ABI ========
 extern "C" {
 
@@ -2618,84 +2638,68 @@ int gn_replay_game(const gn_game *game, gn_board *positions, uint8_t *skipped, u
 int gn_evaluate_games(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int with_children,
                       uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out, size_t position_cap,
                       uint32_t *child_offsets, uint16_t *child_moves, gn_child *child_out, size_t child_cap) {
-  return evaluate_games({ctx, games, n_games, mode, with_children, 0, false, position_offsets, child_offsets, game_status,
-                         position_out, position_cap, child_cap, child_moves, child_out, nullptr});
+  GamesArgs a;
+  a.ctx = ctx, a.games = games, a.n_games = n_games, a.mode = mode, a.position_offsets = position_offsets;
+  a.game_status = game_status, a.position_out = position_out, a.position_cap = position_cap;
+  a.with_children = with_children, a.child_offsets = child_offsets, a.child_moves = child_moves;
+  a.child_out = child_out, a.child_cap = child_cap;
+  return evaluate_games(a);
 }
 
 int gn_evaluate_games_lines(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                             uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                             size_t position_cap, gn_line *lines) {
-  if (int rc = check_n_lines(n_lines)) return rc;
-  return evaluate_games({ctx, games, n_games, mode, 1, n_lines, false, position_offsets, nullptr, game_status,
-                         position_out, position_cap, 0, nullptr, nullptr, lines});
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, false, LeafRule{}, position_offsets, game_status,
+                              position_out, position_cap, lines);
 }
 
 int gn_evaluate_games_lines_history(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                                     uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                                     size_t position_cap, gn_line *lines) {
-  if (int rc = check_n_lines(n_lines)) return rc;
-  return evaluate_games({ctx, games, n_games, mode, 1, n_lines, true, position_offsets, nullptr, game_status,
-                         position_out, position_cap, 0, nullptr, nullptr, lines});
-}
-
-static int evaluate_games_lines2(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines, bool history,
-                                 uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
-                                 size_t position_cap, gn_line2 *lines, int extend = 0) {
-  if (int rc = check_n_lines(n_lines)) return rc;
-  GamesCall c{ctx, games, n_games, mode, 0, n_lines, history, position_offsets, nullptr, game_status,
-              position_out, position_cap, 0, nullptr, nullptr, nullptr, lines};
-  c.extend = extend;
-  return evaluate_games(std::move(c));
-}
-
-int gn_evaluate_games_lines2_extended(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
-                                      int history, uint32_t *position_offsets, int32_t *game_status,
-                                      gn_eval *position_out, size_t position_cap, gn_line2 *lines) {
-  return evaluate_games_lines2(ctx, games, n_games, mode, n_lines, history != 0, position_offsets, game_status,
-                               position_out, position_cap, lines, LEAF_CHECKS);
-}
-
-int gn_evaluate_games_lines2_quiescent(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
-                                       int history, int depth, uint32_t *position_offsets, int32_t *game_status,
-                                       gn_eval *position_out, size_t position_cap, gn_line2 *lines) {
-  if (int rc = check_quiesce_depth(depth)) return rc;
-  return evaluate_games_lines2(ctx, games, n_games, mode, n_lines, history != 0, position_offsets, game_status,
-                               position_out, position_cap, lines, depth);
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, true, LeafRule{}, position_offsets, game_status,
+                              position_out, position_cap, lines);
 }
 
 int gn_evaluate_games_lines_extended(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                                      int history, uint32_t *position_offsets, int32_t *game_status,
                                      gn_eval *position_out, size_t position_cap, gn_line *lines) {
-  if (int rc = check_n_lines(n_lines)) return rc;
-  GamesCall c{ctx, games, n_games, mode, 1, n_lines, history != 0, position_offsets, nullptr, game_status,
-              position_out, position_cap, 0, nullptr, nullptr, lines};
-  c.extend = LEAF_CHECKS;
-  return evaluate_games(std::move(c));
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::checks(), position_offsets,
+                              game_status, position_out, position_cap, lines);
 }
 
 int gn_evaluate_games_lines_quiescent(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                                       int history, int depth, uint32_t *position_offsets, int32_t *game_status,
                                       gn_eval *position_out, size_t position_cap, gn_line *lines) {
-  if (int rc = check_n_lines(n_lines)) return rc;
-  if (int rc = check_quiesce_depth(depth)) return rc;
-  GamesCall c{ctx, games, n_games, mode, 1, n_lines, history != 0, position_offsets, nullptr, game_status,
-              position_out, position_cap, 0, nullptr, nullptr, lines};
-  c.extend = depth;
-  return evaluate_games(std::move(c));
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(depth), position_offsets,
+                              game_status, position_out, position_cap, lines);
 }
 
 int gn_evaluate_games_lines2(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                              uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                              size_t position_cap, gn_line2 *lines) {
-  return evaluate_games_lines2(ctx, games, n_games, mode, n_lines, false, position_offsets, game_status, position_out,
-                               position_cap, lines);
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, false, LeafRule{}, position_offsets, game_status,
+                              position_out, position_cap, lines);
 }
 
 int gn_evaluate_games_lines2_history(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                                      uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                                      size_t position_cap, gn_line2 *lines) {
-  return evaluate_games_lines2(ctx, games, n_games, mode, n_lines, true, position_offsets, game_status, position_out,
-                               position_cap, lines);
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, true, LeafRule{}, position_offsets, game_status,
+                              position_out, position_cap, lines);
+}
+
+int gn_evaluate_games_lines2_extended(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                      int history, uint32_t *position_offsets, int32_t *game_status,
+                                      gn_eval *position_out, size_t position_cap, gn_line2 *lines) {
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::checks(), position_offsets,
+                              game_status, position_out, position_cap, lines);
+}
+
+int gn_evaluate_games_lines2_quiescent(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                       int history, int depth, uint32_t *position_offsets, int32_t *game_status,
+                                       gn_eval *position_out, size_t position_cap, gn_line2 *lines) {
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(depth), position_offsets,
+                              game_status, position_out, position_cap, lines);
 }
 
 int gn_partition(const uint32_t *weights, size_t n_items, int n_shards, size_t *bounds) {
@@ -3113,7 +3117,7 @@ int gn_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, si
   return expand_level(ctx, *d, d_parents, n, mode, d_parent_out, d_offsets, d_moves, d_child_out, cap, total, s, o);
 }
 
-// What the four gn_rank_*_device calls check before they take the device, in this order: the slot,
+// What the gn_rank_*_device calls check before they take the device, in this order: the slot,
 // n_lines, the buffers every parent needs (the child and grandchild buffers may be NULL when no
 // parent has a child: they are then never read) and, for the history forms (h), the entries and
 // the keys.  d: the slot's device.
@@ -3127,16 +3131,26 @@ static int rank_call_args(gn_ctx *ctx, int device_slot, size_t n, const gn_board
   return GN_OK;
 }
 
+// gn_rank_children_device and its forms: with a history, the game-history draws (the extended forms'
+// d_hist NULL: no history at all); with d_ext, the leaves' values from the leaf stage.
+static int rank_children_call(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
+                              const uint16_t *d_moves, const gn_eval *d_child_out, const std::optional<RankHistory> &history,
+                              const int32_t *d_ext, int n_lines, gn_line *d_lines, void *stream) {
+  const RankHistory *h = history ? &*history : nullptr;
+  Dev *d;
+  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, h, d)) return rc;
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables.p, n_lines, d_lines, h,
+                               d_ext, call.s));
+  return GN_OK;
+}
+
 int gn_rank_children_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
                             const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out, int n_lines,
                             gn_line *d_lines, void *stream) {
-  Dev *d;
-  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, nullptr, d)) return rc;
-  DevCall call(*d, stream);
-  if (call.rc) return call.rc;
-  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables.p, n_lines, d_lines, nullptr,
-                               nullptr, call.s));
-  return GN_OK;
+  return rank_children_call(ctx, device_slot, d_parents, n, d_offsets, d_moves, d_child_out, std::nullopt, nullptr,
+                            n_lines, d_lines, stream);
 }
 
 int gn_position_keys_device(gn_ctx *ctx, int device_slot, const gn_board *d_boards, size_t n, uint64_t *d_keys,
@@ -3154,77 +3168,51 @@ int gn_rank_children_history_device(gn_ctx *ctx, int device_slot, const gn_board
                                     const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out,
                                     const uint64_t *d_keys, size_t n_keys, const gn_history *d_hist, int n_lines,
                                     gn_line *d_lines, void *stream) {
-  const RankHistory h = {d_keys, n_keys, d_hist};
-  Dev *d;
-  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, &h, d)) return rc;
-  DevCall call(*d, stream);
-  if (call.rc) return call.rc;
-  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables.p, n_lines, d_lines, &h,
-                               nullptr, call.s));
-  return GN_OK;
-}
-
-int gn_extend_checks_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
-                            const uint16_t *d_moves, const gn_eval *d_rec, size_t total, int mode, int32_t *d_ext,
-                            size_t *extended, void *stream) {
-  Dev *d = slot(ctx, device_slot);
-  if (!d || !extended) return fail(GN_E_INVALID, "bad argument");
-  *extended = 0;
-  if (total && (!n || !d_parents || !d_offsets || !d_moves || !d_rec || !d_ext)) return fail(GN_E_INVALID, "NULL buffer");
-  DevCall call(*d, stream);
-  if (call.rc) return call.rc;
-  const int rc = extend_checks(ctx, *d, d_parents, n, d_offsets, d_moves, d_rec, total, mode, d_ext, extended, call.s);
-  if (rc) return rc;
-  HIP_TRY(call.sg->finish()); // blocking (gpu_nnue.h): d_ext is written when the call returns
-  return GN_OK;
-}
-
-int gn_quiesce_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
-                      const uint16_t *d_moves, const gn_eval *d_rec, size_t total, int mode, int depth, int32_t *d_ext,
-                      size_t *searched, size_t *nodes, void *stream) {
-  Dev *d = slot(ctx, device_slot);
-  if (!d || !searched || !nodes) return fail(GN_E_INVALID, "bad argument");
-  *searched = *nodes = 0;
-  if (total && (!n || !d_parents || !d_offsets || !d_moves || !d_rec || !d_ext)) return fail(GN_E_INVALID, "NULL buffer");
-  DevCall call(*d, stream);
-  if (call.rc) return call.rc;
-  const int rc = quiesce(ctx, *d, d_parents, n, d_offsets, d_moves, d_rec, total, mode, depth, d_ext, searched, nodes,
-                         call.s);
-  if (rc) return rc;
-  HIP_TRY(call.sg->finish()); // blocking (gpu_nnue.h): d_ext is written when the call returns
-  return GN_OK;
+  return rank_children_call(ctx, device_slot, d_parents, n, d_offsets, d_moves, d_child_out,
+                            RankHistory{d_keys, n_keys, d_hist}, nullptr, n_lines, d_lines, stream);
 }
 
 int gn_rank_children_extended_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
                                      const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out,
                                      const uint64_t *d_keys, size_t n_keys, const gn_history *d_hist,
                                      const int32_t *d_ext, int n_lines, gn_line *d_lines, void *stream) {
-  const RankHistory h = {d_keys, n_keys, d_hist};
-  Dev *d;
-  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, d_hist ? &h : nullptr, d))
-    return rc;
+  return rank_children_call(ctx, device_slot, d_parents, n, d_offsets, d_moves, d_child_out,
+                            d_hist ? std::optional<RankHistory>({d_keys, n_keys, d_hist}) : std::nullopt, d_ext, n_lines,
+                            d_lines, stream);
+}
+
+// gn_extend_checks_device / gn_quiesce_device: the leaf stage on a caller's buffers.  *leaves = the
+// leaves valued, *nodes (QUIESCE alone; else NULL) = the positions evaluated below them.
+static int value_leaves_call(gn_ctx *ctx, int device_slot, const PackedLeaves &lv, int mode, LeafRule rule, int32_t *d_ext,
+                             size_t *leaves, size_t *nodes, void *stream) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d || !leaves || (rule.kind == LeafRule::QUIESCE && !nodes)) return fail(GN_E_INVALID, "bad argument");
+  *leaves = 0;
+  if (nodes) *nodes = 0;
+  if (lv.total && (!lv.n || !lv.parents || !lv.offsets || !lv.moves || !lv.rec || !d_ext))
+    return fail(GN_E_INVALID, "NULL buffer");
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
-  HIP_TRY(launch_rank_children(d_parents, n, d_offsets, d_moves, d_child_out, ctx->P, d->tables.p, n_lines, d_lines,
-                               d_hist ? &h : nullptr, d_ext, call.s));
+  LeafCount c;
+  if (int rc = value_leaves(ctx, *d, lv, mode, rule, d_ext, &c, call.s)) return rc;
+  *leaves = c.leaves;
+  if (nodes) *nodes = c.nodes;
+  HIP_TRY(call.sg->finish()); // blocking (gpu_nnue.h): d_ext is written when the call returns
   return GN_OK;
 }
 
-int gn_rank_lines2_extended_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
-                                   const uint32_t *d_offsets, const gn_board *d_children, const gn_eval *d_child_out,
-                                   const uint16_t *d_moves, const uint32_t *d_goffsets, const uint16_t *d_gmoves,
-                                   const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
-                                   const gn_history *d_hist, const int32_t *d_gext, int n_lines, gn_line2 *d_lines,
-                                   void *stream) {
-  const RankHistory h = {d_keys, n_keys, d_hist};
-  Dev *d;
-  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, d_hist ? &h : nullptr, d))
-    return rc;
-  DevCall call(*d, stream);
-  if (call.rc) return call.rc;
-  HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
-                             ctx->P, d->tables.p, n_lines, d_lines, d_hist ? &h : nullptr, d_gext, call.s));
-  return GN_OK;
+int gn_extend_checks_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
+                            const uint16_t *d_moves, const gn_eval *d_rec, size_t total, int mode, int32_t *d_ext,
+                            size_t *extended, void *stream) {
+  return value_leaves_call(ctx, device_slot, PackedLeaves{d_parents, n, d_offsets, d_moves, d_rec, total}, mode,
+                           LeafRule::checks(), d_ext, extended, nullptr, stream);
+}
+
+int gn_quiesce_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
+                      const uint16_t *d_moves, const gn_eval *d_rec, size_t total, int mode, int depth, int32_t *d_ext,
+                      size_t *searched, size_t *nodes, void *stream) {
+  return value_leaves_call(ctx, device_slot, PackedLeaves{d_parents, n, d_offsets, d_moves, d_rec, total}, mode,
+                           LeafRule::quiesce(depth), d_ext, searched, nodes, stream);
 }
 
 // Depth 2: the children of gn_expand_device's children.  Level 2 is
@@ -3309,17 +3297,28 @@ int gn_expand2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, s
                     Expand2Grand{d_goffsets, d_gmoves, d_grand_out, gcap}, total, gtotal, call.s);
 }
 
+// gn_rank_lines2_device and its forms, as rank_children_call.
+static int rank_lines2_call(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
+                            const gn_board *d_children, const gn_eval *d_child_out, const uint16_t *d_moves,
+                            const uint32_t *d_goffsets, const uint16_t *d_gmoves, const gn_eval *d_grand_out,
+                            const std::optional<RankHistory> &history, const int32_t *d_gext, int n_lines,
+                            gn_line2 *d_lines, void *stream) {
+  const RankHistory *h = history ? &*history : nullptr;
+  Dev *d;
+  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, h, d)) return rc;
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
+                             ctx->P, d->tables.p, n_lines, d_lines, h, d_gext, call.s));
+  return GN_OK;
+}
+
 int gn_rank_lines2_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
                           const gn_board *d_children, const gn_eval *d_child_out, const uint16_t *d_moves,
                           const uint32_t *d_goffsets, const uint16_t *d_gmoves, const gn_eval *d_grand_out, int n_lines,
                           gn_line2 *d_lines, void *stream) {
-  Dev *d;
-  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, nullptr, d)) return rc;
-  DevCall call(*d, stream);
-  if (call.rc) return call.rc;
-  HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
-                             ctx->P, d->tables.p, n_lines, d_lines, nullptr, nullptr, call.s));
-  return GN_OK;
+  return rank_lines2_call(ctx, device_slot, d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets,
+                          d_gmoves, d_grand_out, std::nullopt, nullptr, n_lines, d_lines, stream);
 }
 
 int gn_rank_lines2_history_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
@@ -3327,14 +3326,19 @@ int gn_rank_lines2_history_device(gn_ctx *ctx, int device_slot, const gn_board *
                                   const uint16_t *d_moves, const uint32_t *d_goffsets, const uint16_t *d_gmoves,
                                   const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
                                   const gn_history *d_hist, int n_lines, gn_line2 *d_lines, void *stream) {
-  const RankHistory h = {d_keys, n_keys, d_hist};
-  Dev *d;
-  if (int rc = rank_call_args(ctx, device_slot, n, d_parents, d_offsets, n_lines, d_lines, &h, d)) return rc;
-  DevCall call(*d, stream);
-  if (call.rc) return call.rc;
-  HIP_TRY(launch_rank_lines2(d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets, d_gmoves, d_grand_out,
-                             ctx->P, d->tables.p, n_lines, d_lines, &h, nullptr, call.s));
-  return GN_OK;
+  return rank_lines2_call(ctx, device_slot, d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets,
+                          d_gmoves, d_grand_out, RankHistory{d_keys, n_keys, d_hist}, nullptr, n_lines, d_lines, stream);
+}
+
+int gn_rank_lines2_extended_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                   const uint32_t *d_offsets, const gn_board *d_children, const gn_eval *d_child_out,
+                                   const uint16_t *d_moves, const uint32_t *d_goffsets, const uint16_t *d_gmoves,
+                                   const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
+                                   const gn_history *d_hist, const int32_t *d_gext, int n_lines, gn_line2 *d_lines,
+                                   void *stream) {
+  return rank_lines2_call(ctx, device_slot, d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets,
+                          d_gmoves, d_grand_out, d_hist ? std::optional<RankHistory>({d_keys, n_keys, d_hist}) : std::nullopt,
+                          d_gext, n_lines, d_lines, stream);
 }
 
 int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, int mode, int iters,
@@ -3589,29 +3593,20 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
     *value = (int64_t)(m * 1e6);
     return GN_OK;
   }
-  case GN_STAT_EXTEND_NS: { // the last host-buffer call's check extension, the slowest device
-    double m = 0;
-    for (auto &dp : ctx->devs) m = std::max(m, dp->t_extend);
-    *value = (int64_t)(m * 1e6);
-    return GN_OK;
-  }
-  case GN_STAT_QUIESCE_NS: { // the last host-buffer call's quiescence, the slowest device
-    double m = 0;
-    for (auto &dp : ctx->devs) m = std::max(m, dp->t_quiesce);
-    *value = (int64_t)(m * 1e6);
-    return GN_OK;
-  }
-  case GN_STAT_QUIESCE_LEAVES:  // ... its searched leaves
-  case GN_STAT_QUIESCE_NODES: { // ... and the nodes it evaluated, summed over the devices
-    int64_t sum = 0;
-    for (auto &dp : ctx->devs) sum += (int64_t)(option == GN_STAT_QUIESCE_LEAVES ? dp->n_qleaves : dp->n_qnodes);
-    *value = sum;
-    return GN_OK;
-  }
-  case GN_STAT_EXTENDED_LEAVES: { // ... and its extended leaves, summed over the devices
-    int64_t sum = 0;
-    for (auto &dp : ctx->devs) sum += (int64_t)dp->n_extended;
-    *value = sum;
+  case GN_STAT_EXTEND_NS: // the last host-buffer call's leaf stage, by the rule it ran: its time, the
+  case GN_STAT_QUIESCE_NS: // slowest device; the leaves it valued and the nodes it evaluated below
+  case GN_STAT_EXTENDED_LEAVES: // them, summed over the devices
+  case GN_STAT_QUIESCE_LEAVES:
+  case GN_STAT_QUIESCE_NODES: {
+    const bool checks = option == GN_STAT_EXTEND_NS || option == GN_STAT_EXTENDED_LEAVES;
+    double ms = 0;
+    uint64_t leaves = 0, nodes = 0;
+    for (auto &dp : ctx->devs) {
+      const Dev::LeafStage::Stats &st = dp->leaf.stats[checks ? LeafRule::CHECKS : LeafRule::QUIESCE];
+      ms = std::max(ms, st.ms), leaves += st.leaves, nodes += st.nodes;
+    }
+    const bool time = option == GN_STAT_EXTEND_NS || option == GN_STAT_QUIESCE_NS;
+    *value = time ? (int64_t)(ms * 1e6) : (int64_t)(option == GN_STAT_QUIESCE_NODES ? nodes : leaves);
     return GN_OK;
   }
   case GN_STAT_ZERO_ROW_ENTRIES: // ... and its entries on the zero row summed
@@ -3654,11 +3649,10 @@ int gn_expand_and_evaluate(gn_ctx *ctx, const char *const *parent_fens, size_t n
 // keys and its parents' gn_history entries (hist NULL: the plain one) -- and one download of the chunk's parent records and
 // lines into out / lines (the shard's first parent's).  The chunks need no cut at game starts: the
 // keys are the whole shard's.
-// extend: the grandchildren in check are extended after the expansion (extend_stage; the children
-// as parents, the library's own boards), and the ranking takes their values; LEAF_CHECKS, or the
-// quiescent calls' depth (0: a plain call).
+// leaf: a rule that extends values the grandchildren after the expansion (extend_stage; the children
+// as parents, the library's own boards), and the ranking takes their values.
 static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m, int mode, int K, gn_eval *out,
-                         gn_line2 *lines, const RankHistory &history, int extend) {
+                         gn_line2 *lines, const RankHistory &history, LeafRule leaf) {
   hipStream_t s = d.stream;
   Dev::Lines2 &x = d.l2;
   // 1,024 parents are ~1 M grandchildren: a few hundred MB of records, boards and partial sums
@@ -3687,13 +3681,14 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
                         &size_grand);
     if (rc) return rc;
     const RankHistory h = {history.keys, history.n_keys, history.hist ? history.hist + a : nullptr};
-    if (extend) { // (t == 0 or g == 0: nothing is read)
+    if (leaf.extends()) { // (t == 0 or g == 0: nothing is read)
       HIP_TRY(x.gext.ensure(std::max<size_t>(g, 1)));
-      if ((rc = extend_stage(ctx, d, x.ch.p, t, x.goff.p, x.gmv.p, x.gco.p, g, mode, x.gext.p, s, extend)) != GN_OK) return rc;
+      rc = extend_stage(ctx, d, PackedLeaves{x.ch.p, t, x.goff.p, x.gmv.p, x.gco.p, g}, mode, leaf, x.gext.p, s);
+      if (rc) return rc;
     }
     HIP_TRY(hipEventRecord(d.rev[0], s));
     HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables.p, K,
-                               x.ln.p, h.hist ? &h : nullptr, extend ? x.gext.p : nullptr, s));
+                               x.ln.p, h.hist ? &h : nullptr, leaf.extends() ? x.gext.p : nullptr, s));
     HIP_TRY(hipEventRecord(d.rev[1], s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0;
@@ -3711,7 +3706,7 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
 // gn_evaluate_lines2: the boards sharded equally over the devices, each shard uploaded and run
 // through lines2_chunks
 static int lines2_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int mode, int K, gn_eval *out,
-                              gn_line2 *lines, int extend) {
+                              gn_line2 *lines, LeafRule leaf) {
   const size_t nd = ctx->devs.size();
   std::vector<size_t> b(nd + 1);
   partition(nullptr, n, (int)nd, b.data());
@@ -3722,7 +3717,7 @@ static int lines2_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int
     HIP_TRY(hipMemcpyAsync(d.par.p, boards + lo, (hi - lo) * sizeof(gn_board), hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipStreamSynchronize(d.stream));
     d.t_upload += ms_since(t0);
-    return lines2_chunks(ctx, d, d.par.p, hi - lo, mode, K, out + lo, lines + lo * (size_t)K, NO_HISTORY, extend);
+    return lines2_chunks(ctx, d, d.par.p, hi - lo, mode, K, out + lo, lines + lo * (size_t)K, NO_HISTORY, leaf);
   });
 }
 
@@ -3733,34 +3728,35 @@ static int games_lines2(const GamesCall &c, GameShard &sh, Dev &d) {
   if (rc) return rc;
   gn_line2 *const ln = sh.in_place ? c.lines2 + sh.p0 * (size_t)c.n_lines : sh.l2res.data();
   return lines2_chunks(c.ctx, d, sh.parents_of(d), sh.m, c.mode, c.n_lines, sh.records_of(c.position_out), ln,
-                       c.history ? RankHistory{d.rkeys.p, d.n_rkeys, d.hist.p} : NO_HISTORY, c.extend);
+                       c.history ? RankHistory{d.rkeys.p, d.n_rkeys, d.hist.p} : NO_HISTORY, c.leaf);
 }
 
-static int evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,
-                           gn_line2 *lines, int extend) {
+// The FEN lines2 calls
+static int evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, LeafRule leaf,
+                           gn_eval *out, gn_line2 *lines) {
+  if (int rc = check_leaf_rule(leaf)) return rc;
   if (!slot(ctx, 0)) return fail(GN_E_INVALID, "bad context");
   if (int rc = check_n_lines(n_lines)) return rc;
   if (n && (!fens || !out || !lines)) return fail(GN_E_INVALID, "NULL argument");
   if (!n) return GN_OK;
   return on_packed_fens(ctx, fens, n, [&](const gn_board *boards) -> int {
-    return lines2_boards_host(ctx, boards, n, mode, n_lines, out, lines, extend);
+    return lines2_boards_host(ctx, boards, n, mode, n_lines, out, lines, leaf);
   });
 }
 
 int gn_evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,
                        gn_line2 *lines) {
-  return evaluate_lines2(ctx, fens, n, mode, n_lines, out, lines, 0);
+  return evaluate_lines2(ctx, fens, n, mode, n_lines, LeafRule{}, out, lines);
 }
 
 int gn_evaluate_lines2_extended(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, gn_eval *out,
                                 gn_line2 *lines) {
-  return evaluate_lines2(ctx, fens, n, mode, n_lines, out, lines, LEAF_CHECKS);
+  return evaluate_lines2(ctx, fens, n, mode, n_lines, LeafRule::checks(), out, lines);
 }
 
 int gn_evaluate_lines2_quiescent(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, int depth,
                                  gn_eval *out, gn_line2 *lines) {
-  if (int rc = check_quiesce_depth(depth)) return rc;
-  return evaluate_lines2(ctx, fens, n, mode, n_lines, out, lines, depth);
+  return evaluate_lines2(ctx, fens, n, mode, n_lines, LeafRule::quiesce(depth), out, lines);
 }
 
 int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {
