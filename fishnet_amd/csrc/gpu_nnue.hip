@@ -261,6 +261,7 @@ struct LeafRule {
 };
 struct LeafCount { // one run of the leaf stage: the leaves it valued, the positions evaluated below them
   size_t leaves = 0, nodes = 0;
+  float pv_ms = 0; // with a tail: quiesce_walk_kernel's time
 };
 
 // ---- the drop-in's small batches ------------------------------------
@@ -401,6 +402,8 @@ struct Dev {
   DevBuf<gn_line> ln2[2];  // or ranked: the chunk's lines (gn_evaluate_games_lines)
   Event rev[2]; // around a chunk's rank_children_kernel (GN_STAT_RANK_NS)
   DevBuf<uint16_t> mv2[2];
+  DevBuf<gn_pv> pv2[2]; // the _pv calls: the chunk's PVs, downloaded with its lines
+  Event pev[4];         // around quiesce_walk_kernel and around a chunk's PV assembly (GN_STAT_PV_NS)
   // gn_evaluate_lines2: one chunk's depth-2 expansion (gn_expand2_device's outputs, library-owned
   // and grown to the chunk's exact counts) and its lines
   struct Lines2 {
@@ -410,12 +413,16 @@ struct Dev {
     DevBuf<uint16_t> mv, gmv;
     DevBuf<gn_line2> ln;
     DevBuf<int32_t> gext; // a rule that extends: the grandchildren's values from the leaf stage
+    DevBuf<uint16_t> gtail; // the _pv calls: the grandchildren's tails from the leaf stage ...
+    DevBuf<gn_pv> pv;       // ... and the chunk's PVs
   } l2;
   // the leaf stage of one expansion level (value_leaves).  The selected leaves (level 0): the
   // selection and its scan, their indices, boards and values, the count of valued ones; rec: the
   // check extension's own records of them; ext: the one-ply games calls' per-chunk leaf values.
   // The quiescence's levels: lv[k] holds level k's searched-move counts and their scan and, for
-  // k >= 1, its boards, position records and values; moves / owner: the level being made
+  // k >= 1, its boards, position records and values; moves / owner: the level being made.  With a
+  // tail requested (the _pv calls) each level k >= 1 keeps its own moves and each reduced level its
+  // chosen children (best), and tail holds the one-ply games calls' per-chunk tails.
   struct LeafStage {
     DevBuf<uint64_t> sel, pos;
     DevBuf<uint32_t> idx;
@@ -429,12 +436,16 @@ struct Dev {
       DevBuf<gn_eval> rec;
       DevBuf<int32_t> val;
       DevBuf<uint64_t> counts, offsets;
+      DevBuf<uint16_t> moves;
+      DevBuf<uint32_t> best;
     } lv[GN_MAX_QUIESCE_DEPTH + 1];
+    DevBuf<uint16_t> tail;
     DevBuf<uint16_t> moves;
     DevBuf<uint32_t> owner;
     DevBuf<uint32_t> lcnt; // every leaf's searched moves, from the quiescence's selection pass
     void release() { // (a quiescent call's failed allocation: the levels, and what of level 0 grows with the leaves)
       for (Level &l : lv) l.boards.release(), l.rec.release(), l.val.release(), l.counts.release(), l.offsets.release();
+      for (Level &l : lv) l.moves.release(), l.best.release();
       moves.release(), owner.release(), lcnt.release();
       sel.release(), pos.release(), idx.release(), boards.release(), rec.release(), sv.release();
     }
@@ -458,6 +469,7 @@ struct Dev {
   double t_keys = 0; // position_keys_kernel in that call (GN_STAT_KEYS_NS), ms
   // stage times of the last host-buffer call on this device (GN_STAT_HOST_*), ms
   double t_upload = 0, t_replay = 0, t_compute = 0, t_download = 0, t_tail = 0, t_rank = 0, t_rank2 = 0;
+  double t_pv = 0; // the PV kernels in the last _pv call (GN_STAT_PV_NS), ms
   // the drop-in's small-batch graphs (FastBatch): two per size class (128 << k positions) and mode,
   // so that a second call's launch queues on the stream behind a first one in flight
   std::unique_ptr<FastBatch> fast[6][3][2];
@@ -703,6 +715,7 @@ static int create(const uint8_t *big, size_t big_len, const uint8_t *small, size
     for (Event *e : {&d.done, &d.ev_streamed, &d.ev_planned, &d.cev[0], &d.cev[1], &d.cur.scored, &d.alt.scored})
       HIP_TRY(hipEventCreateWithFlags(&e->h, hipEventDisableTiming));
     for (Event &e : d.rev) HIP_TRY(hipEventCreate(&e.h));
+    for (Event &e : d.pev) HIP_TRY(hipEventCreate(&e.h));
     HIP_TRY(d.tables.ensure(1));
     for (ExpSet *x : {&d.cur, &d.alt}) { // the planned expansion's error word and pad count
       HIP_TRY(x->perr.ensure(1));
@@ -1272,8 +1285,12 @@ static int extend_checks(gn_ctx *ctx, Dev &d, size_t m, int mode, const LeafAllo
 // needs).  Then one reduction per level, bottom-up.  A level of 2^31 nodes fails the call with
 // GN_E_CAPACITY.  Every allocation goes through alloc, those of the scans and of evaluate_on
 // included: they are reserved before the call that would make them.
+// tail (the _pv calls; else NULL, and nothing below is allocated or launched): each level keeps its
+// own moves instead of sharing X.moves, the reduction is quiesce_reduce_pv_kernel, which also leaves
+// each node's chosen child, and quiesce_walk_kernel follows those from every selected leaf into
+// tail (zeroed by the caller), between d.pev[0] and d.pev[1].
 static int quiesce(gn_ctx *ctx, Dev &d, const gn_eval *rec, size_t total, size_t m, int mode, int depth,
-                   const LeafAlloc &alloc, size_t *nodes, hipStream_t s) {
+                   const LeafAlloc &alloc, size_t *nodes, uint16_t *tail, hipStream_t s) {
   Dev::LeafStage &X = d.leaf;
   // the levels, top-down: cnt[k] nodes at level k; top: the deepest level whose children were counted
   size_t cnt[GN_MAX_QUIESCE_DEPTH + 2] = {m};
@@ -1301,13 +1318,15 @@ static int quiesce(gn_ctx *ctx, Dev &d, const gn_eval *rec, size_t total, size_t
     LEAF_ALLOC(k + 1, t, N.boards.ensure(t));
     LEAF_ALLOC(k + 1, t, N.rec.ensure(t));
     if (k + 1 < depth) LEAF_ALLOC(k + 1, t, N.val.ensure(t));
-    LEAF_ALLOC(k + 1, t, X.moves.ensure(t));
+    if (tail) LEAF_ALLOC(k + 1, t, N.moves.ensure(t));
+    else LEAF_ALLOC(k + 1, t, X.moves.ensure(t));
+    uint16_t *const moves = tail ? N.moves.p : X.moves.p;
     LEAF_ALLOC(k + 1, t, X.owner.ensure(t));
     // (everything evaluate_on would allocate for the level: it then allocates nothing, so that no
     // allocation of the stage can fail as anything but GN_E_NOMEM)
     LEAF_ALLOC(k + 1, t, reserve_eval_outputs(d.cur.eb, t, mode));
     if (king_sorted(ctx, t)) LEAF_ALLOC(k + 1, t, reserve_king_sort_buffers(d, t, mode));
-    HIP_TRY(launch_quiesce_children(boards, cnt[k], d.tables.p, L.offsets.p, t, X.moves.p, X.owner.p, N.boards.p, s));
+    HIP_TRY(launch_quiesce_children(boards, cnt[k], d.tables.p, L.offsets.p, t, moves, X.owner.p, N.boards.p, s));
     if (int rc = evaluate_on(ctx, d, N.boards.p, t, mode, N.rec.p, s)) return rc;
     *nodes += t;
     boards = N.boards.p;
@@ -1316,9 +1335,25 @@ static int quiesce(gn_ctx *ctx, Dev &d, const gn_eval *rec, size_t total, size_t
   for (int k = top; k >= 0; --k) {
     const size_t nc = cnt[k + 1];
     const bool last = k + 1 == depth || !nc; // the children are valued statically (or there are none)
+    if (tail) {
+      LEAF_ALLOC(k, cnt[k], X.lv[k].best.ensure(cnt[k]));
+      HIP_TRY(launch_quiesce_reduce_pv(k ? X.lv[k].rec.p : rec, k ? nullptr : X.idx.p, cnt[k], X.lv[k].offsets.p, nc,
+                                       nc ? X.lv[k + 1].rec.p : nullptr, last ? nullptr : X.lv[k + 1].val.p,
+                                       nc ? X.lv[k + 1].moves.p : nullptr, k ? X.lv[k].val.p : X.sv.p, X.lv[k].best.p, s));
+      continue;
+    }
     HIP_TRY(launch_quiesce_reduce(k ? X.lv[k].rec.p : rec, k ? nullptr : X.idx.p, cnt[k], X.lv[k].offsets.p, nc,
                                   nc ? X.lv[k + 1].rec.p : nullptr, last ? nullptr : X.lv[k + 1].val.p,
                                   k ? X.lv[k].val.p : X.sv.p, s));
+  }
+  if (tail) {
+    QuiescePvLevels P = {};
+    P.levels = top + 1;
+    for (int k = 0; k <= top; ++k) P.best[k] = X.lv[k].best.p, P.moves[k] = X.lv[k + 1].moves.p;
+    for (int k = 0; k <= top + 1; ++k) P.cnt[k] = (uint32_t)cnt[k];
+    HIP_TRY(hipEventRecord(d.pev[0], s));
+    HIP_TRY(launch_quiesce_walk(P, X.idx.p, m, total, tail, s));
+    HIP_TRY(hipEventRecord(d.pev[1], s));
   }
   return GN_OK;
 }
@@ -1335,9 +1370,11 @@ static int quiesce(gn_ctx *ctx, Dev &d, const gn_eval *rec, size_t total, size_t
 // to ext and counted.  Synchronous: every buffer is sized from a read-back count before anything is
 // queued on it, and the kernels clamp their offsets to those counts; the stream is idle on every
 // return.  d.mu held, inside a sequence on s, no expansion in flight on d.cur.
+// tail (QUIESCE alone; NULL: none): total * GN_MAX_QUIESCE_DEPTH entries, zeroed here, then the
+// searched leaves' own variations (quiesce).
 template <class Parent, class Off>
 static int value_leaves(gn_ctx *ctx, Dev &d, const Leaves<Parent, Off> &lv, int mode, LeafRule rule, int32_t *ext,
-                        LeafCount *res, hipStream_t s) {
+                        uint16_t *tail, LeafCount *res, hipStream_t s) {
   *res = LeafCount{};
   if (int rc = check_leaf_rule(rule)) return rc;
   if (mode < GN_MODE_FULL || mode > GN_MODE_SMALL) return fail(GN_E_INVALID, "bad mode %d", mode);
@@ -1357,6 +1394,7 @@ static int value_leaves(gn_ctx *ctx, Dev &d, const Leaves<Parent, Off> &lv, int 
              : fail(GN_E_INVALID, "the check extension supports < 2^31 leaves per call");
   const LeafAlloc alloc{d, rule};
   Dev::LeafStage &X = d.leaf;
+  if (tail) HIP_TRY(hipMemsetAsync(tail, 0, total * GN_MAX_QUIESCE_DEPTH * sizeof(uint16_t), s));
   LEAF_ALLOC(0, total, X.sel.ensure(total + 1));
   LEAF_ALLOC(0, total, X.pos.ensure(total + 1));
   if (q) {
@@ -1379,13 +1417,14 @@ static int value_leaves(gn_ctx *ctx, Dev &d, const Leaves<Parent, Off> &lv, int 
     LEAF_ALLOC(0, m, X.count.ensure(1));
     HIP_TRY(launch_extend_boards(lv.parents, lv.n, lv.offsets, lv.moves, X.sel.p, X.pos.p, total, d.tables.p, X.idx.p,
                                  X.boards.p, X.sv.p, s));
-    if (int rc = q ? quiesce(ctx, d, lv.rec, total, m, mode, rule.depth, alloc, &below, s)
+    if (int rc = q ? quiesce(ctx, d, lv.rec, total, m, mode, rule.depth, alloc, &below, tail, s)
                    : extend_checks(ctx, d, m, mode, alloc, s))
       return rc;
     HIP_TRY(hipMemsetAsync(X.count.p, 0, sizeof(unsigned long long), s));
     HIP_TRY(launch_extend_scatter(X.idx.p, X.sv.p, m, ext, X.count.p, s));
     HIP_TRY(hipMemcpyAsync(&valued, X.count.p, sizeof(valued), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    if (tail) HIP_TRY(hipEventElapsedTime(&res->pv_ms, d.pev[0], d.pev[1]));
   }
   res->leaves = (size_t)valued, res->nodes = below;
   return idle.ok = true, GN_OK;
@@ -1724,12 +1763,13 @@ static double ms_since(Clock::time_point t) {
 // and its counts are added to the device's statistics of the rule's kind, whatever it returns.
 template <class Parent, class Off>
 static int extend_stage(gn_ctx *ctx, Dev &d, const Leaves<Parent, Off> &lv, int mode, LeafRule rule, int32_t *ext,
-                        hipStream_t s) {
+                        uint16_t *tail, hipStream_t s) {
   const auto t0 = Clock::now();
   LeafCount c;
-  const int rc = value_leaves(ctx, d, lv, mode, rule, ext, &c, s);
+  const int rc = value_leaves(ctx, d, lv, mode, rule, ext, tail, &c, s);
   Dev::LeafStage::Stats &st = d.leaf.stats[rule.kind];
   st.ms += ms_since(t0), st.leaves += c.leaves, st.nodes += c.nodes;
+  d.t_pv += c.pv_ms;
   return rc;
 }
 
@@ -1767,7 +1807,7 @@ static int run_shards(gn_ctx *ctx, const std::vector<size_t> &b, F &&f) {
 
 static void reset_host_stats(gn_ctx *ctx) {
   for (auto &dp : ctx->devs) {
-    dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = dp->t_keys = 0;
+    dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = dp->t_keys = dp->t_pv = 0;
     for (auto &st : dp->leaf.stats) st = {};
   }
 }
@@ -1960,6 +2000,9 @@ struct ExpandOut {
   // gn_evaluate_games_lines_extended / _quiescent: each chunk's children are valued by the rule
   // before the ranking (extend_stage), and the chunks run one after another
   LeafRule leaf;
+  // the _pv calls: pvs[0, m * n_lines) receives each line's gn_pv (the quiescence leaves its tails,
+  // and the PVs are assembled on the device and downloaded with the chunk's lines); NULL: none
+  gn_pv *pvs = nullptr;
 };
 // Pass 2 of a shard (see above).  off: the shard's child offsets from pass 1.
 static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m, int mode,
@@ -1976,6 +2019,8 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
     if (n_lines) HIP_TRY(d.ln2[k].ensure(maxp * (size_t)n_lines));
     else HIP_TRY(d.cc2[k].ensure(maxc));
     if (o.leaf.extends()) HIP_TRY(d.leaf.ext.ensure(maxc));
+    if (o.pvs) HIP_TRY(d.pv2[k].ensure(maxp * (size_t)n_lines));
+    if (o.pvs) HIP_TRY(d.leaf.tail.ensure(maxc * GN_MAX_QUIESCE_DEPTH));
     HIP_TRY(d.mv2[k].ensure(maxc));
   }
   int drc[2] = {GN_OK, GN_OK};
@@ -2005,6 +2050,9 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
       if (e == hipSuccess) e = hipStreamWaitEvent(d.copy, d.cev[k], 0);
       if (e == hipSuccess && n_lines)
         e = hipMemcpyAsync(o.lines + pa * (size_t)n_lines, d.ln2[k].p, mp * (size_t)n_lines * sizeof(gn_line),
+                           hipMemcpyDeviceToHost, d.copy);
+      if (e == hipSuccess && n_lines && o.pvs)
+        e = hipMemcpyAsync(o.pvs + pa * (size_t)n_lines, d.pv2[k].p, mp * (size_t)n_lines * sizeof(gn_pv),
                            hipMemcpyDeviceToHost, d.copy);
       if (e == hipSuccess && t && !n_lines)
         e = hipMemcpyAsync(o.child_out + cb, d.cc2[k].p, t * sizeof(gn_child), hipMemcpyDeviceToHost, d.copy);
@@ -2046,12 +2094,17 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
           // is read)
           if (o.leaf.extends())
             if (int r = extend_stage(ctx, d, UnpackedLeaves{d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, t},
-                                     mode, o.leaf, d.leaf.ext.p, s))
+                                     mode, o.leaf, d.leaf.ext.p, o.pvs ? d.leaf.tail.p : nullptr, s))
               return r;
           HIP_TRY(hipEventRecord(d.rev[0], s));
           HIP_TRY(launch_rank_children(d.cur.unpacked.p, mp, d.cur.offsets.p, d.mv2[k].p, d.co2[k].p, ctx->P, d.tables.p,
                                        n_lines, d.ln2[k].p, h.hist ? &h : nullptr, o.leaf.extends() ? d.leaf.ext.p : nullptr, s));
           HIP_TRY(hipEventRecord(d.rev[1], s));
+          if (o.pvs) { // (t == 0: no line is searched, and the tail is not read)
+            HIP_TRY(hipEventRecord(d.pev[2], s));
+            HIP_TRY(launch_line_pvs(mp, d.cur.offsets.p, d.mv2[k].p, d.leaf.tail.p, d.ln2[k].p, n_lines, d.pv2[k].p, s));
+            HIP_TRY(hipEventRecord(d.pev[3], s));
+          }
         } else {
           HIP_TRY(launch_pack_children(d.co2[k].p, t, d.cc2[k].p, s));
         }
@@ -2062,6 +2115,10 @@ static int expand_pipelined(gn_ctx *ctx, Dev &d, const gn_board *d_par, size_t m
           float ms = 0;
           HIP_TRY(hipEventElapsedTime(&ms, d.rev[0], d.rev[1]));
           d.t_rank += ms;
+          if (o.pvs) {
+            HIP_TRY(hipEventElapsedTime(&ms, d.pev[2], d.pev[3]));
+            d.t_pv += ms;
+          }
         }
         d.t_compute += ms_since(t0), t0 = Clock::now();
         HIP_TRY(hipEventRecord(d.cev[k], s));
@@ -2268,6 +2325,7 @@ struct GameShard {
   std::vector<gn_eval> res;         // gathered: the evaluated positions' records ...
   std::vector<gn_line> lres;        // ... and lines ...
   std::vector<gn_line2> l2res;      // ... or two-ply lines
+  std::vector<gn_pv> pvres;         // ... and the lines' PVs (the _pv calls)
   std::vector<gn_history> hist;     // history call: each evaluated position's game so far, in rboards' indices
   std::vector<uint64_t> off;        // child offsets from pass 1 (m + 1, relative)
   uint64_t child_base = 0;          // the shard's first child in the caller's arrays
@@ -2295,6 +2353,7 @@ struct GamesArgs {
   gn_line2 *lines2 = nullptr; // ... or two-ply (with_children 0)
   bool history = false;       // ... with the game-history draws
   LeafRule leaf;              // ... their leaves valued by this rule (extend_stage)
+  gn_pv *pvs = nullptr;       // ... and each line's whole variation (the _pv calls)
 };
 
 // A games call: its arguments, and what its phases hand on.
@@ -2463,6 +2522,7 @@ static int games_gather(const GamesCall &c, GameShard &sh, Dev &d) {
     sh.res.resize(m);
     if (c.lines2) sh.l2res.resize(m * (size_t)c.n_lines);
     else sh.lres.resize(m * (size_t)c.n_lines);
+    if (c.pvs) sh.pvres.resize(m * (size_t)c.n_lines);
   }
   if (c.history) { // one gn_history per evaluated position, uploaded once per shard
     const auto t0 = Clock::now();
@@ -2534,6 +2594,7 @@ static int games_expand(const GamesCall &c, GameShard &sh, Dev &d) {
                           : ExpandOut{rec, c.child_moves + sh.child_base, c.child_out + sh.child_base};
   if (c.history) o.history = RankHistory{d.rkeys.p, d.n_rkeys, d.hist.p};
   o.leaf = c.leaf;
+  if (c.pvs) o.pvs = sh.in_place ? c.pvs + sh.p0 * (size_t)c.n_lines : sh.pvres.data();
   return expand_pipelined(c.ctx, d, sh.parents_of(d), sh.m, c.mode, sh.off,
                           chunk_plan(sh.m, sh.starts, c.ctx->chunk_parents), o);
 }
@@ -2560,6 +2621,7 @@ static void games_scatter(const GamesCall &c) {
   if (!c.n_lines) return;
   if (c.lines2) games_scatter_lines(c, c.lines2, &GameShard::l2res, gn_line2{0, 0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE, 0});
   else games_scatter_lines(c, c.lines, &GameShard::lres, gn_line{0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE});
+  if (c.pvs) games_scatter_lines(c, c.pvs, &GameShard::pvres, gn_pv{});
 }
 
 // phase B of gn_evaluate_games_lines2: the gather, then the two-ply lines' chunk loop (below, with
@@ -2604,10 +2666,11 @@ static int evaluate_games(const GamesArgs &a) {
 template <class Line>
 static int evaluate_games_lines(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines, bool history,
                                 LeafRule leaf, uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
-                                size_t position_cap, Line *lines) {
+                                size_t position_cap, Line *lines, gn_pv *pvs = nullptr) {
   if (int rc = check_leaf_rule(leaf)) return rc;
   if (int rc = check_n_lines(n_lines)) return rc;
   GamesArgs a;
+  a.pvs = pvs;
   a.ctx = ctx, a.games = games, a.n_games = n_games, a.mode = mode, a.position_offsets = position_offsets;
   a.game_status = game_status, a.position_out = position_out, a.position_cap = position_cap;
   a.n_lines = n_lines, a.history = history, a.leaf = leaf;
@@ -2674,6 +2737,14 @@ int gn_evaluate_games_lines_quiescent(gn_ctx *ctx, const gn_game *games, size_t 
                               game_status, position_out, position_cap, lines);
 }
 
+int gn_evaluate_games_lines_quiescent_pv(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                         int history, int depth, uint32_t *position_offsets, int32_t *game_status,
+                                         gn_eval *position_out, size_t position_cap, gn_line *lines, gn_pv *pvs) {
+  if (n_games && !pvs) return fail(GN_E_INVALID, "pvs is NULL");
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(depth), position_offsets,
+                              game_status, position_out, position_cap, lines, pvs);
+}
+
 int gn_evaluate_games_lines2(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                              uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
                              size_t position_cap, gn_line2 *lines) {
@@ -2700,6 +2771,14 @@ int gn_evaluate_games_lines2_quiescent(gn_ctx *ctx, const gn_game *games, size_t
                                        gn_eval *position_out, size_t position_cap, gn_line2 *lines) {
   return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(depth), position_offsets,
                               game_status, position_out, position_cap, lines);
+}
+
+int gn_evaluate_games_lines2_quiescent_pv(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                          int history, int depth, uint32_t *position_offsets, int32_t *game_status,
+                                          gn_eval *position_out, size_t position_cap, gn_line2 *lines, gn_pv *pvs) {
+  if (n_games && !pvs) return fail(GN_E_INVALID, "pvs is NULL");
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(depth), position_offsets,
+                              game_status, position_out, position_cap, lines, pvs);
 }
 
 int gn_partition(const uint32_t *weights, size_t n_items, int n_shards, size_t *bounds) {
@@ -3184,7 +3263,7 @@ int gn_rank_children_extended_device(gn_ctx *ctx, int device_slot, const gn_boar
 // gn_extend_checks_device / gn_quiesce_device: the leaf stage on a caller's buffers.  *leaves = the
 // leaves valued, *nodes (QUIESCE alone; else NULL) = the positions evaluated below them.
 static int value_leaves_call(gn_ctx *ctx, int device_slot, const PackedLeaves &lv, int mode, LeafRule rule, int32_t *d_ext,
-                             size_t *leaves, size_t *nodes, void *stream) {
+                             size_t *leaves, size_t *nodes, void *stream, uint16_t *d_tail = nullptr) {
   Dev *d = slot(ctx, device_slot);
   if (!d || !leaves || (rule.kind == LeafRule::QUIESCE && !nodes)) return fail(GN_E_INVALID, "bad argument");
   *leaves = 0;
@@ -3194,7 +3273,7 @@ static int value_leaves_call(gn_ctx *ctx, int device_slot, const PackedLeaves &l
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
   LeafCount c;
-  if (int rc = value_leaves(ctx, *d, lv, mode, rule, d_ext, &c, call.s)) return rc;
+  if (int rc = value_leaves(ctx, *d, lv, mode, rule, d_ext, d_tail, &c, call.s)) return rc;
   *leaves = c.leaves;
   if (nodes) *nodes = c.nodes;
   HIP_TRY(call.sg->finish()); // blocking (gpu_nnue.h): d_ext is written when the call returns
@@ -3213,6 +3292,48 @@ int gn_quiesce_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, s
                       size_t *searched, size_t *nodes, void *stream) {
   return value_leaves_call(ctx, device_slot, PackedLeaves{d_parents, n, d_offsets, d_moves, d_rec, total}, mode,
                            LeafRule::quiesce(depth), d_ext, searched, nodes, stream);
+}
+
+int gn_quiesce_pv_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
+                         const uint16_t *d_moves, const gn_eval *d_rec, size_t total, int mode, int depth, int32_t *d_ext,
+                         uint16_t *d_tail, size_t *searched, size_t *nodes, void *stream) {
+  if (total && !d_tail) return fail(GN_E_INVALID, "d_tail is NULL");
+  return value_leaves_call(ctx, device_slot, PackedLeaves{d_parents, n, d_offsets, d_moves, d_rec, total}, mode,
+                           LeafRule::quiesce(depth), d_ext, searched, nodes, stream, d_tail);
+}
+
+// gn_line_pvs_device / gn_line2_pvs_device: checked as the ranking calls are (rank_call_args, without
+// parents), then one launch.
+static int line_pvs_args(gn_ctx *ctx, int device_slot, size_t n, const uint32_t *d_offsets, int n_lines,
+                         const void *d_lines, const void *d_pvs, Dev *&d) {
+  d = slot(ctx, device_slot);
+  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
+  if (int rc = check_n_lines(n_lines)) return rc;
+  if (n && (!d_offsets || !d_lines || !d_pvs)) return fail(GN_E_INVALID, "NULL buffer");
+  return GN_OK;
+}
+
+int gn_line_pvs_device(gn_ctx *ctx, int device_slot, size_t n, const uint32_t *d_offsets, const uint16_t *d_moves,
+                       const uint16_t *d_tail, const gn_line *d_lines, int n_lines, gn_pv *d_pvs, void *stream) {
+  Dev *d;
+  if (int rc = line_pvs_args(ctx, device_slot, n, d_offsets, n_lines, d_lines, d_pvs, d)) return rc;
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_line_pvs(n, d_offsets, d_moves, d_moves ? d_tail : nullptr, d_lines, n_lines, d_pvs, call.s));
+  return GN_OK;
+}
+
+int gn_line2_pvs_device(gn_ctx *ctx, int device_slot, size_t n, const uint32_t *d_offsets, const uint16_t *d_moves,
+                        const uint32_t *d_goffsets, const uint16_t *d_gmoves, const uint16_t *d_gtail,
+                        const gn_line2 *d_lines, int n_lines, gn_pv *d_pvs, void *stream) {
+  Dev *d;
+  if (int rc = line_pvs_args(ctx, device_slot, n, d_offsets, n_lines, d_lines, d_pvs, d)) return rc;
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  const bool tails = d_moves && d_goffsets && d_gmoves; // (a NULL level: nothing to find a leaf in)
+  HIP_TRY(launch_line2_pvs(n, d_offsets, d_moves, d_goffsets, d_gmoves, tails ? d_gtail : nullptr, d_lines, n_lines, d_pvs,
+                           call.s));
+  return GN_OK;
 }
 
 // Depth 2: the children of gn_expand_device's children.  Level 2 is
@@ -3577,6 +3698,7 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
   case GN_STAT_RANK_NS:
   case GN_STAT_RANK2_NS:
   case GN_STAT_KEYS_NS:
+  case GN_STAT_PV_NS:
   case GN_STAT_HOST_TAIL_NS: { // the last host-buffer call, max over devices
     double m = 0;
     for (auto &dp : ctx->devs) {
@@ -3588,6 +3710,7 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
                       : option == GN_STAT_RANK_NS          ? d.t_rank
                       : option == GN_STAT_RANK2_NS         ? d.t_rank2
                       : option == GN_STAT_KEYS_NS          ? d.t_keys
+                      : option == GN_STAT_PV_NS            ? d.t_pv
                                                            : d.t_tail);
     }
     *value = (int64_t)(m * 1e6);
@@ -3651,8 +3774,10 @@ int gn_expand_and_evaluate(gn_ctx *ctx, const char *const *parent_fens, size_t n
 // keys are the whole shard's.
 // leaf: a rule that extends values the grandchildren after the expansion (extend_stage; the children
 // as parents, the library's own boards), and the ranking takes their values.
+// pvs (the _pv calls; NULL: none): the shard's PVs, as lines; the leaf stage leaves the grandchildren's
+// tails, the PVs are assembled after the ranking and downloaded with the chunk's lines.
 static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m, int mode, int K, gn_eval *out,
-                         gn_line2 *lines, const RankHistory &history, LeafRule leaf) {
+                         gn_line2 *lines, const RankHistory &history, LeafRule leaf, gn_pv *pvs = nullptr) {
   hipStream_t s = d.stream;
   Dev::Lines2 &x = d.l2;
   // 1,024 parents are ~1 M grandchildren: a few hundred MB of records, boards and partial sums
@@ -3683,20 +3808,34 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
     const RankHistory h = {history.keys, history.n_keys, history.hist ? history.hist + a : nullptr};
     if (leaf.extends()) { // (t == 0 or g == 0: nothing is read)
       HIP_TRY(x.gext.ensure(std::max<size_t>(g, 1)));
-      rc = extend_stage(ctx, d, PackedLeaves{x.ch.p, t, x.goff.p, x.gmv.p, x.gco.p, g}, mode, leaf, x.gext.p, s);
+      if (pvs) HIP_TRY(x.gtail.ensure(std::max<size_t>(g, 1) * GN_MAX_QUIESCE_DEPTH));
+      rc = extend_stage(ctx, d, PackedLeaves{x.ch.p, t, x.goff.p, x.gmv.p, x.gco.p, g}, mode, leaf, x.gext.p,
+                        pvs ? x.gtail.p : nullptr, s);
       if (rc) return rc;
     }
+    if (pvs) HIP_TRY(x.pv.ensure(mp * (size_t)K));
     HIP_TRY(hipEventRecord(d.rev[0], s));
     HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables.p, K,
                                x.ln.p, h.hist ? &h : nullptr, leaf.extends() ? x.gext.p : nullptr, s));
     HIP_TRY(hipEventRecord(d.rev[1], s));
+    if (pvs) { // (g == 0: no line is searched, and the tails are not read)
+      HIP_TRY(hipEventRecord(d.pev[2], s));
+      HIP_TRY(launch_line2_pvs(mp, x.off.p, x.mv.p, x.goff.p, x.gmv.p, leaf.extends() ? x.gtail.p : nullptr, x.ln.p, K,
+                               x.pv.p, s));
+      HIP_TRY(hipEventRecord(d.pev[3], s));
+    }
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, d.rev[0], d.rev[1]));
     d.t_rank2 += ms;
+    if (pvs) {
+      HIP_TRY(hipEventElapsedTime(&ms, d.pev[2], d.pev[3]));
+      d.t_pv += ms;
+    }
     d.t_compute += ms_since(t0), t0 = Clock::now();
     HIP_TRY(hipMemcpyAsync(out + a, x.po.p, mp * sizeof(gn_eval), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(lines + a * (size_t)K, x.ln.p, mp * (size_t)K * sizeof(gn_line2), hipMemcpyDeviceToHost, s));
+    if (pvs) HIP_TRY(hipMemcpyAsync(pvs + a * (size_t)K, x.pv.p, mp * (size_t)K * sizeof(gn_pv), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     d.t_download += ms_since(t0);
   }
@@ -3706,7 +3845,7 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
 // gn_evaluate_lines2: the boards sharded equally over the devices, each shard uploaded and run
 // through lines2_chunks
 static int lines2_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int mode, int K, gn_eval *out,
-                              gn_line2 *lines, LeafRule leaf) {
+                              gn_line2 *lines, LeafRule leaf, gn_pv *pvs) {
   const size_t nd = ctx->devs.size();
   std::vector<size_t> b(nd + 1);
   partition(nullptr, n, (int)nd, b.data());
@@ -3717,7 +3856,8 @@ static int lines2_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int
     HIP_TRY(hipMemcpyAsync(d.par.p, boards + lo, (hi - lo) * sizeof(gn_board), hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipStreamSynchronize(d.stream));
     d.t_upload += ms_since(t0);
-    return lines2_chunks(ctx, d, d.par.p, hi - lo, mode, K, out + lo, lines + lo * (size_t)K, NO_HISTORY, leaf);
+    return lines2_chunks(ctx, d, d.par.p, hi - lo, mode, K, out + lo, lines + lo * (size_t)K, NO_HISTORY, leaf,
+                         pvs ? pvs + lo * (size_t)K : nullptr);
   });
 }
 
@@ -3728,19 +3868,20 @@ static int games_lines2(const GamesCall &c, GameShard &sh, Dev &d) {
   if (rc) return rc;
   gn_line2 *const ln = sh.in_place ? c.lines2 + sh.p0 * (size_t)c.n_lines : sh.l2res.data();
   return lines2_chunks(c.ctx, d, sh.parents_of(d), sh.m, c.mode, c.n_lines, sh.records_of(c.position_out), ln,
-                       c.history ? RankHistory{d.rkeys.p, d.n_rkeys, d.hist.p} : NO_HISTORY, c.leaf);
+                       c.history ? RankHistory{d.rkeys.p, d.n_rkeys, d.hist.p} : NO_HISTORY, c.leaf,
+                       !c.pvs ? nullptr : sh.in_place ? c.pvs + sh.p0 * (size_t)c.n_lines : sh.pvres.data());
 }
 
 // The FEN lines2 calls
 static int evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, LeafRule leaf,
-                           gn_eval *out, gn_line2 *lines) {
+                           gn_eval *out, gn_line2 *lines, gn_pv *pvs = nullptr) {
   if (int rc = check_leaf_rule(leaf)) return rc;
   if (!slot(ctx, 0)) return fail(GN_E_INVALID, "bad context");
   if (int rc = check_n_lines(n_lines)) return rc;
   if (n && (!fens || !out || !lines)) return fail(GN_E_INVALID, "NULL argument");
   if (!n) return GN_OK;
   return on_packed_fens(ctx, fens, n, [&](const gn_board *boards) -> int {
-    return lines2_boards_host(ctx, boards, n, mode, n_lines, out, lines, leaf);
+    return lines2_boards_host(ctx, boards, n, mode, n_lines, out, lines, leaf, pvs);
   });
 }
 
@@ -3757,6 +3898,12 @@ int gn_evaluate_lines2_extended(gn_ctx *ctx, const char *const *fens, size_t n, 
 int gn_evaluate_lines2_quiescent(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, int depth,
                                  gn_eval *out, gn_line2 *lines) {
   return evaluate_lines2(ctx, fens, n, mode, n_lines, LeafRule::quiesce(depth), out, lines);
+}
+
+int gn_evaluate_lines2_quiescent_pv(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, int depth,
+                                    gn_eval *out, gn_line2 *lines, gn_pv *pvs) {
+  if (n && !pvs) return fail(GN_E_INVALID, "pvs is NULL");
+  return evaluate_lines2(ctx, fens, n, mode, n_lines, LeafRule::quiesce(depth), out, lines, pvs);
 }
 
 int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {

@@ -350,6 +350,32 @@ hipError_t launch_quiesce_children(const gn_board *boards, size_t n, const Table
                                    size_t nc, uint16_t *moves, uint32_t *owner, gn_board *children, hipStream_t s);
 hipError_t launch_quiesce_reduce(const gn_eval *rec, const uint32_t *idx, size_t m, const uint64_t *off, size_t nc,
                                  const gn_eval *crec, const int32_t *cval, int32_t *val, hipStream_t s);
+// The quiescence's own variation (the rule at gn_pv in include/gpu_nnue.h).  reduce_pv: reduce, plus
+// best[i] = the chosen child's index in the next level (cmoves: that level's moves, for the tie rule),
+// QUIESCE_NO_BEST where the node stands pat or has no child.  walk: a lane per selected leaf follows
+// best down L.levels levels and writes the moves it passes to tail[idx[i] * GN_MAX_QUIESCE_DEPTH + k]
+// (tail zeroed by the caller, total * GN_MAX_QUIESCE_DEPTH entries).  line_pvs / line2_pvs: pvs[p * K
+// + k] = the gn_pv of lines[p * K + k], its tail (NULL: none) found through the position's offsets
+// and moves; a lane per (position, line).
+constexpr uint32_t QUIESCE_NO_BEST = 0xFFFFFFFFu;
+struct QuiescePvLevels {
+  const uint32_t *best[GN_MAX_QUIESCE_DEPTH]; // level k's chosen children ...
+  const uint16_t *moves[GN_MAX_QUIESCE_DEPTH]; // ... and level k + 1's moves
+  uint32_t cnt[GN_MAX_QUIESCE_DEPTH + 1];      // the levels' node counts
+  int levels;                                  // the levels that were reduced (best[k] valid for k < levels)
+};
+hipError_t launch_quiesce_reduce_pv(const gn_eval *rec, const uint32_t *idx, size_t m, const uint64_t *off, size_t nc,
+                                    const gn_eval *crec, const int32_t *cval, const uint16_t *cmoves, int32_t *val,
+                                    uint32_t *best, hipStream_t s);
+hipError_t launch_quiesce_walk(const QuiescePvLevels &L, const uint32_t *idx, size_t m, size_t total, uint16_t *tail,
+                               hipStream_t s);
+hipError_t launch_line_pvs(size_t n, const uint64_t *off, const uint16_t *moves, const uint16_t *tail,
+                           const gn_line *lines, int K, gn_pv *pvs, hipStream_t s);
+hipError_t launch_line_pvs(size_t n, const uint32_t *off, const uint16_t *moves, const uint16_t *tail,
+                           const gn_line *lines, int K, gn_pv *pvs, hipStream_t s);
+hipError_t launch_line2_pvs(size_t n, const uint32_t *off, const uint16_t *moves, const uint32_t *goff,
+                            const uint16_t *gmoves, const uint16_t *gtail, const gn_line2 *lines, int K, gn_pv *pvs,
+                            hipStream_t s);
 // exclusive_scan_u64's / king_sort's temporary storage for n1 counts / n boards grown now, so that
 // the call itself does not allocate (a caller that reports a failed allocation as its own)
 hipError_t reserve_scan_u64(size_t n1, void *&temp, size_t &temp_bytes);

@@ -2337,6 +2337,170 @@ hipError_t launch_quiesce_reduce(const gn_eval *rec, const uint32_t *idx, size_t
   return hipGetLastError();
 }
 
+// ---- the quiescence's own variation (include/gpu_nnue.h gn_pv, PVQ) ----
+// quiesce_reduce_kernel with the argmax: the same val[i], and best[i] = the index in the next level
+// of the child the value came from, QUIESCE_NO_BEST where the node stands pat, has no legal move or
+// has no children.  Among children of equal value the smaller move encoding wins (cmoves: the next
+// level's moves; gen_legal's order is not relied on); stand pat wins a tie with a move, since a move
+// replaces it only when it is strictly better.  A sibling, so that the calls without PVs keep
+// quiesce_reduce_kernel's code and registers.
+__global__ void quiesce_reduce_pv_kernel(const gn_eval *__restrict__ rec, const uint32_t *__restrict__ idx, size_t m,
+                                         const uint64_t *__restrict__ off, size_t nc, const gn_eval *__restrict__ crec,
+                                         const int32_t *__restrict__ cval, const uint16_t *__restrict__ cmoves,
+                                         int32_t *__restrict__ val, uint32_t *__restrict__ best_out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const gn_eval r = rec[idx ? idx[i] : i];
+  const bool check = (r.flags & GN_FLAG_IN_CHECK) != 0;
+  int32_t best;
+  uint32_t bi = QUIESCE_NO_BEST;
+  if (!idx && (r.flags & GN_FLAG_NO_MOVES)) {
+    best = check ? -VALUE_MATE : 0;
+  } else {
+    best = check ? INT32_MIN : r.final_v;
+    uint16_t bm = 0;
+    const uint64_t c1 = std::min<uint64_t>(off[i + 1], nc);
+    for (uint64_t c = std::min<uint64_t>(off[i], c1); c < c1; ++c) {
+      int32_t v;
+      if (cval) v = cval[c];
+      else {
+        const gn_eval k = crec[c];
+        v = (k.flags & GN_FLAG_NO_MOVES) ? ((k.flags & GN_FLAG_IN_CHECK) ? -VALUE_MATE : 0) : k.final_v;
+      }
+      v = negate_ply(v);
+      const uint16_t mv = cmoves[c];
+      if (v > best || (v == best && bi != QUIESCE_NO_BEST && mv < bm)) best = v, bi = (uint32_t)c, bm = mv;
+    }
+    if (best == INT32_MIN) best = r.final_v; // (unreachable, as in quiesce_reduce_kernel)
+  }
+  val[i] = best;
+  best_out[i] = bi;
+}
+
+// tail[j * GN_MAX_QUIESCE_DEPTH + k] = 0 for all j < total (the caller's memset), then a lane per
+// selected leaf i walks best down the levels: node i of level 0, its chosen child in level 1, ...;
+// the move into level k + 1 goes to tail[idx[i] * GN_MAX_QUIESCE_DEPTH + k].  It stops at
+// QUIESCE_NO_BEST, which every index at or beyond the level's count is too (the counts the levels'
+// buffers were sized from), and after L.levels moves.
+__global__ void quiesce_walk_kernel(QuiescePvLevels L, const uint32_t *__restrict__ idx, size_t m, size_t total,
+                                    uint16_t *__restrict__ tail) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const size_t j = idx[i];
+  if (j >= total) return;
+  uint32_t node = (uint32_t)i;
+  for (int k = 0; k < GN_MAX_QUIESCE_DEPTH; ++k) {
+    if (k >= L.levels) break;
+    const uint32_t b = L.best[k][node];
+    if (b >= L.cnt[k + 1]) break;
+    tail[j * GN_MAX_QUIESCE_DEPTH + k] = L.moves[k][b];
+    node = b;
+  }
+}
+
+// The PV of line k of position p (the rule at gn_pv), a lane per (position, line): the line's own
+// one move or two, then the leaf's tail when the line carries GN_FLAG_SEARCHED.  The leaf is found
+// by its move among the position's children -- and, two plies deep, by the reply among that child's
+// grandchildren -- every range clamped to the offsets' own last entry, which the move and tail
+// buffers were sized from.  A move that is not found (inconsistent input) leaves the PV without a tail.
+__device__ __forceinline__ void pv_tail(gn_pv &pv, const uint16_t *__restrict__ tail, uint64_t leaf) {
+  for (int k = 0; k < GN_MAX_QUIESCE_DEPTH; ++k) {
+    const uint16_t m = tail[leaf * GN_MAX_QUIESCE_DEPTH + k];
+    if (!m) break;
+    pv.moves[pv.len++] = m;
+  }
+}
+// the index in [off[p], off[p + 1]) clamped to end of the entry whose move is m; end: none
+template <class Off>
+__device__ __forceinline__ uint64_t pv_find(const Off *__restrict__ off, size_t p, uint64_t end,
+                                            const uint16_t *__restrict__ moves, uint16_t m) {
+  const uint64_t c1 = std::min<uint64_t>(off[p + 1], end);
+  for (uint64_t c = std::min<uint64_t>(off[p], c1); c < c1; ++c)
+    if (moves[c] == m) return c;
+  return end;
+}
+template <class Off>
+__global__ void line_pvs_kernel(size_t n, const Off *__restrict__ off, const uint16_t *__restrict__ moves,
+                                const uint16_t *__restrict__ tail, const gn_line *__restrict__ lines, int K,
+                                gn_pv *__restrict__ pvs) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * (size_t)K) return;
+  const size_t p = t / (size_t)K;
+  const gn_line ln = lines[t];
+  gn_pv pv = {};
+  if (!(ln.flags & GN_FLAG_NO_SCORE)) {
+    pv.moves[pv.len++] = ln.move;
+    if (tail && (ln.flags & GN_FLAG_SEARCHED)) {
+      const uint64_t end = off[n], c = pv_find(off, p, end, moves, ln.move);
+      if (c < end) pv_tail(pv, tail, c);
+    }
+  }
+  pvs[t] = pv;
+}
+__global__ void line2_pvs_kernel(size_t n, const uint32_t *__restrict__ off, const uint16_t *__restrict__ moves,
+                                 const uint32_t *__restrict__ goff, const uint16_t *__restrict__ gmoves,
+                                 const uint16_t *__restrict__ gtail, const gn_line2 *__restrict__ lines, int K,
+                                 gn_pv *__restrict__ pvs) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * (size_t)K) return;
+  const size_t p = t / (size_t)K;
+  const gn_line2 ln = lines[t];
+  gn_pv pv = {};
+  if (!(ln.flags & GN_FLAG_NO_SCORE)) {
+    pv.moves[pv.len++] = ln.move;
+    if (ln.plies == 2) {
+      pv.moves[pv.len++] = ln.reply;
+      if (gtail && (ln.flags & GN_FLAG_SEARCHED)) {
+        const uint64_t end = off[n], c = pv_find(off, p, end, moves, ln.move);
+        if (c < end) {
+          const uint64_t gend = goff[end], g = pv_find(goff, (size_t)c, gend, gmoves, ln.reply);
+          if (g < gend) pv_tail(pv, gtail, g);
+        }
+      }
+    }
+  }
+  pvs[t] = pv;
+}
+
+hipError_t launch_quiesce_reduce_pv(const gn_eval *rec, const uint32_t *idx, size_t m, const uint64_t *off, size_t nc,
+                                    const gn_eval *crec, const int32_t *cval, const uint16_t *cmoves, int32_t *val,
+                                    uint32_t *best, hipStream_t s) {
+  if (!m) return hipSuccess;
+  hipLaunchKernelGGL(quiesce_reduce_pv_kernel, dim3(blocks_for(m, 256)), dim3(256), 0, s, rec, idx, m, off, nc, crec,
+                     cval, cmoves, val, best);
+  return hipGetLastError();
+}
+hipError_t launch_quiesce_walk(const QuiescePvLevels &L, const uint32_t *idx, size_t m, size_t total, uint16_t *tail,
+                               hipStream_t s) {
+  if (!m) return hipSuccess;
+  hipLaunchKernelGGL(quiesce_walk_kernel, dim3(blocks_for(m, 256)), dim3(256), 0, s, L, idx, m, total, tail);
+  return hipGetLastError();
+}
+template <class Off>
+static hipError_t line_pvs_t(size_t n, const Off *off, const uint16_t *moves, const uint16_t *tail, const gn_line *lines,
+                             int K, gn_pv *pvs, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL((line_pvs_kernel<Off>), dim3(blocks_for(n * (size_t)K, 256)), dim3(256), 0, s, n, off, moves, tail,
+                     lines, K, pvs);
+  return hipGetLastError();
+}
+hipError_t launch_line_pvs(size_t n, const uint64_t *off, const uint16_t *moves, const uint16_t *tail,
+                           const gn_line *lines, int K, gn_pv *pvs, hipStream_t s) {
+  return line_pvs_t(n, off, moves, tail, lines, K, pvs, s);
+}
+hipError_t launch_line_pvs(size_t n, const uint32_t *off, const uint16_t *moves, const uint16_t *tail,
+                           const gn_line *lines, int K, gn_pv *pvs, hipStream_t s) {
+  return line_pvs_t(n, off, moves, tail, lines, K, pvs, s);
+}
+hipError_t launch_line2_pvs(size_t n, const uint32_t *off, const uint16_t *moves, const uint32_t *goff,
+                            const uint16_t *gmoves, const uint16_t *gtail, const gn_line2 *lines, int K, gn_pv *pvs,
+                            hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(line2_pvs_kernel, dim3(blocks_for(n * (size_t)K, 256)), dim3(256), 0, s, n, off, moves, goff, gmoves,
+                     gtail, lines, K, pvs);
+  return hipGetLastError();
+}
+
 hipError_t launch_count_sum(const gn_board *boards, size_t n, const Tables *tables, unsigned long long *total,
                             hipStream_t s) {
   if (!n) return hipSuccess;

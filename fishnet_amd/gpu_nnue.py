@@ -47,6 +47,10 @@ LINE2_DTYPE = np.dtype([("value", "<i4"), ("score", "<i4"), ("move", "<u2"), ("r
 EVAL_SIZE, BOARD_SIZE, CHILD_SIZE = EVAL_DTYPE.itemsize, BOARD_DTYPE.itemsize, CHILD_DTYPE.itemsize
 assert EVAL_SIZE == 24 and BOARD_SIZE == 32 and CHILD_SIZE == 12 and LINE_DTYPE.itemsize == 12
 assert LINE2_DTYPE.itemsize == 16
+# gn_pv: one line's whole variation (its own moves, then the quiescence's; gpu_nnue.h at gn_pv), 16 bytes
+MAX_PV = 6  # GN_MAX_PV
+PV_DTYPE = np.dtype([("len", "<u2"), ("moves", "<u2", (MAX_PV,)), ("reserved", "<u2")])
+assert PV_DTYPE.itemsize == 16
 ABI_VERSION = 4
 
 EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_abi_version",
@@ -65,7 +69,9 @@ EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_
            "gn_extend_checks_device", "gn_rank_children_extended_device", "gn_rank_lines2_extended_device",
            "gn_evaluate_lines2_extended", "gn_evaluate_games_lines2_extended", "gn_evaluate_games_lines_extended",
            "gn_quiesce_device", "gn_evaluate_lines2_quiescent", "gn_evaluate_games_lines2_quiescent",
-           "gn_evaluate_games_lines_quiescent"]
+           "gn_evaluate_games_lines_quiescent",
+           "gn_quiesce_pv_device", "gn_line_pvs_device", "gn_line2_pvs_device", "gn_evaluate_lines2_quiescent_pv",
+           "gn_evaluate_games_lines2_quiescent_pv", "gn_evaluate_games_lines_quiescent_pv"]
 OPT_INCREMENTAL_CHILDREN, OPT_XCD_SWIZZLE, OPT_KING_SORT, OPT_CHAIN, OPT_KING_CACHE = 1, 2, 3, 4, 5
 OPT_CHUNK_PARENTS, OPT_COALESCE, OPT_STREAM_SLICES, OPT_FAST_BATCH, OPT_EXPAND_PIPELINE = 6, 7, 8, 9, 10
 STAT_PLAN_NS, STAT_STREAM_NS, STAT_SCRATCH_PADS, STAT_FINISH_NS = 101, 102, 103, 104
@@ -74,6 +80,7 @@ STAT_BATCH_LAUNCHES, STAT_BATCH_CALLS, STAT_FAST_BATCHES, STAT_FAST_FALLBACKS = 
 STAT_RANK_NS, STAT_RANK2_NS, STAT_KEYS_NS = 121, 122, 123
 STAT_EXTEND_NS, STAT_EXTENDED_LEAVES = 124, 125
 STAT_QUIESCE_NS, STAT_QUIESCE_LEAVES, STAT_QUIESCE_NODES = 126, 127, 128
+STAT_PV_NS = 129
 MAX_QUIESCE_DEPTH = 4  # GN_MAX_QUIESCE_DEPTH
 NOT_EXTENDED = -(2 ** 31)  # GN_NOT_EXTENDED: a d_ext entry of a leaf the check extension does not value
 HOST_STAGES = {"parse": 110, "upload": 111, "replay": 112, "compute": 113, "download": 114, "tail": 115, "total": 116}
@@ -211,6 +218,12 @@ def lib():
         "gn_evaluate_lines2_quiescent": [vp, vp, sz, i32, i32, i32, vp, vp],
         "gn_evaluate_games_lines2_quiescent": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp],
         "gn_evaluate_games_lines_quiescent": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp],
+        "gn_quiesce_pv_device": [vp, i32, vp, sz, vp, vp, vp, sz, i32, i32, vp, vp, C.POINTER(sz), C.POINTER(sz), vp],
+        "gn_line_pvs_device": [vp, i32, sz, vp, vp, vp, vp, i32, vp, vp],
+        "gn_line2_pvs_device": [vp, i32, sz, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+        "gn_evaluate_lines2_quiescent_pv": [vp, vp, sz, i32, i32, i32, vp, vp, vp],
+        "gn_evaluate_games_lines2_quiescent_pv": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp, vp],
+        "gn_evaluate_games_lines_quiescent_pv": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -536,7 +549,7 @@ class GpuNnue:
         """gn_evaluate_games_lines2_history: evaluate_games_lines2 with each game's history."""
         return self.evaluate_games_lines2(games, n_lines, mode, cap, history=True)
 
-    def _games_lines(self, call, line_dtype, games, n_lines, mode, cap):
+    def _games_lines(self, call, line_dtype, games, n_lines, mode, cap, pvs=False):
         ng = len(games)
         arr, _keep = _games_array(games)
         offs = np.zeros(ng + 1, dtype=np.uint32)
@@ -545,14 +558,15 @@ class GpuNnue:
         for _ in range(2):
             pos = np.zeros(max(pcap, 1), dtype=EVAL_DTYPE)
             lines = np.zeros((max(pcap, 1), max(n_lines, 1)), dtype=line_dtype)
+            pv = np.zeros((max(pcap, 1), max(n_lines, 1)), dtype=PV_DTYPE) if pvs else None
             rc = call(self.h, arr, ng, mode, n_lines, offs.ctypes.data, status.ctypes.data, pos.ctypes.data, pcap,
-                      lines.ctypes.data)
+                      lines.ctypes.data, *([pv.ctypes.data] if pvs else []))
             if rc == E_CAPACITY and cap is None and int(offs[-1]) > pcap:
                 pcap = int(offs[-1])
                 continue
             _check(rc)
             p = int(offs[-1])
-            return offs, status, pos[:p], lines[:p]
+            return (offs, status, pos[:p], lines[:p]) + ((pv[:p],) if pvs else ())
         raise GnError(E_CAPACITY, "capacity retry failed")
 
     def evaluate_games_lines_extended(self, games, n_lines, mode=MODE_FULL, cap=None, history=False):
@@ -593,6 +607,32 @@ class GpuNnue:
         f = lib().gn_evaluate_lines2_quiescent
         call = lambda h, arr, n, mode, K, *rest: f(h, arr, n, mode, K, depth, *rest)
         return self.evaluate_lines2(fens, n_lines, mode, call=call)
+
+    def evaluate_games_lines_quiescent_pv(self, games, n_lines, depth, mode=MODE_FULL, cap=None, history=False):
+        """gn_evaluate_games_lines_quiescent_pv: evaluate_games_lines_quiescent plus pvs[positions,
+        n_lines] (PV_DTYPE): each line's move followed by the quiescence's own moves below it."""
+        f = lib().gn_evaluate_games_lines_quiescent_pv
+        call = lambda h, arr, ng, mode, K, *rest: f(h, arr, ng, mode, K, int(bool(history)), depth, *rest)
+        return self._games_lines(call, LINE_DTYPE, games, n_lines, mode, cap, pvs=True)
+
+    def evaluate_games_lines2_quiescent_pv(self, games, n_lines, depth, mode=MODE_FULL, cap=None, history=False):
+        """gn_evaluate_games_lines2_quiescent_pv: evaluate_games_lines2_quiescent plus pvs[positions,
+        n_lines] (PV_DTYPE): move, reply and the quiescence's own moves below the grandchild."""
+        f = lib().gn_evaluate_games_lines2_quiescent_pv
+        call = lambda h, arr, ng, mode, K, *rest: f(h, arr, ng, mode, K, int(bool(history)), depth, *rest)
+        return self._games_lines(call, LINE2_DTYPE, games, n_lines, mode, cap, pvs=True)
+
+    def evaluate_lines2_quiescent_pv(self, fens, n_lines, depth, mode=MODE_FULL):
+        """gn_evaluate_lines2_quiescent_pv: evaluate_lines2_quiescent plus pvs[positions, n_lines]
+        (PV_DTYPE)."""
+        n = len(fens)
+        arr, _keep = _fen_array(fens)
+        out = np.zeros(n, dtype=EVAL_DTYPE)
+        lines = np.zeros((n, max(n_lines, 1)), dtype=LINE2_DTYPE)
+        pvs = np.zeros((n, max(n_lines, 1)), dtype=PV_DTYPE)
+        _check(lib().gn_evaluate_lines2_quiescent_pv(self.h, arr, n, mode, n_lines, depth, out.ctypes.data,
+                                                     lines.ctypes.data, pvs.ctypes.data))
+        return out, lines, pvs
 
     def evaluate_games_lines_history(self, games, n_lines, mode=MODE_FULL, cap=None):
         """gn_evaluate_games_lines_history: evaluate_games_lines with each game's history."""
@@ -732,6 +772,32 @@ class GpuNnue:
         _check(lib().gn_quiesce_device(self.h, slot, p(d_parents), n, p(d_offsets), p(d_moves), p(d_rec), total, mode,
                                        depth, p(d_ext), C.byref(ns), C.byref(nn), stream))
         return ns.value, nn.value
+
+    def quiesce_pv_device(self, d_parents, n, d_offsets, d_moves, d_rec, total, mode, depth, d_ext, d_tail, stream=None,
+                          slot=0):
+        """gn_quiesce_pv_device: quiesce_device plus d_tail[total * MAX_QUIESCE_DEPTH] (uint16): each
+        searched leaf's own variation, 0-terminated; all 0 for an unsearched leaf.  Blocking."""
+        ns, nn = C.c_size_t(), C.c_size_t()
+        p = lambda b: b.ptr if b is not None else None
+        _check(lib().gn_quiesce_pv_device(self.h, slot, p(d_parents), n, p(d_offsets), p(d_moves), p(d_rec), total, mode,
+                                          depth, p(d_ext), p(d_tail), C.byref(ns), C.byref(nn), stream))
+        return ns.value, nn.value
+
+    def line_pvs_device(self, n, d_offsets, d_moves, d_tail, d_lines, n_lines, d_pvs, stream=None, slot=0):
+        """gn_line_pvs_device: d_pvs[n * n_lines] (PV_DTYPE) of the ranked d_lines (LINE_DTYPE); d_tail
+        from quiesce_pv_device, None: the lines' own moves only.  Asynchronous."""
+        p = lambda b: b.ptr if b is not None else None
+        _check(lib().gn_line_pvs_device(self.h, slot, n, p(d_offsets), p(d_moves), p(d_tail), p(d_lines), n_lines,
+                                        p(d_pvs), stream))
+
+    def line2_pvs_device(self, n, out, d_gtail, d_lines, n_lines, d_pvs, stream=None, slot=0):
+        """gn_line2_pvs_device: d_pvs[n * n_lines] (PV_DTYPE) of the ranked two-ply d_lines (out: the
+        expand2_device dict); d_gtail from quiesce_pv_device over the children as parents, None: no
+        tails.  Asynchronous."""
+        p = lambda k: out[k].ptr if out.get(k) is not None else None
+        _check(lib().gn_line2_pvs_device(self.h, slot, n, p("off"), p("mv"), p("goff"), p("gmv"),
+                                         d_gtail.ptr if d_gtail is not None else None, d_lines.ptr, n_lines, d_pvs.ptr,
+                                         stream))
 
     def rank_children_extended_device(self, d_parents, n, d_offsets, d_moves, d_child_out, d_ext, n_lines, d_lines,
                                       d_keys=None, n_keys=0, d_hist=None, stream=None, slot=0):

@@ -208,6 +208,12 @@ extern "C" {
 #define GN_STAT_QUIESCE_LEAVES 127    /* ... the leaves it searched, summed over the devices */
 #define GN_STAT_QUIESCE_NODES 128     /* ... and the positions it evaluated below them (both
                                          0 after any other host-buffer call)               */
+#define GN_STAT_PV_NS 129             /* the PV kernels (the walk down the quiescence's levels and
+                                         the assembly of the gn_pv entries) in the last
+                                         gn_evaluate_lines2_quiescent_pv or
+                                         gn_evaluate_games_lines[2]_quiescent_pv, summed over its
+                                         chunks (the slowest device; 0 after any other
+                                         host-buffer call)                                 */
 #define GN_STAT_BATCH_LAUNCHES 117    /* merged gn_evaluate_batch launches since load ...   */
 #define GN_STAT_BATCH_CALLS 118       /* ... and the calls they served (GN_OPT_COALESCE)    */
 #define GN_STAT_FAST_BATCHES 119      /* evaluations run by the captured small-batch graphs
@@ -352,14 +358,36 @@ typedef struct gn_child {
  * GN_NOT_EXTENDED and the ranking values it as the plain calls do: mate, stalemate or static.  The
  * precedence in the ranking is the extended calls': no legal move, then (history forms) drawn by
  * rule, then the d_ext override, then static.  The quiescence knows no history and no fifty-move
- * rule inside its tree, as the extension knows none, and its own moves are not reported (plies stays
- * 1 or 2).  The quiescent calls do not also run the check extension: rule 3 is how they treat a leaf
+ * rule inside its tree, as the extension knows none, and its own moves are not reported in the line
+ * (plies stays 1 or 2; the _pv calls below return them beside it).  The quiescent calls do not also run the check extension: rule 3 is how they treat a leaf
  * in check.  Consequences: for a leaf in check, Q(x, 1) equals the score rule's value(x, 1); for a
  * searched leaf not in check, Q(x, d) >= final_v(x); a position none of whose leaves is searched has
  * byte-equal lines from the plain and the quiescent call; and mate values can appear on a line
- * through a capture. */
+ * through a capture.
+ *
+ * The quiescence's own moves (gn_pv below; gn_quiesce_pv_device, gn_line_pvs_device,
+ * gn_line2_pvs_device, gn_evaluate_lines2_quiescent_pv, gn_evaluate_games_lines_quiescent_pv,
+ * gn_evaluate_games_lines2_quiescent_pv).  PVQ(x, d) is the quiescence's variation below a leaf x,
+ * with the same Q, noisy moves, negate_ply and searched set:
+ *   1. x has no legal move, or d == 0: PVQ is empty;
+ *   2. x is in check: m* = the legal move that maximises negate_ply(Q(child(m), d - 1)), ties to
+ *      the smaller 16-bit move encoding; PVQ = [m*] + PVQ(child(m*), d - 1);
+ *   3. otherwise m* = the same argmax over the noisy legal moves, if there is one; if
+ *      negate_ply(Q(child(m*), d - 1)) > final_v(x), PVQ = [m*] + PVQ(child(m*), d - 1), else PVQ
+ *      is empty: stand pat wins a tie with a move, so the shorter PV wins.
+ * Consequences: len(PVQ(x, d)) <= d; every move of it is legal where it is played, and noisy
+ * unless the mover is in check; and with x_end the position after PVQ and v = -VALUE_MATE (in
+ * check) or 0 when x_end has no legal move, else x_end's static final_v in the call's mode,
+ * negate_ply applied len times to v equals Q(x, d).
+ * A line's PV (gn_pv): an empty line (GN_FLAG_NO_SCORE) has len 0; a gn_line has [move], followed
+ * by PVQ(child, depth) exactly when the line carries GN_FLAG_SEARCHED; a gn_line2 has [move] when
+ * plies == 1, else [move, reply], followed by PVQ(grandchild, depth) exactly when plies == 2 and
+ * the line carries GN_FLAG_SEARCHED.  A leaf the ranking values as mate, as stalemate or, in the
+ * history forms, as drawn by rule has no tail, even where the quiescence searched it: such a line
+ * never carries GN_FLAG_SEARCHED.  The check extension's replies are not reported. */
 #define GN_NOT_EXTENDED INT32_MIN /* a d_ext entry of a leaf the extension / quiescence does not value */
 #define GN_MAX_QUIESCE_DEPTH 4    /* the quiescent calls' depth is 1..GN_MAX_QUIESCE_DEPTH */
+#define GN_MAX_PV (2 + GN_MAX_QUIESCE_DEPTH) /* a line's two moves and the quiescence's own */
 #define GN_MAX_LINES 8 /* lichess sends multipv <= 5 */
 typedef struct gn_line {
   int32_t value;  /* the rule value, p's side-to-move POV, Stockfish units              */
@@ -372,6 +400,14 @@ typedef struct gn_line {
                      only (gn_history below); GN_FLAG_SEARCHED: the check-extended
                      and the quiescent calls only (above)                                */
 } gn_line;
+
+/* The whole variation of one ranked line (the rule at gn_line, "the quiescence's own moves"):
+ * what fishnet's pvs[multipv][depth], a Vec<UciMove>, takes.  Unused entries and reserved are 0. */
+typedef struct gn_pv { /* 16 bytes */
+  uint16_t len;              /* moves in the PV, 0..GN_MAX_PV */
+  uint16_t moves[GN_MAX_PV]; /* Stockfish encoding, castling = king takes rook */
+  uint16_t reserved;
+} gn_pv;
 
 /* Game-history draws in ranked lines (gn_rank_children_history_device,
  * gn_evaluate_games_lines_history): what Stockfish, given `position fen ... moves ...`, scores
@@ -766,6 +802,24 @@ GN_API int gn_evaluate_games_lines_quiescent(gn_ctx *ctx, const gn_game *games, 
                                              int history, int depth, uint32_t *position_offsets, int32_t *game_status,
                                              gn_eval *position_out, size_t position_cap, gn_line *lines);
 
+/* The three quiescent calls above with the lines' whole variations (gn_pv): the same arguments, plus
+ * pvs[positions * n_lines] as the last; pvs[position * n_lines + k] belongs to
+ * lines[position * n_lines + k].  Every other output is byte-equal to the quiescent call's; skipped,
+ * bad and failed positions have len 0.  pvs == NULL: GN_E_INVALID.  The PVs are identical for every
+ * GN_OPT_CHUNK_PARENTS, GN_OPT_EXPAND_PIPELINE and device count.  With PVs each level of the
+ * quiescence keeps its moves and its chosen children (6 bytes per node more), and 16 * n_lines bytes
+ * more per position are downloaded.  GN_STAT_PV_NS: the PV kernels' time. */
+GN_API int gn_evaluate_lines2_quiescent_pv(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines,
+                                           int depth, gn_eval *out, gn_line2 *lines, gn_pv *pvs);
+GN_API int gn_evaluate_games_lines2_quiescent_pv(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode,
+                                                 int n_lines, int history, int depth, uint32_t *position_offsets,
+                                                 int32_t *game_status, gn_eval *position_out, size_t position_cap,
+                                                 gn_line2 *lines, gn_pv *pvs);
+GN_API int gn_evaluate_games_lines_quiescent_pv(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode,
+                                                int n_lines, int history, int depth, uint32_t *position_offsets,
+                                                int32_t *game_status, gn_eval *position_out, size_t position_cap,
+                                                gn_line *lines, gn_pv *pvs);
+
 /* The partitioner the library uses to shard work over the devices of a context and
  * that multi-process callers use to shard over ranks: contiguous ranges of n_items
  * items, bounds[k] = first item of shard k, bounds[n_shards] = n_items; shard k
@@ -895,6 +949,31 @@ GN_API int gn_extend_checks_device(gn_ctx *ctx, int device_slot, const gn_board 
 GN_API int gn_quiesce_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
                              const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_rec, size_t total,
                              int mode, int depth, int32_t *d_ext, size_t *searched, size_t *nodes, void *stream);
+/* gn_quiesce_device plus the searched leaves' own variations: d_tail[j * GN_MAX_QUIESCE_DEPTH + k]
+ * (total * GN_MAX_QUIESCE_DEPTH entries) = move k of PVQ(leaf j, depth) (the rule at gn_line),
+ * 0-terminated when shorter than GN_MAX_QUIESCE_DEPTH: move 0 is never legal.  All entries of an
+ * unsearched leaf are 0, entries no parent's offsets cover included.  d_ext, *searched and *nodes are
+ * byte-equal to gn_quiesce_device's.  Blocking; errors as gn_quiesce_device; d_tail == NULL with
+ * total > 0: GN_E_INVALID. */
+GN_API int gn_quiesce_pv_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_rec, size_t total,
+                                int mode, int depth, int32_t *d_ext, uint16_t *d_tail, size_t *searched, size_t *nodes,
+                                void *stream);
+/* d_pvs[i * n_lines + k] = the gn_pv of d_lines[i * n_lines + k], the lines a ranking call wrote for
+ * the same expansion (d_offsets, d_moves as gn_expand_device wrote them) and d_tail as
+ * gn_quiesce_pv_device wrote it for the level the ranking took d_ext from; d_tail == NULL: no tails
+ * (the lines' own moves only).  A line's leaf is found by its move; every range is clamped to
+ * d_offsets[n], and a move that is not found gives the PV without a tail.  Asynchronous on `stream`
+ * (NULL = the context's own), no read-back.  n_lines outside 1..GN_MAX_LINES: GN_E_INVALID. */
+GN_API int gn_line_pvs_device(gn_ctx *ctx, int device_slot, size_t n, const uint32_t *d_offsets,
+                              const uint16_t *d_moves, const uint16_t *d_tail, const gn_line *d_lines, int n_lines,
+                              gn_pv *d_pvs, void *stream);
+/* The same for two-ply lines: the expansion as gn_expand2_device wrote it, d_gtail as
+ * gn_quiesce_pv_device wrote it for the grandchild level (NULL: no tails). */
+GN_API int gn_line2_pvs_device(gn_ctx *ctx, int device_slot, size_t n, const uint32_t *d_offsets,
+                               const uint16_t *d_moves, const uint32_t *d_goffsets, const uint16_t *d_gmoves,
+                               const uint16_t *d_gtail, const gn_line2 *d_lines, int n_lines, gn_pv *d_pvs,
+                               void *stream);
 /* gn_rank_children_history_device with check-extended (or quiescent) leaves: d_ext as
  * gn_extend_checks_device (or gn_quiesce_device)
  * wrote it for the same expansion (NULL: nothing is extended).  d_hist == NULL selects no history

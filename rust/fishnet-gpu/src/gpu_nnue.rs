@@ -23,6 +23,7 @@ pub use sys::gn_child as GpuChild;
 pub use sys::gn_eval as GpuEval;
 pub use sys::gn_line as GpuLine;
 pub use sys::gn_line2 as GpuLine2;
+pub use sys::gn_pv as GpuPv;
 
 pub struct GpuNnue(*mut sys::gn_ctx);
 
@@ -368,6 +369,75 @@ impl GpuNnue {
         evals.truncate(total);
         lines.truncate(total * n_lines);
         Ok((offsets, status, evals, lines))
+    }
+
+    /// evaluate_lines2_quiescent with each line's whole variation (gn_evaluate_lines2_quiescent_pv;
+    /// the header at gn_pv): pvs[i * n_lines + k] is line k's move and reply followed by the
+    /// quiescence's own moves below the grandchild, what `pvs[multipv][depth]` takes.
+    #[allow(clippy::type_complexity)]
+    pub fn evaluate_lines2_quiescent_pv(&self, fens: &[Fen], n_lines: usize, depth: i32, mode: i32)
+                                        -> Result<(Vec<GpuEval>, Vec<GpuLine2>, Vec<GpuPv>), GpuError> {
+        let owned: Vec<CString> = fens.iter().map(|f| CString::new(f.to_string()).unwrap()).collect();
+        let ptrs: Vec<*const std::os::raw::c_char> = owned.iter().map(|c| c.as_ptr()).collect();
+        let mut evals = vec![GpuEval::default(); fens.len()];
+        let mut lines = vec![GpuLine2::default(); fens.len() * n_lines];
+        let mut pvs = vec![GpuPv::default(); fens.len() * n_lines];
+        // SAFETY: as evaluate_lines2_quiescent; pvs has as many elements as lines.
+        check(unsafe {
+            sys::gn_evaluate_lines2_quiescent_pv(self.0, ptrs.as_ptr(), ptrs.len(), mode, n_lines as i32, depth,
+                                                 evals.as_mut_ptr(), lines.as_mut_ptr(), pvs.as_mut_ptr())
+        })?;
+        Ok((evals, lines, pvs))
+    }
+
+    /// evaluate_games_lines_quiescent with each line's whole variation
+    /// (gn_evaluate_games_lines_quiescent_pv): the move, then the quiescence's own moves.
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn evaluate_games_lines_quiescent_pv(&self, games: &[(CString, CString, Vec<u32>)], n_lines: usize, depth: i32,
+                                             history: bool, mode: i32)
+                                             -> Result<(Vec<u32>, Vec<i32>, Vec<GpuEval>, Vec<GpuLine>, Vec<GpuPv>), GpuError> {
+        let (gs, cap) = games_and_capacity(games);
+        let mut offsets = vec![0u32; games.len() + 1];
+        let mut status = vec![0i32; games.len()];
+        let mut evals = vec![GpuEval::default(); cap];
+        let mut lines = vec![GpuLine::default(); cap * n_lines];
+        let mut pvs = vec![GpuPv::default(); cap * n_lines];
+        // SAFETY: as evaluate_games_lines_quiescent; pvs has as many elements as lines.
+        check(unsafe {
+            sys::gn_evaluate_games_lines_quiescent_pv(self.0, gs.as_ptr(), gs.len(), mode, n_lines as i32,
+                                                      history as i32, depth, offsets.as_mut_ptr(), status.as_mut_ptr(),
+                                                      evals.as_mut_ptr(), cap, lines.as_mut_ptr(), pvs.as_mut_ptr())
+        })?;
+        let total = offsets[games.len()] as usize;
+        evals.truncate(total);
+        lines.truncate(total * n_lines);
+        pvs.truncate(total * n_lines);
+        Ok((offsets, status, evals, lines, pvs))
+    }
+
+    /// evaluate_games_lines2_quiescent with each line's whole variation
+    /// (gn_evaluate_games_lines2_quiescent_pv): move, reply, then the quiescence's own moves.
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn evaluate_games_lines2_quiescent_pv(&self, games: &[(CString, CString, Vec<u32>)], n_lines: usize, depth: i32,
+                                              history: bool, mode: i32)
+                                              -> Result<(Vec<u32>, Vec<i32>, Vec<GpuEval>, Vec<GpuLine2>, Vec<GpuPv>), GpuError> {
+        let (gs, cap) = games_and_capacity(games);
+        let mut offsets = vec![0u32; games.len() + 1];
+        let mut status = vec![0i32; games.len()];
+        let mut evals = vec![GpuEval::default(); cap];
+        let mut lines = vec![GpuLine2::default(); cap * n_lines];
+        let mut pvs = vec![GpuPv::default(); cap * n_lines];
+        // SAFETY: as evaluate_games_lines_quiescent_pv.
+        check(unsafe {
+            sys::gn_evaluate_games_lines2_quiescent_pv(self.0, gs.as_ptr(), gs.len(), mode, n_lines as i32,
+                                                       history as i32, depth, offsets.as_mut_ptr(), status.as_mut_ptr(),
+                                                       evals.as_mut_ptr(), cap, lines.as_mut_ptr(), pvs.as_mut_ptr())
+        })?;
+        let total = offsets[games.len()] as usize;
+        evals.truncate(total);
+        lines.truncate(total * n_lines);
+        pvs.truncate(total * n_lines);
+        Ok((offsets, status, evals, lines, pvs))
     }
 
     /// Whole acquired batches: replay root FEN + UCI moves (skipPositions honoured) and

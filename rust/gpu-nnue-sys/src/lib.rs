@@ -65,6 +65,7 @@ pub const GN_NOT_EXTENDED: i32 = i32::MIN;
 pub const GN_STAT_QUIESCE_NS: c_int = 126;
 pub const GN_STAT_QUIESCE_LEAVES: c_int = 127;
 pub const GN_STAT_QUIESCE_NODES: c_int = 128;
+pub const GN_STAT_PV_NS: c_int = 129;
 
 // per-position flags
 pub const GN_FLAG_IN_CHECK: u16 = 1;
@@ -119,6 +120,19 @@ impl gn_child {
 pub const MAX_LINES: usize = 8;
 /// The header's GN_MAX_QUIESCE_DEPTH: the quiescent calls' depth is 1..=MAX_QUIESCE_DEPTH.
 pub const MAX_QUIESCE_DEPTH: c_int = 4;
+/// The header's GN_MAX_PV: a line's two moves and the quiescence's own.
+pub const MAX_PV: usize = 6;
+
+/// The whole variation of one ranked line (16 bytes): the line's move (and reply), followed by the
+/// quiescence's own moves below its leaf when the line carries GN_FLAG_SEARCHED; unused entries
+/// and reserved are 0; an empty line has len 0.  See the header at gn_pv.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct gn_pv {
+    pub len: u16,
+    pub moves: [u16; MAX_PV],
+    pub reserved: u16,
+}
 
 /// One ranked line of a position (MultiPV, 12 bytes): the rule value of a legal move, its score
 /// (`cp`, or the mate distance with GN_FLAG_MATE), the move and its flags (GN_FLAG_IN_CHECK: the
@@ -279,6 +293,19 @@ extern "C" {
                                              n_lines: c_int, history: c_int, depth: c_int, position_offsets: *mut u32,
                                              game_status: *mut i32, position_out: *mut gn_eval, position_cap: usize,
                                              lines: *mut gn_line) -> c_int;
+    pub fn gn_evaluate_lines2_quiescent_pv(ctx: *mut gn_ctx, fens: *const *const c_char, n: usize, mode: c_int,
+                                           n_lines: c_int, depth: c_int, out: *mut gn_eval, lines: *mut gn_line2,
+                                           pvs: *mut gn_pv) -> c_int;
+    pub fn gn_evaluate_games_lines2_quiescent_pv(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
+                                                 n_lines: c_int, history: c_int, depth: c_int,
+                                                 position_offsets: *mut u32, game_status: *mut i32,
+                                                 position_out: *mut gn_eval, position_cap: usize,
+                                                 lines: *mut gn_line2, pvs: *mut gn_pv) -> c_int;
+    pub fn gn_evaluate_games_lines_quiescent_pv(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
+                                                n_lines: c_int, history: c_int, depth: c_int,
+                                                position_offsets: *mut u32, game_status: *mut i32,
+                                                position_out: *mut gn_eval, position_cap: usize, lines: *mut gn_line,
+                                                pvs: *mut gn_pv) -> c_int;
     pub fn gn_partition(weights: *const u32, n_items: usize, n_shards: c_int, bounds: *mut usize) -> c_int;
     pub fn gn_perft(ctx: *mut gn_ctx, fen: *const c_char, depth: c_int, nodes: *mut u64) -> c_int;
     pub fn gn_pack_fens(fens: *const *const c_char, n: usize, out: *mut gn_board, ok: *mut u8) -> c_int;
@@ -324,6 +351,17 @@ extern "C" {
                              d_offsets: *const u32, d_moves: *const u16, d_rec: *const gn_eval, total: usize,
                              mode: c_int, depth: c_int, d_ext: *mut i32, searched: *mut usize, nodes: *mut usize,
                              stream: *mut c_void) -> c_int;
+    pub fn gn_quiesce_pv_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                                d_offsets: *const u32, d_moves: *const u16, d_rec: *const gn_eval, total: usize,
+                                mode: c_int, depth: c_int, d_ext: *mut i32, d_tail: *mut u16, searched: *mut usize,
+                                nodes: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn gn_line_pvs_device(ctx: *mut gn_ctx, device_slot: c_int, n: usize, d_offsets: *const u32,
+                              d_moves: *const u16, d_tail: *const u16, d_lines: *const gn_line, n_lines: c_int,
+                              d_pvs: *mut gn_pv, stream: *mut c_void) -> c_int;
+    pub fn gn_line2_pvs_device(ctx: *mut gn_ctx, device_slot: c_int, n: usize, d_offsets: *const u32,
+                               d_moves: *const u16, d_goffsets: *const u32, d_gmoves: *const u16,
+                               d_gtail: *const u16, d_lines: *const gn_line2, n_lines: c_int, d_pvs: *mut gn_pv,
+                               stream: *mut c_void) -> c_int;
     pub fn gn_rank_children_extended_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
                                             d_offsets: *const u32, d_moves: *const u16, d_child_out: *const gn_eval,
                                             d_keys: *const u64, n_keys: usize, d_hist: *const gn_history,

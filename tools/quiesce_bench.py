@@ -11,10 +11,12 @@ GN_STAT_EXTEND_NS, GN_STAT_QUIESCE_NS, GN_STAT_QUIESCE_LEAVES, GN_STAT_QUIESCE_N
   one_ply   gn_evaluate_games_lines / _extended / _quiescent (history 0) over `--games` seeded random
             games of `--plies` plies (gn_random_games_uci).  The extended and quiescent calls run their
             chunks unpipelined; GN_OPT_CHUNK_PARENTS is `--chunk` (0: the default).
-The variants are plain, extended and q<d> for every depth of `--depths`.  The plain and extended
+The variants are plain, extended and q<d> for every depth of `--depths`; a depth written <d>pv adds
+q<d>pv, the quiescent call that also returns each line's whole variation (gn_evaluate_lines2_quiescent_pv,
+gn_evaluate_games_lines_quiescent_pv; GN_STAT_PV_NS is then reported as "pv").  The plain and extended
 paths are the parent commit's code; run with GPU_NNUE_LIB set to another build of the library and
 `--depths ""` to measure that build's calls.  Prints one JSON line.
-Usage: python tools/quiesce_bench.py [--positions N] [--games G] [--lines K] [--reps R] [--depths 1,2,3]
+Usage: python tools/quiesce_bench.py [--positions N] [--games G] [--lines K] [--reps R] [--depths 1,1pv,2,2pv,3]
 """
 import argparse
 import json
@@ -44,7 +46,8 @@ def main():
     nn.set_option(G.OPT_CHUNK_PARENTS, args.chunk)
     L = G.lib()
     K = args.lines
-    depths = [int(d) for d in args.depths.split(",") if d]
+    depths = [d for d in args.depths.split(",") if d]  # "2": q2, "2pv": q2pv
+    with_pv = any(d.endswith("pv") for d in depths)
 
     fens = G.boards_to_fens(G.random_positions(0x5EED2222, 0, args.positions, 160))
     n = len(fens)
@@ -52,12 +55,16 @@ def main():
     out = np.zeros(n, dtype=G.EVAL_DTYPE)
     lines2 = np.zeros((n, K), dtype=G.LINE2_DTYPE)
     ends = (out.ctypes.data, lines2.ctypes.data)
+    pvs2 = np.zeros((n, K), dtype=G.PV_DTYPE)
 
     def two_ply(variant):
         if variant == "plain":
             return lambda: G._check(L.gn_evaluate_lines2(nn.h, arr, n, G.MODE_FULL, K, *ends))
         if variant == "extended":
             return lambda: G._check(L.gn_evaluate_lines2_extended(nn.h, arr, n, G.MODE_FULL, K, *ends))
+        if variant.endswith("pv"):
+            return lambda: G._check(L.gn_evaluate_lines2_quiescent_pv(nn.h, arr, n, G.MODE_FULL, K, int(variant[1:-2]), *ends,
+                                                                      pvs2.ctypes.data))
         return lambda: G._check(L.gn_evaluate_lines2_quiescent(nn.h, arr, n, G.MODE_FULL, K, int(variant[1:]), *ends))
 
     start = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1"
@@ -69,12 +76,16 @@ def main():
     pos = np.zeros(pcap, dtype=G.EVAL_DTYPE)
     lines1 = np.zeros((pcap, K), dtype=G.LINE_DTYPE)
     tail = (offs.ctypes.data, status.ctypes.data, pos.ctypes.data, pcap, lines1.ctypes.data)
+    pvs1 = np.zeros((pcap, K), dtype=G.PV_DTYPE)
 
     def one_ply(variant):
         if variant == "plain":
             return lambda: G._check(L.gn_evaluate_games_lines(nn.h, garr, ng, G.MODE_FULL, K, *tail))
         if variant == "extended":
             return lambda: G._check(L.gn_evaluate_games_lines_extended(nn.h, garr, ng, G.MODE_FULL, K, 0, *tail))
+        if variant.endswith("pv"):
+            return lambda: G._check(L.gn_evaluate_games_lines_quiescent_pv(nn.h, garr, ng, G.MODE_FULL, K, 0,
+                                                                           int(variant[1:-2]), *tail, pvs1.ctypes.data))
         return lambda: G._check(L.gn_evaluate_games_lines_quiescent(nn.h, garr, ng, G.MODE_FULL, K, 0, int(variant[1:]),
                                                                     *tail))
 
@@ -87,6 +98,8 @@ def main():
             st["quiesce"] = round(nn.get_option(G.STAT_QUIESCE_NS) / 1e6, 3)
             st["quiesce_leaves"] = nn.get_option(G.STAT_QUIESCE_LEAVES)
             st["quiesce_nodes"] = nn.get_option(G.STAT_QUIESCE_NODES)
+        if with_pv:
+            st["pv"] = round(nn.get_option(G.STAT_PV_NS) / 1e6, 3)
         return st
 
     def measure(make):
