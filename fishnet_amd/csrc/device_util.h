@@ -300,7 +300,7 @@ __device__ __forceinline__ int32_t wave_sum_dpp(int32_t v) {
 
 // ---- the column-sliced stream's finishing step for one position (finalize_kernel, which
 // takes the big net's outputs from the partial sums itself): the NPART
-// slices' fc_0 sums (part[t * npos + q][16]) + bias, the activations, fc_1, fc_2 -- the
+// slices' fc_0 sums (part[t * npos + q], one record of GN_PART_DWORDS dwords) + bias, the activations, fc_1, fc_2 -- the
 // whole-row kernel's finishing step in scalar integer arithmetic (exact: every sum is an
 // integer sum, the wrapping adds as there).  info = pinfo[q] (PSQT value, bucket >= 0).
 // w1s: the 8 buckets' fc_1 weights (32 outputs x 32 int8, 8 dwords per output) staged in LDS
@@ -308,10 +308,41 @@ __device__ __forceinline__ int32_t wave_sum_dpp(int32_t v) {
 __device__ __forceinline__ void stage_fc1(int4v *w1s, const NetDevice &net) {
   for (int i = threadIdx.x; i < 8 * 32 * 2; i += blockDim.x) w1s[i] = reinterpret_cast<const int4v *>(net.w1)[i];
 }
+// Four unsigned 24-bit values in three dwords (the packed partial sums' record, kernels.h), and back
+typedef uint32_t uint3v __attribute__((ext_vector_type(3)));
+__device__ __forceinline__ uint3v pack24x4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+  return uint3v{a | b << 24, b >> 8 | c << 16, c >> 16 | d << 8};
+}
+__device__ __forceinline__ int4v unpack24x4(uint32_t x, uint32_t y, uint32_t z) {
+  return int4v{(int)(x & 0xFFFFFFu), (int)(x >> 24 | (y & 0xFFFFu) << 8), (int)(y >> 16 | (z & 0xFFu) << 16),
+               (int)(z >> 8)};
+}
 // a position's fc_0 sums over the NPART slices (sums[k]: outputs 4k .. 4k + 3, bias not added),
-// read by its own lane (wrapping int32 adds, as the LDS atomics)
-template <int NPART>
+// read by its own lane.  Packed records (DW = GN_PART_DWORDS = 12): three 16-B loads per slice, the
+// values biased by the slice's part_off, which slice_finish_from's b0p takes off again; int32
+// records (DW 16, the in-place array): wrapping int32 adds, as the LDS atomics
+template <int NPART, int DW>
 __device__ __forceinline__ void slice_sums(const int32_t *__restrict__ part, uint64_t npos, uint64_t q, int4v (&sums)[4]) {
+  static_assert(DW == 12 || DW == 16, "record width");
+  if constexpr (DW == 12) {
+  int4v rec[NPART][3];
+#pragma unroll
+  for (int t = 0; t < NPART; ++t)
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+      rec[t][r] = *reinterpret_cast<const int4v *>(part + ((uint64_t)t * npos + q) * 12 + 4 * r);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    sums[r] = int4v{0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < NPART; ++t) {
+      auto dw = [&](int i) { return (uint32_t)rec[t][i >> 2][i & 3]; }; // (constant indices once unrolled)
+      const int4v c = unpack24x4(dw(3 * r), dw(3 * r + 1), dw(3 * r + 2));
+#pragma unroll
+      for (int k = 0; k < 4; ++k) sums[r][k] = wadd(sums[r][k], c[k]);
+    }
+  }
+  } else {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     sums[r] = *reinterpret_cast<const int4v *>(part + q * 16 + 4 * r);
@@ -322,14 +353,16 @@ __device__ __forceinline__ void slice_sums(const int32_t *__restrict__ part, uin
       for (int k = 0; k < 4; ++k) sums[r][k] = wadd(sums[r][k], c[k]);
     }
   }
+  }
 }
-// ... and the finishing step from them
-__device__ __forceinline__ int2 slice_finish_from(const NetDevice &net, const int4v *w1s, const int4v (&sums)[4],
-                                                  int2 info) {
+// ... and the finishing step from them (bias0: net.b0p for packed records, whose values carry the
+// slices' offsets; net.b0 for int32 records)
+__device__ __forceinline__ int2 slice_finish_from(const NetDevice &net, const int32_t *__restrict__ bias0,
+                                                  const int4v *w1s, const int4v (&sums)[4], int2 info) {
   const int b = info.y & 7;
   int32_t v[16];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) v[r] = wadd(sums[r >> 2][r & 3], net.b0[b * 16 + r]);
+  for (int r = 0; r < 16; ++r) v[r] = wadd(sums[r >> 2][r & 3], bias0[b * 16 + r]);
   // fc_1's 32 inputs as int8 packed 4 per dword: 15 squared, 15 clipped, 2 zero
   uint32_t x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll

@@ -369,7 +369,7 @@ struct Dev {
   DevBuf<uint32_t> kidx, kperm;   // king-sort permutation
   DevBuf<unsigned long long> sum;
   DevBuf<uint8_t> nslot; // chained walk: child of parent i that is parent i + 1 (255: none)
-  DevBuf<int32_t> part;  // column-sliced stream: fc_0 partial sums of the 3 slices (3 x positions x 16)
+  DevBuf<int32_t> part;  // column-sliced stream: fc_0 partial sums of the 3 slices (3 x positions x GN_PART_DWORDS)
   bool part_locked = false; // a pipeline runs: part is in use by a back half (no reallocation)
   DevBuf<uint64_t> ebound;  // planned expansion (stream.hip): per-parent entry bounds
   DevBuf<uint32_t> pool;    // ... and the scratch-slot pool
@@ -629,7 +629,7 @@ static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static int upload_net(Dev &d, int which, const HostNet &h) {
   const size_t RS = ft_row_stride((uint32_t)h.L1);
-  size_t off[10], o = 0;
+  size_t off[12], o = 0;
   const int carry = h.L1 == 128 ? 0 : CARRY_SLOTS; // the chained walk's scratch rows
   // the PSQT weights once more as [bucket][row] (721 KB: L2-resident for the plan kernel's
   // scattered 4-byte reads, which would otherwise each touch a 6 KB FT row)
@@ -647,15 +647,21 @@ static int upload_net(Dev &d, int which, const HostNet &h) {
       for (int ln = 0; ln < 64; ++ln)
         memcpy(&w0f[(((size_t)b * KS + ks) * 64 + ln) * 16],
                &h.w0[((size_t)b * 16 + (ln & 15)) * h.L1 + 64 * (size_t)ks + 16 * (ln >> 4)], 16);
-  const size_t sz[10] = {((size_t)FT_ROWS + 4 * (size_t)carry + 128 * (size_t)carry + (carry ? 1 : 0)) * RS, h.bias.size() * 2, h.w0.size(), h.b0.size() * 4,
-                         h.w1.size(), h.b1.size() * 4, h.w2.size(), h.b2.size() * 4, psqt.size() * 4, w0f.size()};
-  const void *src[10] = {h.ft.data(), h.bias.data(), h.w0.data(), h.b0.data(),
-                         h.w1.data(), h.b1.data(), h.w2.data(), h.b2.data(), psqt.data(), w0f.data()};
-  for (int i = 0; i < 10; ++i) off[i] = o, o += align256(sz[i]);
+  // the column-sliced stream's packed partial sums (kernels.h): the slices' offsets, the corrected bias
+  std::vector<int32_t> poff(h.L1 == 3072 ? LAYER_STACKS * 3 * 16 : 0), b0p(h.L1 == 3072 ? LAYER_STACKS * 16 : 0);
+  if (h.L1 == 3072 && !part_offsets(h.w0.data(), h.b0.data(), h.L1, poff.data(), b0p.data()))
+    return fail(GN_E_FORMAT, "fc_0 weights of a column slice span 2^24 or more");
+  const size_t sz[12] = {((size_t)FT_ROWS + 4 * (size_t)carry + 128 * (size_t)carry + (carry ? 1 : 0)) * RS, h.bias.size() * 2, h.w0.size(), h.b0.size() * 4,
+                         h.w1.size(), h.b1.size() * 4, h.w2.size(), h.b2.size() * 4, psqt.size() * 4, w0f.size(),
+                         poff.size() * 4, b0p.size() * 4};
+  const void *src[12] = {h.ft.data(), h.bias.data(), h.w0.data(), h.b0.data(),
+                         h.w1.data(), h.b1.data(), h.w2.data(), h.b2.data(), psqt.data(), w0f.data(),
+                         poff.data(), b0p.data()};
+  for (int i = 0; i < 12; ++i) off[i] = o, o += align256(sz[i]);
   if (d.net_mem[which].ensure(o) != hipSuccess) return fail(GN_E_NOMEM, "device allocation of %zu bytes failed", o);
   uint8_t *const m = d.net_mem[which].p;
-  for (int i = 0; i < 10; ++i)
-    HIP_TRY(hipMemcpy(m + off[i], src[i], i == 0 ? (size_t)FT_ROWS * RS : sz[i], hipMemcpyHostToDevice));
+  for (int i = 0; i < 12; ++i)
+    if (sz[i]) HIP_TRY(hipMemcpy(m + off[i], src[i], i == 0 ? (size_t)FT_ROWS * RS : sz[i], hipMemcpyHostToDevice));
   if (carry) HIP_TRY(hipMemset(m + off[0] + (size_t)FT_ROWS * RS, 0, 4 * (size_t)carry * RS));
   if (carry) HIP_TRY(hipMemset(m + off[0] + (size_t)ZERO_ROW * RS, 0, RS)); // the zero row
   NetDevice &n = d.net[which];
@@ -673,6 +679,8 @@ static int upload_net(Dev &d, int which, const HostNet &h) {
   n.b2 = reinterpret_cast<const int32_t *>(m + off[7]);
   n.psqt = reinterpret_cast<const int32_t *>(m + off[8]);
   n.w0f = reinterpret_cast<const int8_t *>(m + off[9]);
+  n.part_off = poff.empty() ? nullptr : reinterpret_cast<const int32_t *>(m + off[10]);
+  n.b0p = b0p.empty() ? nullptr : reinterpret_cast<const int32_t *>(m + off[11]);
   d.has[which] = true;
   return GN_OK;
 }
@@ -1114,12 +1122,12 @@ static int expand_evaluate(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t 
       HIP_TRY(x.tiles.ensure((n + total) / 16 + (K + 2) * nblk + 2));
       HIP_TRY(x.btiles.ensure(nblk + 1));
       HIP_TRY(d.pool.ensure(88)); // 8 XCDs x 8 words of scratch-slot bits, then 8 block claim counters
-      // the sliced stream's partial sums cost 200 B per position (include/gpu_nnue.h,
+      // the sliced stream's partial sums cost 152 B per position (include/gpu_nnue.h,
       // GN_OPT_STREAM_SLICES); when they do not fit, the whole-row stream gives the same results
       // (part_locked: a pipelined front, beside the back half of the previous expansion that reads
       // part -- it may not reallocate it; when it is too small this expansion streams whole rows)
       if (d.net[BIG].L1 == 3072 && ctx->stream_slices == 3) {
-        const size_t need = (size_t)GN_PART_SLICES * 16 * (n + total);
+        const size_t need = (size_t)GN_PART_SLICES * GN_PART_DWORDS * (n + total);
         bool ok = d.part_locked ? d.part.cap >= need : d.part.ensure(need) == hipSuccess;
         ok = ok && x.pinfo.ensure(n + total) == hipSuccess;
         if (ok) x.slices = 3;
@@ -1953,7 +1961,7 @@ static int run_expansions(gn_ctx *ctx, Dev &d, int mode, size_t count, size_t la
     HIP_TRY(hipStreamWaitEvent(F, d.ev_streamed, 0));
     if (largest) {
       if (d.has[BIG] && d.net[BIG].L1 == 3072 && ctx->stream_slices == 3 &&
-          d.part.ensure((size_t)GN_PART_SLICES * 16 * largest) != hipSuccess)
+          d.part.ensure((size_t)GN_PART_SLICES * GN_PART_DWORDS * largest) != hipSuccess)
         (void)hipGetLastError(); // (then the steps that do not fit stream whole rows)
       d.part_locked = true;
     }
@@ -4001,6 +4009,20 @@ int gn_debug_plan_snapshot(gn_ctx *ctx, int device_slot, gn_plan_snapshot_header
     else
       for (size_t i = 0; i < c.need; ++i) static_cast<uint32_t *>(c.dst)[i] = (uint32_t)i; // (order: as they come)
   }
+  return GN_OK;
+}
+
+// plan_snapshot.h (internal, for the tests): the big net's packed-partial-sum tables as the device holds them.
+int gn_debug_part_offsets(gn_ctx *ctx, int device_slot, int32_t *part_off, int32_t *b0p) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d || !part_off || !b0p) return fail(GN_E_INVALID, "bad argument");
+  DevCall call(*d);
+  if (call.rc) return call.rc;
+  const NetDevice &n = d->net[BIG];
+  if (!d->has[BIG] || !n.part_off || !n.b0p) return fail(GN_E_INVALID, "no 3072-wide big net is loaded");
+  HIP_TRY(hipStreamSynchronize(call.s));
+  HIP_TRY(hipMemcpy(part_off, n.part_off, (size_t)LAYER_STACKS * 3 * 16 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(b0p, n.b0p, (size_t)LAYER_STACKS * 16 * sizeof(int32_t), hipMemcpyDeviceToHost));
   return GN_OK;
 }
 

@@ -52,10 +52,20 @@ constexpr unsigned ENT_SPARE = 32;
 // slower (round 5: finish 5.44 -> 2.75 ms, but each later stream launch +2.1 ms: the prefetch
 // misses to HBM and, vector-memory completion being in order, holds up the ring's next loads).
 // GN_PART_SLICES: the arrays launch_plan_stream's part holds.
+// A position's record in a slice's array (GN_PART_DWORDS dwords): its 16 sums as unsigned 24-bit
+// numbers, 48 B.  A slice's sum over its 1,024 activations (each in [0, 127], transform8) with int8
+// weights lies in [127 N, 127 P], N / P the sums of the row's negative / positive weights, a span
+// of 127 sum|w| <= 127 * 128 * 1024 < 2^24: stored as sum + part_off, part_off = -127 N
+// (NetDevice), it never needs more, for any net.  Lane wj of the writer packs outputs 4 wj ..
+// 4 wj + 3 into dwords 3 wj .. 3 wj + 2 (pack24x4 / unpack24x4, device_util.h); finalize adds the
+// slices' values and b0p = b0 - the three offsets: the int32 sum of before, bit for bit.  The
+// in-place array keeps int32 sums (its running totals over the slices exceed 24 bits).
 #ifdef GN_PART_INPLACE
 #define GN_PART_SLICES 1
+#define GN_PART_DWORDS 16
 #else
 #define GN_PART_SLICES 3
+#define GN_PART_DWORDS 12
 #endif
 
 namespace gn {
@@ -158,8 +168,9 @@ struct PlanStreamArgs {
   unsigned long long *pads_out = nullptr;
   const uint32_t *order = nullptr;        // block order of the stream (block_order) or NULL
   // slices == 3 (L1 3072; part, pinfo non-null): the stream runs as three launches over 1,024
-  // columns each (stream_eval_kernel<3072, 3>); part = GN_PART_SLICES x npos x 16 int32 fc_0
-  // partial sums, pinfo = npos (PSQT value, bucket) pairs (written by the plan), npos = n + the
+  // columns each (stream_eval_kernel<3072, 3>); part = GN_PART_SLICES x npos x GN_PART_DWORDS
+  // dwords of fc_0 partial sums, pinfo = npos (PSQT value, bucket) pairs (the plan writes every one:
+  // (0, -1) for a position the big net does not evaluate), npos = n + the
   // children; out_parent / out_child stay unwritten: the caller's launch_finalize takes the big
   // net's outputs from part and pinfo itself (SlicedOut).  Otherwise one launch over whole rows
   int slices = 1;

@@ -832,10 +832,10 @@ __global__ void finalize_kernel(const gn_board *__restrict__ boards, size_t n, i
       }
       // (mode FULL: only the positions the big net evaluates have sums -- the small net's read
       // none; mode BIG: every position, with no load in front of the sums')
-      if (mode == GN_MODE_BIG || (mode == GN_MODE_FULL && need_big[i])) slice_sums<GN_PART_SLICES>(part, npos, q, sums);
+      if (mode == GN_MODE_BIG || (mode == GN_MODE_FULL && need_big[i])) slice_sums<GN_PART_SLICES, GN_PART_DWORDS>(part, npos, q, sums);
     }
     auto big_out = [&](size_t j) -> int2 {
-      return part && info.y >= 0 ? slice_finish_from(bnet, w1s, sums, info) : out_big[j];
+      return part && info.y >= 0 ? slice_finish_from(bnet, GN_PART_DWORDS == 12 ? bnet.b0p : bnet.b0, w1s, sums, info) : out_big[j];
     };
     Board B;
     gn_eval e = {0, 0, 0, 0, 0, 0, 0};

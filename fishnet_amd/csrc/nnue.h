@@ -73,7 +73,35 @@ struct NetDevice {
   const int32_t *b2;
   const int32_t *psqt; // [PSQT_BUCKETS][FT_ROWS]: the rows' PSQT weights by bucket (a copy)
   const int8_t *w0f;   // [8][L1 / 64][64 lanes][16]: w0 in the int8 MFMA's operand order (a copy)
+  // L1 3072 only (else NULL), the column-sliced stream's packed partial sums (kernels.h):
+  const int32_t *part_off; // [8][3 slices][16]: 127 x the sum of max(-w, 0) over the slice's 1,024 fc_0 weights
+  const int32_t *b0p;      // [8][16]: b0 less the three slices' part_off
 };
+
+// The fc_0 inputs of bucket-row (b, o) that column slice s of an L1-wide net covers: for each
+// perspective h the columns h L1 / 2 + s L1 / 6 .. + L1 / 6 - 1 (the net's k-steps 24 h + 8 s ..
+// + 7 for L1 3072, the ones stream.hip's wc_load takes).  part_off / b0p from row-major w0 and b0;
+// false when a row's span 127 sum|w| would not fit 24 bits (it cannot: see kernels.h).
+inline bool part_offsets(const int8_t *w0, const int32_t *b0, int L1, int32_t *part_off, int32_t *b0p) {
+  const int half = L1 / 2, cols = L1 / 6;
+  for (int b = 0; b < LAYER_STACKS; ++b)
+    for (int o = 0; o < 16; ++o) {
+      uint32_t total = 0;
+      for (int s = 0; s < 3; ++s) {
+        uint32_t neg = 0, mag = 0;
+        for (int h = 0; h < 2; ++h)
+          for (int c = 0; c < cols; ++c) {
+            const int w = w0[((size_t)b * 16 + o) * L1 + (size_t)h * half + (size_t)s * cols + c];
+            neg += w < 0 ? (uint32_t)-w : 0u, mag += w < 0 ? (uint32_t)-w : (uint32_t)w;
+          }
+        if (127u * mag >= (1u << 24)) return false;
+        part_off[(b * 3 + s) * 16 + o] = (int32_t)(127u * neg);
+        total += 127u * neg;
+      }
+      b0p[b * 16 + o] = (int32_t)((uint32_t)b0[b * 16 + o] - total);
+    }
+  return true;
+}
 
 // HalfKAv2_hm feature index:
 //   (sq ^ orient) + 64 * plane(piece, perspective) + 704 * king_bucket

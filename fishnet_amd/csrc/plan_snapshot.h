@@ -84,6 +84,12 @@ __attribute__((visibility("default"))) int gn_debug_plan_snapshot(struct gn_ctx 
                                                                   gn_plan_snapshot_header *header,
                                                                   const gn_plan_snapshot_bufs *bufs);
 
+// The loaded big net's tables for the column slices' packed partial sums (nnue.h NetDevice, kernels.h
+// GN_PART_DWORDS), copied from the device: part_off [8 buckets][3 slices][16 outputs] and b0p [8][16]
+// int32.  GN_E_INVALID when the context has no 3072-wide big net.  Internal, as above.
+__attribute__((visibility("default"))) int gn_debug_part_offsets(struct gn_ctx *ctx, int device_slot,
+                                                                 int32_t *part_off, int32_t *b0p);
+
 #ifdef __cplusplus
 }
 #endif

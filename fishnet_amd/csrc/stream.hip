@@ -539,6 +539,12 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
           pinfo[q == 0 ? (uint64_t)p : (uint64_t)np + off + (uint64_t)child_of(q)] =
               make_int2((int32_t)((uint32_t)sv[0] - (uint32_t)sv[1]) / 2, bk | (q == 0 && have ? PINFO_ALIAS | have_ns << PINFO_NS_SH : 0));
       }
+      // ... and every other slot of the parent (not wanted, or the parent is not live) is marked
+      // unevaluated: pinfo.y < 0, which finalize reads as "no big-net output from the sums".  The
+      // plan visits every slot of every parent, so pinfo needs no fill before it
+      // (a parent that is not live has no chained child: child_of is the identity)
+      if (pinfo && in && !(live && vld))
+        pinfo[q == 0 ? (uint64_t)p : (uint64_t)np + off + (uint64_t)child_of(q)] = make_int2(0, -1);
       if (in) {
         // (a chained parent's slot is not evaluated: the child that is its position, bit 6, is)
         *tf(tk0 + tix, offsetof(TileDesc, meta) + t) =
@@ -791,10 +797,11 @@ __global__ void __launch_bounds__(GN_FRONT_WG) __attribute__((amdgpu_waves_per_e
 // every entry of the plan over its own L1 / SL columns (pairs j, j + L1 / 2 of the transform
 // together), so that an XCD's L2 holds the slice's rows of the king buckets in flight (the
 // whole 3072-wide rows of one bucket pair, 8.6 MB, exceed its 4 MB).  A slice's fc_0 sums are
-// partial: every slice stores them (part[slice][position][16], position = the output index:
-// parent P, or np + child) and slice 0 the position's PSQT value and layer-stack bucket
-// (pinfo[position]); finalize_kernel adds the SL sums (wrapping int32 adds, as the LDS
-// atomics: the sum is the whole-row kernel's exactly) and runs the rest of the layer stack.
+// partial: every slice stores them (part[slice][position], position = the output index:
+// parent P, or np + child; a record of 16 biased 24-bit values in 48 B, kernels.h) and the plan
+// the position's PSQT value and layer-stack bucket (pinfo[position]); finalize_kernel adds the
+// SL sums and the corrected bias (wrapping int32 adds, as the LDS atomics: the sum is the
+// whole-row kernel's exactly) and runs the rest of the layer stack.
 // (The last slice finishing in its own launch, one of its two waves per bucket, took 59.6 ms
 // against 49 for the others.)
 template <int L1, int SL = 1>
@@ -829,6 +836,15 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hu = __builtin_amdgcn_readfirstlane((tid / G) & 1);
   for (int i = tid; i < 2 * 16 * AS; i += NT) (&acc0[0][0])[i] = 0;
+  // (packed partial sums, kernels.h) this slice's offsets of the 8 buckets' 16 outputs, staged here,
+  // before the ring's first load: the writer takes its four from LDS (a vector load there would
+  // wait behind the ring's loads in flight, see adj_of); read after the first tile's barrier
+  constexpr bool PACK = SL > 1 && GN_PART_DWORDS == 12;
+  __shared__ __attribute__((aligned(16))) int32_t poff[PACK ? 8 * 16 : 4];
+  if constexpr (PACK) {
+    static_assert(NT == 8 * 16, "one offset per thread");
+    poff[tid] = net.part_off[((tid >> 4) * 3 + slice) * 16 + (tid & 15)];
+  }
   // this launch evaluates blocks [b0, b1).  swz: XCD x (= dispatch index mod 8) takes the x-th
   // contiguous eighth of them; otherwise (default) every workgroup claims the next block of the
   // order with one atomic (claim[0], zeroed per launch), so blocks are taken in order wherever
@@ -1372,11 +1388,26 @@ __global__ void __launch_bounds__(L1 / SL / 8) __attribute__((amdgpu_waves_per_e
           if (present(wp)) {
             const uint64_t q = out_index(wp, adjv);
             int4v v = *src;
-            if (GN_PART_N == 1 && slice > 0) {
+            if constexpr (PACK) {
+              // + the slice's offsets of bucket b: four values in [0, 2^24) (kernels.h), 12 B of the
+              // position's 48-B record.  One asm block ending in a wait state, as the king-cache
+              // stores (a VALU write to the data registers of a > 64-bit store needs one)
+              const int4v o = *reinterpret_cast<const int4v *>(&poff[b * 16 + 4 * wj]);
+              const uint3v pk = pack24x4((uint32_t)(v[0] + o[0]), (uint32_t)(v[1] + o[1]), (uint32_t)(v[2] + o[2]),
+                                         (uint32_t)(v[3] + o[3]));
+              int32_t *dst = part + ((uint64_t)slice * npos + q) * GN_PART_DWORDS + 3 * wj;
+              asm volatile("global_store_dwordx3 %0, %1, off\n\t"
+                           "s_nop 0"
+                           :
+                           : "v"(dst), "v"(pk)
+                           : "memory");
+            } else {
+              if (GN_PART_N == 1 && slice > 0) {
 #pragma unroll
-              for (int k = 0; k < 4; ++k) v[k] = wadd(v[k], pv[k]); // (wrapping, as the LDS atomics)
+                for (int k = 0; k < 4; ++k) v[k] = wadd(v[k], pv[k]); // (wrapping, as the LDS atomics)
+              }
+              *reinterpret_cast<int4v *>(part + ((uint64_t)(GN_PART_N == 1 ? 0 : slice) * npos + q) * 16 + 4 * wj) = v;
             }
-            *reinterpret_cast<int4v *>(part + ((uint64_t)(GN_PART_N == 1 ? 0 : slice) * npos + q) * 16 + 4 * wj) = v;
           }
           *src = int4v{0, 0, 0, 0}; // free for bucket bq + 2
         }
@@ -1511,10 +1542,7 @@ hipError_t launch_plan_stream(const NetDevice &net, const PlanStreamArgs &a, int
   if (net.L1 == 3072) {
     const bool sliced = geo.sliced;
     if (do_plan) {
-      if (sliced) { // (positions the big net does not evaluate keep pinfo.y < 0; the plan writes the rest)
-        hipError_t e = hipMemsetAsync(a.pinfo, 0xFF, a.npos * sizeof(int2), s);
-        if (e != hipSuccess) return e;
-      }
+      // (sliced: the plan writes pinfo for every position, (0, -1) for one the big net does not evaluate)
       hipLaunchKernelGGL((plan_kernel<3072>), dim3(pg), dim3(GN_FRONT_WG), 0, s, net, a.parents, a.offsets, a.deltas,
                          a.need_parent, a.need_child, next_slot, (uint32_t)n, K, B0, B1, kc, a.eoff, a.ent, a.tiles,
                          a.btiles, a.rows_out, a.pads_out, a.err, sliced ? a.pinfo : nullptr, geo.xu, geo.hu);

@@ -139,7 +139,7 @@ extern "C" {
                                          XCD's L2 holds the slice's rows of the king buckets
                                          in flight; 1: one launch over whole rows.  Results
                                          are identical either way.  The slices' fc_0 partial
-                                         sums take 200 B of device memory per evaluated
+                                         sums take 152 B of device memory per evaluated
                                          position (parents + children of a call or chunk);
                                          when that allocation fails the call runs the
                                          whole-row stream instead.                        */
