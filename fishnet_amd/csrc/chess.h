@@ -302,6 +302,63 @@ GN_HD int move_to(uint16_t m) { return m & 63; }
 GN_HD int move_type(uint16_t m) { return m >> 14; }
 GN_HD int move_promo(uint16_t m) { return ((m >> 12) & 3) + KNIGHT; }
 
+// ---- static exchange evaluation (include/gpu_nnue.h at gn_line, "exchange evaluation") ----
+// v(P N B R Q); a king is worth 0.  A 20-byte by-value kernel argument on the device.
+struct SeeValues {
+  int32_t v[5];
+};
+// (a select chain, not an index: the values stay in registers)
+GN_HD int32_t see_value(const SeeValues &V, int pt) {
+  int32_t r = 0;
+#pragma unroll
+  for (int t = PAWN; t <= QUEEN; ++t) r = pt == t ? V.v[t - 1] : r;
+  return r;
+}
+// see(B, m) of the header's rule for a legal move m of B: the classical swap list on m's destination,
+// 0 for castling, en passant and promotions.  No gain array: with s_k the first mover's balance after
+// k captures (s_1 = the captured piece, s_k = s_{k-1} -/+ the piece taken by capture k), the side to
+// make capture k + 1 may stop instead, so the value is min(s_1, max(s_2, min(s_3, ... s_n))) -- the
+// rule's c - R with R = max(0, v - R') written on balances -- and that is clamp(s_n, lo, hi) with each
+// s_k, k < n, folded into the window as it passes: hi = max(lo, min(hi, s_k)) for the second mover's
+// choice (k odd), lo = min(hi, max(lo, s_k)) for the first mover's (k even).  The attackers are those
+// of B as it stands, through occ: taken once in full (the moving piece may have left any line, a pawn
+// its file), then only the line a capturing pawn, bishop, rook or queen leaves is looked at again.
+// A king captures only when the other side has no attacker left, and the exchange ends there.
+GN_HD int32_t see(const Board &B, const Tables &T, uint16_t m, const SeeValues &V) {
+  if (move_type(m) != MT_NORMAL) return 0;
+  const int from = move_from(m), to = move_to(m);
+  const Bitboard diag = B.byType[BISHOP] | B.byType[QUEEN], orth = B.byType[ROOK] | B.byType[QUEEN];
+  Bitboard occ = B.byType[0] & ~sqbb(from);
+  Bitboard att = attackers_to(B, T, to, occ) & occ;
+  int side = B.stm ^ 1;             // the side to capture next
+  int standing = piece_on(B, from) & 7; // the piece that stands on `to` and is taken next
+  int32_t s = see_value(V, piece_on(B, to) & 7), lo = INT32_MIN, hi = INT32_MAX;
+  for (int k = 1; k < 32; ++k) {
+    const Bitboard mine = att & color_bb(B, side);
+    if (!mine) break;
+    int pt = KING;
+    Bitboard ab = mine;
+#pragma unroll
+    for (int t = QUEEN; t >= PAWN; --t) {
+      const Bitboard b = mine & B.byType[t];
+      if (b) pt = t, ab = b;
+    }
+    if (pt == KING && (att & color_bb(B, side ^ 1))) break;
+    if (k & 1) hi = s < hi ? (s > lo ? s : lo) : hi;
+    else lo = s > lo ? (s < hi ? s : hi) : lo;
+    const int32_t v = see_value(V, standing);
+    s = (k & 1) ? s - v : s + v;
+    if (pt == KING) break;
+    standing = pt;
+    occ &= ~(ab & (0 - ab)); // the lowest square of that type
+    if (pt == PAWN || pt == BISHOP || pt == QUEEN) att |= bishop_attacks(T, to, occ) & diag;
+    if (pt == ROOK || pt == QUEEN) att |= rook_attacks(T, to, occ) & orth;
+    att &= occ;
+    side ^= 1;
+  }
+  return s < lo ? lo : (s > hi ? hi : s);
+}
+
 // emit(m) of gen_legal returns void, or bool: true stops the generation (any_legal)
 template <class F>
 GN_HD bool emit_stop(F &emit, uint16_t m) {

@@ -254,9 +254,10 @@ struct EvalBufs {
 // quiescence to `depth` plies, 1..GN_MAX_QUIESCE_DEPTH (the _quiescent calls; check_leaf_rule).
 struct LeafRule {
   enum Kind { STATIC, CHECKS, QUIESCE } kind = STATIC;
-  int depth = 0; // QUIESCE alone
+  int depth = 0;       // QUIESCE alone
+  bool pruned = false; // QUIESCE alone: Qs, the losing captures pruned (GN_OPT_QUIESCE_SEE, read once per call)
   static LeafRule checks() { return {CHECKS, 0}; }
-  static LeafRule quiesce(int depth) { return {QUIESCE, depth}; }
+  static LeafRule quiesce(const gn_ctx *ctx, int depth);
   bool extends() const { return kind != STATIC; } // the call runs the leaf stage, and its ranking takes ext
 };
 struct LeafCount { // one run of the leaf stage: the leaves it valued, the positions evaluated below them
@@ -593,6 +594,7 @@ struct gn_ctx {
   bool king_cache = true;   // GN_OPT_KING_CACHE
   int stream_slices = 3;    // GN_OPT_STREAM_SLICES (3 or 1)
   int64_t chunk_parents = 0; // GN_OPT_CHUNK_PARENTS (0: automatic)
+  bool quiesce_see = false;  // GN_OPT_QUIESCE_SEE
   int l1[2] = {0, 0};
   uint32_t hash[2] = {0, 0};
   double t_parse = 0, t_total = 0; // the last host-buffer expansion call (GN_STAT_HOST_*), ms
@@ -854,6 +856,14 @@ static int check_n_lines(int n_lines) {
   return GN_OK;
 }
 // ... and their leaf rule: the quiescent calls' depth
+LeafRule LeafRule::quiesce(const gn_ctx *ctx, int depth) { return {QUIESCE, depth, ctx && ctx->quiesce_see}; }
+// the context's piece values, as the exchange evaluation takes them
+static SeeValues see_values(const gn_ctx *ctx) {
+  SeeValues V;
+  for (int i = 0; i < 5; ++i) V.v[i] = ctx->P.piece_value[i];
+  return V;
+}
+
 static int check_leaf_rule(LeafRule rule) {
   if (rule.kind == LeafRule::QUIESCE && (rule.depth < 1 || rule.depth > GN_MAX_QUIESCE_DEPTH))
     return fail(GN_E_INVALID, "quiescence depth %d outside 1..%d", rule.depth, GN_MAX_QUIESCE_DEPTH);
@@ -1297,8 +1307,9 @@ static int extend_checks(gn_ctx *ctx, Dev &d, size_t m, int mode, const LeafAllo
 // own moves instead of sharing X.moves, the reduction is quiesce_reduce_pv_kernel, which also leaves
 // each node's chosen child, and quiesce_walk_kernel follows those from every selected leaf into
 // tail (zeroed by the caller), between d.pev[0] and d.pev[1].
+// see (the pruned rule; else NULL): the values the count and children launches prune by.
 static int quiesce(gn_ctx *ctx, Dev &d, const gn_eval *rec, size_t total, size_t m, int mode, int depth,
-                   const LeafAlloc &alloc, size_t *nodes, uint16_t *tail, hipStream_t s) {
+                   const LeafAlloc &alloc, size_t *nodes, uint16_t *tail, hipStream_t s, const SeeValues *see) {
   Dev::LeafStage &X = d.leaf;
   // the levels, top-down: cnt[k] nodes at level k; top: the deepest level whose children were counted
   size_t cnt[GN_MAX_QUIESCE_DEPTH + 2] = {m};
@@ -1309,7 +1320,7 @@ static int quiesce(gn_ctx *ctx, Dev &d, const gn_eval *rec, size_t total, size_t
     LEAF_ALLOC(k, cnt[k], L.counts.ensure(cnt[k] + 1));
     LEAF_ALLOC(k, cnt[k], L.offsets.ensure(cnt[k] + 1));
     LEAF_ALLOC(k, cnt[k], reserve_scan_u64(cnt[k] + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap));
-    if (k) HIP_TRY(launch_quiesce_count(boards, cnt[k], d.tables.p, L.counts.p, s));
+    if (k) HIP_TRY(launch_quiesce_count(boards, cnt[k], d.tables.p, L.counts.p, s, see));
     else HIP_TRY(launch_quiesce_level0_counts(X.sel.p, X.pos.p, X.lcnt.p, total, L.counts.p, s)); // (counted by the selection)
     uint64_t t = 0;
     HIP_TRY(scan_total(d, L.counts.p, L.offsets.p, cnt[k], s, &t));
@@ -1334,7 +1345,7 @@ static int quiesce(gn_ctx *ctx, Dev &d, const gn_eval *rec, size_t total, size_t
     // allocation of the stage can fail as anything but GN_E_NOMEM)
     LEAF_ALLOC(k + 1, t, reserve_eval_outputs(d.cur.eb, t, mode));
     if (king_sorted(ctx, t)) LEAF_ALLOC(k + 1, t, reserve_king_sort_buffers(d, t, mode));
-    HIP_TRY(launch_quiesce_children(boards, cnt[k], d.tables.p, L.offsets.p, t, moves, X.owner.p, N.boards.p, s));
+    HIP_TRY(launch_quiesce_children(boards, cnt[k], d.tables.p, L.offsets.p, t, moves, X.owner.p, N.boards.p, s, see));
     if (int rc = evaluate_on(ctx, d, N.boards.p, t, mode, N.rec.p, s)) return rc;
     *nodes += t;
     boards = N.boards.p;
@@ -1401,6 +1412,7 @@ static int value_leaves(gn_ctx *ctx, Dev &d, const Leaves<Parent, Off> &lv, int 
                     total, rule.depth)
              : fail(GN_E_INVALID, "the check extension supports < 2^31 leaves per call");
   const LeafAlloc alloc{d, rule};
+  const SeeValues values = see_values(ctx), *const see = q && rule.pruned ? &values : nullptr;
   Dev::LeafStage &X = d.leaf;
   if (tail) HIP_TRY(hipMemsetAsync(tail, 0, total * GN_MAX_QUIESCE_DEPTH * sizeof(uint16_t), s));
   LEAF_ALLOC(0, total, X.sel.ensure(total + 1));
@@ -1409,7 +1421,7 @@ static int value_leaves(gn_ctx *ctx, Dev &d, const Leaves<Parent, Off> &lv, int 
     LEAF_ALLOC(0, total, X.lcnt.ensure(total));
     LEAF_ALLOC(0, total, reserve_scan_u64(total + 1, d.cur.scan_tmp.p, d.cur.scan_tmp.cap)); // (the scan then allocates nothing)
     HIP_TRY(hipMemsetAsync(X.sel.p, 0, (total + 1) * sizeof(uint64_t), s));
-    HIP_TRY(launch_quiesce_select(lv.parents, lv.n, lv.offsets, lv.moves, total, d.tables.p, X.sel.p, X.lcnt.p, ext, s));
+    HIP_TRY(launch_quiesce_select(lv.parents, lv.n, lv.offsets, lv.moves, total, d.tables.p, X.sel.p, X.lcnt.p, ext, s, see));
   } else {
     HIP_TRY(launch_extend_select(lv.rec, total, X.sel.p, ext, s));
   }
@@ -1425,7 +1437,7 @@ static int value_leaves(gn_ctx *ctx, Dev &d, const Leaves<Parent, Off> &lv, int 
     LEAF_ALLOC(0, m, X.count.ensure(1));
     HIP_TRY(launch_extend_boards(lv.parents, lv.n, lv.offsets, lv.moves, X.sel.p, X.pos.p, total, d.tables.p, X.idx.p,
                                  X.boards.p, X.sv.p, s));
-    if (int rc = q ? quiesce(ctx, d, lv.rec, total, m, mode, rule.depth, alloc, &below, tail, s)
+    if (int rc = q ? quiesce(ctx, d, lv.rec, total, m, mode, rule.depth, alloc, &below, tail, s, see)
                    : extend_checks(ctx, d, m, mode, alloc, s))
       return rc;
     HIP_TRY(hipMemsetAsync(X.count.p, 0, sizeof(unsigned long long), s));
@@ -2741,7 +2753,7 @@ int gn_evaluate_games_lines_extended(gn_ctx *ctx, const gn_game *games, size_t n
 int gn_evaluate_games_lines_quiescent(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                                       int history, int depth, uint32_t *position_offsets, int32_t *game_status,
                                       gn_eval *position_out, size_t position_cap, gn_line *lines) {
-  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(depth), position_offsets,
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(ctx, depth), position_offsets,
                               game_status, position_out, position_cap, lines);
 }
 
@@ -2749,7 +2761,7 @@ int gn_evaluate_games_lines_quiescent_pv(gn_ctx *ctx, const gn_game *games, size
                                          int history, int depth, uint32_t *position_offsets, int32_t *game_status,
                                          gn_eval *position_out, size_t position_cap, gn_line *lines, gn_pv *pvs) {
   if (n_games && !pvs) return fail(GN_E_INVALID, "pvs is NULL");
-  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(depth), position_offsets,
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(ctx, depth), position_offsets,
                               game_status, position_out, position_cap, lines, pvs);
 }
 
@@ -2777,7 +2789,7 @@ int gn_evaluate_games_lines2_extended(gn_ctx *ctx, const gn_game *games, size_t 
 int gn_evaluate_games_lines2_quiescent(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                                        int history, int depth, uint32_t *position_offsets, int32_t *game_status,
                                        gn_eval *position_out, size_t position_cap, gn_line2 *lines) {
-  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(depth), position_offsets,
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(ctx, depth), position_offsets,
                               game_status, position_out, position_cap, lines);
 }
 
@@ -2785,7 +2797,7 @@ int gn_evaluate_games_lines2_quiescent_pv(gn_ctx *ctx, const gn_game *games, siz
                                           int history, int depth, uint32_t *position_offsets, int32_t *game_status,
                                           gn_eval *position_out, size_t position_cap, gn_line2 *lines, gn_pv *pvs) {
   if (n_games && !pvs) return fail(GN_E_INVALID, "pvs is NULL");
-  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(depth), position_offsets,
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history != 0, LeafRule::quiesce(ctx, depth), position_offsets,
                               game_status, position_out, position_cap, lines, pvs);
 }
 
@@ -3299,7 +3311,7 @@ int gn_quiesce_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, s
                       const uint16_t *d_moves, const gn_eval *d_rec, size_t total, int mode, int depth, int32_t *d_ext,
                       size_t *searched, size_t *nodes, void *stream) {
   return value_leaves_call(ctx, device_slot, PackedLeaves{d_parents, n, d_offsets, d_moves, d_rec, total}, mode,
-                           LeafRule::quiesce(depth), d_ext, searched, nodes, stream);
+                           LeafRule::quiesce(ctx, depth), d_ext, searched, nodes, stream);
 }
 
 int gn_quiesce_pv_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
@@ -3307,7 +3319,38 @@ int gn_quiesce_pv_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents
                          uint16_t *d_tail, size_t *searched, size_t *nodes, void *stream) {
   if (total && !d_tail) return fail(GN_E_INVALID, "d_tail is NULL");
   return value_leaves_call(ctx, device_slot, PackedLeaves{d_parents, n, d_offsets, d_moves, d_rec, total}, mode,
-                           LeafRule::quiesce(depth), d_ext, searched, nodes, stream, d_tail);
+                           LeafRule::quiesce(ctx, depth), d_ext, searched, nodes, stream, d_tail);
+}
+
+// The exchange evaluation by itself (include/gpu_nnue.h at gn_line, "exchange evaluation"): the
+// host form runs chess.h's see() on the host tables, the device form see_moves_kernel.
+int gn_see_moves(const gn_board *boards, size_t n, const uint16_t *moves, const int32_t *piece_value, int32_t *out) {
+  if (n && (!boards || !moves || !out)) return fail(GN_E_INVALID, "NULL buffer");
+  SeeValues V;
+  const gn_eval_params defaults = default_params();
+  for (int i = 0; i < 5; ++i) V.v[i] = piece_value ? piece_value[i] : defaults.piece_value[i];
+  const Tables &T = host_tables();
+  for (size_t i = 0; i < n; ++i) {
+    out[i] = GN_NOT_EXTENDED;
+    Board B;
+    if (!unpack(boards[i], B, T)) continue;
+    const uint16_t m = moves[i];
+    bool legal = false;
+    gen_legal(B, T, [&](uint16_t x) { return legal = x == m; });
+    if (legal) out[i] = see(B, T, m, V);
+  }
+  return GN_OK;
+}
+
+int gn_see_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
+                  const uint16_t *d_moves, size_t total, int32_t *d_see, void *stream) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
+  if (total && (!d_parents || !d_offsets || !d_moves || !d_see)) return fail(GN_E_INVALID, "NULL buffer");
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_see_moves(d_parents, n, d_offsets, d_moves, total, d->tables.p, see_values(ctx), d_see, call.s));
+  return GN_OK;
 }
 
 // gn_line_pvs_device / gn_line2_pvs_device: checked as the ranking calls are (rank_call_args, without
@@ -3596,6 +3639,12 @@ int gn_random_games_device(gn_ctx *ctx, int device_slot, uint64_t seed, size_t f
 
 int gn_set_option(gn_ctx *ctx, int option, int64_t value) {
   if (!ctx) return fail(GN_E_INVALID, "ctx is NULL");
+  if (option == GN_OPT_QUIESCE_SEE) { // stored before the generation moves; a bad value changes nothing
+    if (value != 0 && value != 1) return fail(GN_E_INVALID, "GN_OPT_QUIESCE_SEE %lld not 0 or 1", (long long)value);
+    ctx->quiesce_see = value != 0;
+    ++ctx->graph_gen;
+    return GN_OK;
+  }
   ++ctx->graph_gen; // (the small-batch graphs hold the options they were captured with)
   switch (option) {
   case GN_OPT_INCREMENTAL_CHILDREN:
@@ -3670,6 +3719,9 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
     return GN_OK;
   case GN_OPT_EXPAND_PIPELINE:
     *value = ctx->pipeline;
+    return GN_OK;
+  case GN_OPT_QUIESCE_SEE:
+    *value = ctx->quiesce_see;
     return GN_OK;
   case GN_STAT_FAST_BATCHES:
     *value = (int64_t)ctx->fast_runs.load();
@@ -3905,13 +3957,13 @@ int gn_evaluate_lines2_extended(gn_ctx *ctx, const char *const *fens, size_t n, 
 
 int gn_evaluate_lines2_quiescent(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, int depth,
                                  gn_eval *out, gn_line2 *lines) {
-  return evaluate_lines2(ctx, fens, n, mode, n_lines, LeafRule::quiesce(depth), out, lines);
+  return evaluate_lines2(ctx, fens, n, mode, n_lines, LeafRule::quiesce(ctx, depth), out, lines);
 }
 
 int gn_evaluate_lines2_quiescent_pv(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, int depth,
                                     gn_eval *out, gn_line2 *lines, gn_pv *pvs) {
   if (n && !pvs) return fail(GN_E_INVALID, "pvs is NULL");
-  return evaluate_lines2(ctx, fens, n, mode, n_lines, LeafRule::quiesce(depth), out, lines, pvs);
+  return evaluate_lines2(ctx, fens, n, mode, n_lines, LeafRule::quiesce(ctx, depth), out, lines, pvs);
 }
 
 int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {

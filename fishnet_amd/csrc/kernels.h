@@ -347,18 +347,27 @@ hipError_t launch_extend_scatter(const uint32_t *idx, const int32_t *sv, size_t 
 // moves, their owners and boards at offsets (the scan of counts), at most nc.  reduce: val[i] of the
 // m nodes from their records (rec[idx[i]] with idx: level 0's child records) and their children's
 // values cval, or with cval NULL the children's static part from their position records crec.
+// see (select, count, children; NULL: unpruned): the piece values of the pruned rule Qs
+// (GN_OPT_QUIESCE_SEE): a node not in check searches only its noisy moves with see >= 0; the pruned
+// forms are kernels of their own.
 hipError_t launch_quiesce_select(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
                                  size_t total, const Tables *tables, uint64_t *sel, uint32_t *lcnt, int32_t *ext,
-                                 hipStream_t s);
+                                 hipStream_t s, const SeeValues *see);
 hipError_t launch_quiesce_select(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
                                  size_t total, const Tables *tables, uint64_t *sel, uint32_t *lcnt, int32_t *ext,
-                                 hipStream_t s);
+                                 hipStream_t s, const SeeValues *see);
+// gn_see_device: out[j] = see(parent of j, moves[j]) where a valid parent's offsets cover j,
+// GN_NOT_EXTENDED for every other j < total (a 32-bit fill, then see_moves_kernel)
+hipError_t launch_see_moves(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves, size_t total,
+                            const Tables *tables, const SeeValues &V, int32_t *out, hipStream_t s);
 // level 0's counts (m + 1, m = pos[total]) compacted from the selection pass's per-leaf lcnt
 hipError_t launch_quiesce_level0_counts(const uint64_t *sel, const uint64_t *pos, const uint32_t *lcnt, size_t total,
                                         uint64_t *counts, hipStream_t s);
-hipError_t launch_quiesce_count(const gn_board *boards, size_t n, const Tables *tables, uint64_t *counts, hipStream_t s);
+hipError_t launch_quiesce_count(const gn_board *boards, size_t n, const Tables *tables, uint64_t *counts, hipStream_t s,
+                                const SeeValues *see);
 hipError_t launch_quiesce_children(const gn_board *boards, size_t n, const Tables *tables, const uint64_t *offsets,
-                                   size_t nc, uint16_t *moves, uint32_t *owner, gn_board *children, hipStream_t s);
+                                   size_t nc, uint16_t *moves, uint32_t *owner, gn_board *children, hipStream_t s,
+                                   const SeeValues *see);
 hipError_t launch_quiesce_reduce(const gn_eval *rec, const uint32_t *idx, size_t m, const uint64_t *off, size_t nc,
                                  const gn_eval *crec, const int32_t *cval, int32_t *val, hipStream_t s);
 // The quiescence's own variation (the rule at gn_pv in include/gpu_nnue.h).  reduce_pv: reduce, plus

@@ -2176,6 +2176,16 @@ __device__ __forceinline__ void gen_searched(const Board &B, const Tables &T, F 
     return false;
   });
 }
+// ... and under GN_OPT_QUIESCE_SEE (rule 4s): a node that is not in check keeps only the noisy moves
+// whose exchange does not lose, see(B, m) >= 0 with the context's piece values V.
+template <class F>
+__device__ __forceinline__ void gen_searched(const Board &B, const Tables &T, F &&emit, const SeeValues &V) {
+  const bool check = in_check(B, T);
+  gen_legal(B, T, [&](uint16_t m) {
+    if (check || (noisy_move(B, m) && see(B, T, m, V) >= 0)) return emit_stop(emit, m);
+    return false;
+  });
+}
 
 // Level 0's selection, shaped like extend_boards_kernel: a 32-lane group per parent, a lane per
 // leaf, the parent unpacked once (through the gate when it is a caller's board).  ext[j] =
@@ -2212,6 +2222,38 @@ __global__ void __launch_bounds__(RANK_WG)
     }
   }
 }
+// The pruned rule's selection (GN_OPT_QUIESCE_SEE): the same kernel with the pruned filter, so a leaf
+// is searched when it is in check with a legal move or has a kept move, and lcnt counts the kept
+// moves.  This and the two _see kernels below are siblings, not a shared body: the unpruned kernels
+// keep their code and registers (a body shared through a function moved quiesce_count_kernel from 78
+// to 88 VGPRs).
+template <class Parent, class Off>
+__global__ void __launch_bounds__(RANK_WG)
+    quiesce_select_see_kernel(const Parent *__restrict__ parents, size_t n, const Off *__restrict__ offsets,
+                              const uint16_t *__restrict__ moves, size_t total, const Tables *__restrict__ tables,
+                              uint64_t *__restrict__ sel, uint32_t *__restrict__ lcnt, int32_t *__restrict__ ext,
+                              const SeeValues V) {
+  __shared__ Tables T;
+  load_tables(T, tables);
+  constexpr int W = 32;
+  const int lane = threadIdx.x & (W - 1);
+  const size_t stride = (size_t)gridDim.x * (RANK_WG / W);
+  for (size_t j = (size_t)blockIdx.x * RANK_WG + threadIdx.x; j < total; j += (size_t)gridDim.x * RANK_WG)
+    ext[j] = GN_NOT_EXTENDED;
+  for (size_t p = (size_t)blockIdx.x * (RANK_WG / W) + threadIdx.x / W; p < n; p += stride) {
+    const uint64_t c1 = std::min<uint64_t>(offsets[p + 1], total), c0 = std::min<uint64_t>(offsets[p], c1);
+    if (c0 >= c1) continue;
+    Board B;
+    if (!rank_parent(parents[p], B, T)) continue;
+    for (uint64_t c = c0 + lane; c < c1; c += W) {
+      const Board C = do_move(B, moves[c], nullptr);
+      uint32_t k = 0;
+      gen_searched(C, T, [&](uint16_t) { ++k; }, V);
+      lcnt[c] = k;
+      if (k) sel[c] = 1;
+    }
+  }
+}
 // level 0's counts from the selection pass: counts[pos[c]] = lcnt[c] for a selected leaf c,
 // counts[pos[total]] = 0 (the scan's end)
 __global__ void quiesce_level0_counts_kernel(const uint64_t *__restrict__ sel, const uint64_t *__restrict__ pos,
@@ -2236,6 +2278,17 @@ __global__ void quiesce_count_kernel(const gn_board *__restrict__ boards, size_t
   if (i < n && unpack_fields(boards[i], B)) gen_searched(B, T, [&](uint16_t) { ++c; });
   counts[i] = c;
 }
+__global__ void quiesce_count_see_kernel(const gn_board *__restrict__ boards, size_t n, const Tables *__restrict__ tables,
+                                         uint64_t *__restrict__ counts, const SeeValues V) {
+  __shared__ Tables T;
+  load_tables(T, tables);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  uint64_t c = 0;
+  Board B;
+  if (i < n && unpack_fields(boards[i], B)) gen_searched(B, T, [&](uint16_t) { ++c; }, V);
+  counts[i] = c;
+}
 
 // ... and their moves and owners at offsets[i] (the scan of counts), clamped to the nc children the
 // next level was sized for; child_boards_kernel then makes the boards.
@@ -2253,6 +2306,44 @@ __global__ void quiesce_moves_kernel(const gn_board *__restrict__ boards, size_t
     if (k < nc) moves[k] = m, owner[k] = (uint32_t)i;
     ++k;
   });
+}
+__global__ void quiesce_moves_see_kernel(const gn_board *__restrict__ boards, size_t n, const Tables *__restrict__ tables,
+                                         const uint64_t *__restrict__ offsets, size_t nc, uint16_t *__restrict__ moves,
+                                         uint32_t *__restrict__ owner, const SeeValues V) {
+  __shared__ Tables T;
+  load_tables(T, tables);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Board B;
+  if (!unpack_fields(boards[i], B)) return;
+  uint64_t k = offsets[i];
+  gen_searched(B, T, [&](uint16_t m) {
+    if (k < nc) moves[k] = m, owner[k] = (uint32_t)i;
+    ++k;
+  }, V);
+}
+
+// d_see of gn_see_device, shaped like quiesce_select_kernel: a 32-lane group per parent, a lane per
+// move: out[c] = see(parent, moves[c]) for the moves its offsets cover, clamped to total.  A parent goes
+// through the gate; a rejected one's moves, and the entries no offsets cover, keep the GN_NOT_EXTENDED
+// the launcher filled out with before this kernel (a fill inside it, as quiesce_select_kernel's of
+// ext, would race with another workgroup's values: here the values are written by the same kernel).
+__global__ void __launch_bounds__(RANK_WG)
+    see_moves_kernel(const gn_board *__restrict__ parents, size_t n, const uint32_t *__restrict__ offsets,
+                     const uint16_t *__restrict__ moves, size_t total, const Tables *__restrict__ tables,
+                     const SeeValues V, int32_t *__restrict__ out) {
+  __shared__ Tables T;
+  load_tables(T, tables);
+  constexpr int W = 32;
+  const int lane = threadIdx.x & (W - 1);
+  const size_t stride = (size_t)gridDim.x * (RANK_WG / W);
+  for (size_t p = (size_t)blockIdx.x * (RANK_WG / W) + threadIdx.x / W; p < n; p += stride) {
+    const uint64_t c1 = std::min<uint64_t>(offsets[p + 1], total), c0 = std::min<uint64_t>(offsets[p], c1);
+    if (c0 >= c1) continue;
+    Board B;
+    if (!unpack(parents[p], B, T)) continue;
+    for (uint64_t c = c0 + lane; c < c1; c += W) out[c] = see(B, T, moves[c], V);
+  }
 }
 
 // One level of the reduction, a lane per node i (rules 1 to 4): its record r (rec[idx[i]] with idx,
@@ -2291,23 +2382,38 @@ __global__ void quiesce_reduce_kernel(const gn_eval *__restrict__ rec, const uin
 
 template <class Parent, class Off>
 static hipError_t quiesce_select_t(const Parent *parents, size_t n, const Off *offsets, const uint16_t *moves, size_t total,
-                                   const Tables *tables, uint64_t *sel, uint32_t *lcnt, int32_t *ext, hipStream_t s) {
+                                   const Tables *tables, uint64_t *sel, uint32_t *lcnt, int32_t *ext, hipStream_t s,
+                                   const SeeValues *see) {
   if (!n) return hipSuccess;
   constexpr size_t per_wg = RANK_WG / 32, max_blocks = 8192;
   const size_t blocks = std::min<size_t>((n + per_wg - 1) / per_wg, max_blocks);
-  hipLaunchKernelGGL((quiesce_select_kernel<Parent, Off>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets, moves,
-                     total, tables, sel, lcnt, ext);
+  if (see)
+    hipLaunchKernelGGL((quiesce_select_see_kernel<Parent, Off>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n,
+                       offsets, moves, total, tables, sel, lcnt, ext, *see);
+  else
+    hipLaunchKernelGGL((quiesce_select_kernel<Parent, Off>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets, moves,
+                       total, tables, sel, lcnt, ext);
   return hipGetLastError();
 }
 hipError_t launch_quiesce_select(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
                                  size_t total, const Tables *tables, uint64_t *sel, uint32_t *lcnt, int32_t *ext,
-                                 hipStream_t s) {
-  return quiesce_select_t(unpacked, n, offsets, moves, total, tables, sel, lcnt, ext, s);
+                                 hipStream_t s, const SeeValues *see) {
+  return quiesce_select_t(unpacked, n, offsets, moves, total, tables, sel, lcnt, ext, s, see);
 }
 hipError_t launch_quiesce_select(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
                                  size_t total, const Tables *tables, uint64_t *sel, uint32_t *lcnt, int32_t *ext,
-                                 hipStream_t s) {
-  return quiesce_select_t(parents, n, offsets, moves, total, tables, sel, lcnt, ext, s);
+                                 hipStream_t s, const SeeValues *see) {
+  return quiesce_select_t(parents, n, offsets, moves, total, tables, sel, lcnt, ext, s, see);
+}
+hipError_t launch_see_moves(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves, size_t total,
+                            const Tables *tables, const SeeValues &V, int32_t *out, hipStream_t s) {
+  if (!total) return hipSuccess;
+  if (hipError_t e = hipMemsetD32Async((hipDeviceptr_t)out, (int)GN_NOT_EXTENDED, total, s)) return e;
+  if (!n) return hipSuccess;
+  constexpr size_t per_wg = RANK_WG / 32, max_blocks = 8192;
+  const size_t blocks = std::min<size_t>((n + per_wg - 1) / per_wg, max_blocks);
+  hipLaunchKernelGGL(see_moves_kernel, dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets, moves, total, tables, V, out);
+  return hipGetLastError();
 }
 hipError_t launch_quiesce_level0_counts(const uint64_t *sel, const uint64_t *pos, const uint32_t *lcnt, size_t total,
                                         uint64_t *counts, hipStream_t s) {
@@ -2315,16 +2421,26 @@ hipError_t launch_quiesce_level0_counts(const uint64_t *sel, const uint64_t *pos
                      counts);
   return hipGetLastError();
 }
-hipError_t launch_quiesce_count(const gn_board *boards, size_t n, const Tables *tables, uint64_t *counts, hipStream_t s) {
-  hipLaunchKernelGGL(quiesce_count_kernel, dim3(blocks_for(n + 1, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, n, tables,
-                     counts);
+hipError_t launch_quiesce_count(const gn_board *boards, size_t n, const Tables *tables, uint64_t *counts, hipStream_t s,
+                                const SeeValues *see) {
+  if (see)
+    hipLaunchKernelGGL(quiesce_count_see_kernel, dim3(blocks_for(n + 1, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, n,
+                       tables, counts, *see);
+  else
+    hipLaunchKernelGGL(quiesce_count_kernel, dim3(blocks_for(n + 1, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, n,
+                       tables, counts);
   return hipGetLastError();
 }
 hipError_t launch_quiesce_children(const gn_board *boards, size_t n, const Tables *tables, const uint64_t *offsets,
-                                   size_t nc, uint16_t *moves, uint32_t *owner, gn_board *children, hipStream_t s) {
+                                   size_t nc, uint16_t *moves, uint32_t *owner, gn_board *children, hipStream_t s,
+                                   const SeeValues *see) {
   if (!n || !nc) return hipSuccess;
-  hipLaunchKernelGGL(quiesce_moves_kernel, dim3(blocks_for(n, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, n, tables,
-                     offsets, nc, moves, owner);
+  if (see)
+    hipLaunchKernelGGL(quiesce_moves_see_kernel, dim3(blocks_for(n, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, n,
+                       tables, offsets, nc, moves, owner, *see);
+  else
+    hipLaunchKernelGGL(quiesce_moves_kernel, dim3(blocks_for(n, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, n, tables,
+                       offsets, nc, moves, owner);
   hipLaunchKernelGGL(child_boards_kernel, dim3(blocks_for(nc, GN_FRONT_WG)), dim3(GN_FRONT_WG), 0, s, boards, (size_t)0, nc,
                      moves, owner, children, (ChildDelta *)nullptr, (unsigned long long *)nullptr, (const Board *)nullptr);
   return hipGetLastError();

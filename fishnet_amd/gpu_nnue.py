@@ -71,9 +71,11 @@ EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_
            "gn_quiesce_device", "gn_evaluate_lines2_quiescent", "gn_evaluate_games_lines2_quiescent",
            "gn_evaluate_games_lines_quiescent",
            "gn_quiesce_pv_device", "gn_line_pvs_device", "gn_line2_pvs_device", "gn_evaluate_lines2_quiescent_pv",
-           "gn_evaluate_games_lines2_quiescent_pv", "gn_evaluate_games_lines_quiescent_pv"]
+           "gn_evaluate_games_lines2_quiescent_pv", "gn_evaluate_games_lines_quiescent_pv",
+           "gn_see_moves", "gn_see_device"]
 OPT_INCREMENTAL_CHILDREN, OPT_XCD_SWIZZLE, OPT_KING_SORT, OPT_CHAIN, OPT_KING_CACHE = 1, 2, 3, 4, 5
 OPT_CHUNK_PARENTS, OPT_COALESCE, OPT_STREAM_SLICES, OPT_FAST_BATCH, OPT_EXPAND_PIPELINE = 6, 7, 8, 9, 10
+OPT_QUIESCE_SEE = 11  # 1: the quiescent calls prune the noisy moves with see < 0 (the one option that changes results)
 STAT_PLAN_NS, STAT_STREAM_NS, STAT_SCRATCH_PADS, STAT_FINISH_NS = 101, 102, 103, 104
 STAT_ZERO_ROW_ENTRIES = 105
 STAT_BATCH_LAUNCHES, STAT_BATCH_CALLS, STAT_FAST_BATCHES, STAT_FAST_FALLBACKS = 117, 118, 119, 120
@@ -224,6 +226,8 @@ def lib():
         "gn_evaluate_lines2_quiescent_pv": [vp, vp, sz, i32, i32, i32, vp, vp, vp],
         "gn_evaluate_games_lines2_quiescent_pv": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp, vp],
         "gn_evaluate_games_lines_quiescent_pv": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp, vp],
+        "gn_see_moves": [vp, sz, vp, vp, vp],
+        "gn_see_device": [vp, i32, vp, sz, vp, vp, sz, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -285,6 +289,21 @@ def position_keys(boards) -> np.ndarray:
     keys = np.zeros(len(b), dtype=np.uint64)
     _check(lib().gn_position_keys(b.ctypes.data, len(b), keys.ctypes.data))
     return keys
+
+
+def see_moves(boards, moves, piece_value=None) -> np.ndarray:
+    """gn_see_moves: see(boards[i], moves[i]) as int32 (the rule in gpu_nnue.h at gn_line, "exchange
+    evaluation"); NOT_EXTENDED for a rejected board or a move that is not legal there.  piece_value: the
+    five values P N B R Q, None: the defaults.  Host only."""
+    b = np.ascontiguousarray(np.asarray(boards, dtype=BOARD_DTYPE).reshape(-1))
+    m = np.ascontiguousarray(np.asarray(moves, dtype=np.uint16).reshape(-1))
+    if len(b) != len(m):
+        raise ValueError("one move per board")
+    pv = None if piece_value is None else np.ascontiguousarray(np.asarray(piece_value, dtype=np.int32).reshape(5))
+    out = np.zeros(len(b), dtype=np.int32)
+    _check(lib().gn_see_moves(b.ctypes.data, len(b), m.ctypes.data, None if pv is None else pv.ctypes.data,
+                              out.ctypes.data))
+    return out
 
 
 def replay_game(root_fen: str, moves, skip=()):
@@ -772,6 +791,13 @@ class GpuNnue:
         _check(lib().gn_quiesce_device(self.h, slot, p(d_parents), n, p(d_offsets), p(d_moves), p(d_rec), total, mode,
                                        depth, p(d_ext), C.byref(ns), C.byref(nn), stream))
         return ns.value, nn.value
+
+    def see_device(self, d_parents, n, d_offsets, d_moves, total, d_see, stream=None, slot=0):
+        """gn_see_device: d_see[total] (int32) = see(parent, move) of every move of a preceding expansion
+        level with the context's piece values, NOT_EXTENDED where no valid parent's offsets cover the
+        entry.  Asynchronous.  The buffers may be None when total is 0."""
+        p = lambda b: b.ptr if b is not None else None
+        _check(lib().gn_see_device(self.h, slot, p(d_parents), n, p(d_offsets), p(d_moves), total, p(d_see), stream))
 
     def quiesce_pv_device(self, d_parents, n, d_offsets, d_moves, d_rec, total, mode, depth, d_ext, d_tail, stream=None,
                           slot=0):

@@ -97,6 +97,16 @@ extern "C" {
                                          stream still runs (151.3 against 153.9 ms per bench
                                          step unpipelined); 0: one after another.  Results
                                          are identical for every value.                     */
+#define GN_OPT_QUIESCE_SEE 11         /* 0 (default): the quiescent calls search every noisy
+                                         move (Q / PVQ at gn_line).  1: gn_quiesce_device,
+                                         gn_quiesce_pv_device and the six _quiescent /
+                                         _quiescent_pv host-buffer calls follow Qs / PVQs: a
+                                         node that is not in check searches only its noisy
+                                         moves with see >= 0 (gn_line, "exchange
+                                         evaluation").  Read once when a call starts; no
+                                         other call reads it.  Any other value:
+                                         GN_E_INVALID, the option unchanged.  This is the one
+                                         option whose values give DIFFERENT results.        */
 #define GN_OPT_INCREMENTAL_CHILDREN 1 /* 1 (default): children from the parent accumulators
                                          by add/sub deltas; 0: full refresh per child    */
 #define GN_OPT_XCD_SWIZZLE 2          /* bit mask, default 9: each XCD takes a contiguous
@@ -384,7 +394,43 @@ typedef struct gn_child {
  * plies == 1, else [move, reply], followed by PVQ(grandchild, depth) exactly when plies == 2 and
  * the line carries GN_FLAG_SEARCHED.  A leaf the ranking values as mate, as stalemate or, in the
  * history forms, as drawn by rule has no tail, even where the quiescence searched it: such a line
- * never carries GN_FLAG_SEARCHED.  The check extension's replies are not reported. */
+ * never carries GN_FLAG_SEARCHED.  The check extension's replies are not reported.
+ *
+ * Exchange evaluation (gn_see_moves, gn_see_device, GN_OPT_QUIESCE_SEE).  see(x, m) is an int32_t,
+ * defined for a position x that passes the gate (gn_board) and a legal move m of x: the classical swap
+ * list on m's destination.  v(P N B R Q) = gn_eval_params.piece_value[0..4] (the host call takes them
+ * as an argument; NULL: the defaults 208 781 825 1276 2538); v(K) = 0.
+ *   - m is castling, an en-passant capture or a promotion (capturing or not): see = 0 (Stockfish's
+ *     convention for non-normal moves).
+ *   - Otherwise, with `to` m's destination, P0 the type of the moving piece, occ0 the occupancy of x
+ *     without m's origin square and c = v(type of the piece on `to`), 0 when `to` is empty:
+ *     see = c - R(P0, occ0, the side that did not move).
+ *   - R(P, occ, s).  A = the pieces of x, as they stand in x, that are in occ and attack `to` with
+ *     occupancy occ: a pawn by its colour's capture direction, knights and kings by their steps, a
+ *     bishop, rook or queen along its lines with occ as the blockers (so a slider behind a piece that
+ *     has left occ counts).  The piece that moved is not in occ, and `to` is never in A.
+ *       If A holds no piece of side s: R = 0.  Otherwise a = s's piece in A of the lowest type in the
+ *       order P, N, B, R, Q, K (by type, never by the configured values), among those the one on the
+ *       lowest square index.
+ *       a is a king and A holds a piece of the other side: R = 0 (a king does not capture onto an
+ *       attacked square; the same A, not a recomputed one).
+ *       a is a king and A holds no piece of the other side: R = max(0, v(P)), and the exchange ends.
+ *       Otherwise R = max(0, v(P) - R(type(a), occ without a's square, the other side)).
+ * Pins are ignored, and a pawn that recaptures on a back rank stays a pawn.  Arithmetic is int32; the
+ * result is defined while 32 * max|piece_value| < 2^31.  see is NOT invariant under the board
+ * symmetries: between two attackers of one type the lower square captures first.
+ * Pruned quiescence.  Qs(x, d) is Q(x, d) with rule 4 replaced by
+ *   4s. otherwise max(final_v(x), the maximum over the noisy legal moves m with see(x, m) >= 0 of
+ *       negate_ply(Qs(child, d - 1))).
+ * Rules 1 to 3 stand: a node in check searches every legal move.  A kept move is a noisy legal move
+ * with see >= 0; a leaf is searched when it has a legal move and is in check, or has a kept move.  A
+ * leaf whose noisy moves all lose keeps GN_NOT_EXTENDED: its line carries no GN_FLAG_SEARCHED and
+ * takes the static value.  PVQs is PVQ over the kept moves.  The ranking's precedence, the history
+ * forms, negate_ply, the score rule, the ties and the empty lines are unchanged, and the searched /
+ * nodes counts and GN_STAT_QUIESCE_* count the pruned tree.  Consequences: Qs(x, 1) <= Q(x, 1) for a
+ * leaf not in check (no inequality holds from depth 2 on: pruning the opponent's moves raises a
+ * value); the nodes under pruning are at most those without it; and a position below none of whose
+ * searched leaves a noisy legal move loses has byte-equal results with and without pruning. */
 #define GN_NOT_EXTENDED INT32_MIN /* a d_ext entry of a leaf the extension / quiescence does not value */
 #define GN_MAX_QUIESCE_DEPTH 4    /* the quiescent calls' depth is 1..GN_MAX_QUIESCE_DEPTH */
 #define GN_MAX_PV (2 + GN_MAX_QUIESCE_DEPTH) /* a line's two moves and the quiescence's own */
@@ -959,6 +1005,23 @@ GN_API int gn_quiesce_pv_device(gn_ctx *ctx, int device_slot, const gn_board *d_
                                 const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_rec, size_t total,
                                 int mode, int depth, int32_t *d_ext, uint16_t *d_tail, size_t *searched, size_t *nodes,
                                 void *stream);
+/* The exchange evaluation of a list of moves (the rule at gn_line, "exchange evaluation"), on the
+ * host and without a context: out[i] = see(boards[i], moves[i]) with the values piece_value[0..4]
+ * (P N B R Q; NULL: the defaults).  Each board goes through the gate; a rejected board, or a move
+ * that is not legal there, gives GN_NOT_EXTENDED in out[i], and the call still returns GN_OK.
+ * n == 0: GN_OK, the buffers may be NULL; a NULL buffer otherwise: GN_E_INVALID. */
+GN_API int gn_see_moves(const gn_board *boards, size_t n, const uint16_t *moves, const int32_t *piece_value,
+                        int32_t *out);
+/* ... and of one expansion level on the device: inputs as gn_quiesce_device takes them (a preceding
+ * gn_expand_device, or level 2 of gn_expand2_device with the children as parents).  d_see[j] (total
+ * entries) = see(parent of j, d_moves[j]) with the context's piece values (gn_set_eval_params) for
+ * every j a parent's offsets cover, GN_NOT_EXTENDED for every other j < total and for the moves of a
+ * parent the gate rejects.  Offsets are clamped to total; the moves are taken as legal.  Asynchronous
+ * on `stream` (NULL = the context's own), no read-back.  total == 0: GN_OK, the buffers may be NULL;
+ * a NULL buffer with total > 0: GN_E_INVALID. */
+GN_API int gn_see_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                         const uint32_t *d_offsets, const uint16_t *d_moves, size_t total, int32_t *d_see,
+                         void *stream);
 /* d_pvs[i * n_lines + k] = the gn_pv of d_lines[i * n_lines + k], the lines a ranking call wrote for
  * the same expansion (d_offsets, d_moves as gn_expand_device wrote them) and d_tail as
  * gn_quiesce_pv_device wrote it for the level the ranking took d_ext from; d_tail == NULL: no tails

@@ -440,6 +440,14 @@ impl GpuNnue {
         Ok((offsets, status, evals, lines, pvs))
     }
 
+    /// GN_OPT_QUIESCE_SEE: with `true` the quiescent calls above prune the noisy moves whose exchange
+    /// loses (see < 0; include/gpu_nnue.h at gn_line, "exchange evaluation").  The one option that
+    /// changes results; off by default.
+    pub fn set_quiesce_see(&self, on: bool) -> Result<(), GpuError> {
+        // SAFETY: the context is live; the call only stores the value.
+        check(unsafe { sys::gn_set_option(self.0, sys::GN_OPT_QUIESCE_SEE, i64::from(on)) })
+    }
+
     /// Whole acquired batches: replay root FEN + UCI moves (skipPositions honoured) and
     /// evaluate every position and every legal child; buffers grow on GN_E_CAPACITY.
     pub fn evaluate_games(&self, games: &[(CString, CString, Vec<u32>)], mode: i32) -> Result<GamesResult, GpuError> {
@@ -502,6 +510,20 @@ fn games_and_capacity(games: &[(CString, CString, Vec<u32>)]) -> (Vec<sys::gn_ga
         .collect();
     let cap = games.iter().map(|(_, m, _)| m.as_bytes().split(|&b| b == b' ').filter(|t| !t.is_empty()).count() + 1).sum();
     (gs, cap)
+}
+
+/// The exchange evaluation of moves[i] on boards[i] (gn_see_moves; host only): what a CPU search
+/// orders its captures by.  piece_value: P N B R Q, None: the defaults.  An entry of i32::MIN
+/// (GN_NOT_EXTENDED) marks a rejected board or a move that is not legal there.
+pub fn see_moves(boards: &[sys::gn_board], moves: &[u16], piece_value: Option<&[i32; 5]>) -> Result<Vec<i32>, GpuError> {
+    assert_eq!(boards.len(), moves.len());
+    let mut out = vec![0i32; boards.len()];
+    // SAFETY: boards, moves and out have the same length; piece_value is 5 values or NULL.
+    check(unsafe {
+        sys::gn_see_moves(boards.as_ptr(), boards.len(), moves.as_ptr(),
+                          piece_value.map_or(ptr::null(), |p| p.as_ptr()), out.as_mut_ptr())
+    })?;
+    Ok(out)
 }
 
 /// A move in Stockfish's 16-bit encoding (gn_eval.best_move, child_moves) as the Chess960 UCI

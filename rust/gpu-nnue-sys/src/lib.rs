@@ -27,7 +27,7 @@ pub const GN_MODE_FULL: c_int = 0;
 pub const GN_MODE_BIG: c_int = 1;
 pub const GN_MODE_SMALL: c_int = 2;
 
-// options (gn_set_option / gn_get_option); results never depend on them
+// options (gn_set_option / gn_get_option); results never depend on them, GN_OPT_QUIESCE_SEE excepted
 pub const GN_OPT_INCREMENTAL_CHILDREN: c_int = 1;
 pub const GN_OPT_XCD_SWIZZLE: c_int = 2;
 pub const GN_OPT_KING_SORT: c_int = 3;
@@ -38,6 +38,7 @@ pub const GN_OPT_COALESCE: c_int = 7;
 pub const GN_OPT_STREAM_SLICES: c_int = 8;
 pub const GN_OPT_FAST_BATCH: c_int = 9;
 pub const GN_OPT_EXPAND_PIPELINE: c_int = 10;
+pub const GN_OPT_QUIESCE_SEE: c_int = 11;
 // read-only statistics (gn_get_option)
 pub const GN_STAT_PLAN_NS: c_int = 101;
 pub const GN_STAT_STREAM_NS: c_int = 102;
@@ -355,6 +356,11 @@ extern "C" {
                                 d_offsets: *const u32, d_moves: *const u16, d_rec: *const gn_eval, total: usize,
                                 mode: c_int, depth: c_int, d_ext: *mut i32, d_tail: *mut u16, searched: *mut usize,
                                 nodes: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn gn_see_moves(boards: *const gn_board, n: usize, moves: *const u16, piece_value: *const i32,
+                        out: *mut i32) -> c_int;
+    pub fn gn_see_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                         d_offsets: *const u32, d_moves: *const u16, total: usize, d_see: *mut i32,
+                         stream: *mut c_void) -> c_int;
     pub fn gn_line_pvs_device(ctx: *mut gn_ctx, device_slot: c_int, n: usize, d_offsets: *const u32,
                               d_moves: *const u16, d_tail: *const u16, d_lines: *const gn_line, n_lines: c_int,
                               d_pvs: *mut gn_pv, stream: *mut c_void) -> c_int;

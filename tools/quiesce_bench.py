@@ -13,10 +13,12 @@ GN_STAT_EXTEND_NS, GN_STAT_QUIESCE_NS, GN_STAT_QUIESCE_LEAVES, GN_STAT_QUIESCE_N
             chunks unpipelined; GN_OPT_CHUNK_PARENTS is `--chunk` (0: the default).
 The variants are plain, extended and q<d> for every depth of `--depths`; a depth written <d>pv adds
 q<d>pv, the quiescent call that also returns each line's whole variation (gn_evaluate_lines2_quiescent_pv,
-gn_evaluate_games_lines_quiescent_pv; GN_STAT_PV_NS is then reported as "pv").  The plain and extended
+gn_evaluate_games_lines_quiescent_pv; GN_STAT_PV_NS is then reported as "pv"); a depth written <d>see
+adds q<d>see, the same call under GN_OPT_QUIESCE_SEE = 1 (the losing captures pruned; the option is set
+around that call alone, outside the timed region).  The plain and extended
 paths are the parent commit's code; run with GPU_NNUE_LIB set to another build of the library and
 `--depths ""` to measure that build's calls.  Prints one JSON line.
-Usage: python tools/quiesce_bench.py [--positions N] [--games G] [--lines K] [--reps R] [--depths 1,1pv,2,2pv,3]
+Usage: python tools/quiesce_bench.py [--positions N] [--games G] [--lines K] [--reps R] [--depths 1,1see,1pv,2,2see,2pv,3,3see]
 """
 import argparse
 import json
@@ -89,6 +91,14 @@ def main():
         return lambda: G._check(L.gn_evaluate_games_lines_quiescent(nn.h, garr, ng, G.MODE_FULL, K, 0, int(variant[1:]),
                                                                     *tail))
 
+    def pruned(make):
+        """make(variant), with a trailing "see" taken off the variant and the option set around the call."""
+        def made(variant):
+            if not variant.endswith("see"):
+                return make(variant), None
+            return make(variant[:-3]), G.OPT_QUIESCE_SEE
+        return made
+
     def stats():
         st = {k: round(v, 3) for k, v in nn.host_stages().items()}
         st["rank"] = round(nn.get_option(G.STAT_RANK_NS) / 1e6, 3)
@@ -104,15 +114,25 @@ def main():
 
     def measure(make):
         variants = ["plain", "extended"] + [f"q{d}" for d in depths]
-        calls = [(v, make(v)) for v in variants]
+        calls = [(v, *pruned(make)(v)) for v in variants]
         runs = {v: [] for v in variants}
-        for _, f in calls:  # warm-up: device buffers grown, host pages touched
+
+        def timed(f, opt):
+            if opt is not None:
+                nn.set_option(opt, 1)
+            t = time.perf_counter()
             f()
+            t = time.perf_counter() - t
+            st = stats()
+            if opt is not None:
+                nn.set_option(opt, 0)
+            return t, st
+
+        for _, f, opt in calls:  # warm-up: device buffers grown, host pages touched
+            timed(f, opt)
         for _ in range(args.reps):
-            for v, f in calls:
-                t = time.perf_counter()
-                f()
-                runs[v].append((time.perf_counter() - t, stats()))
+            for v, f, opt in calls:
+                runs[v].append(timed(f, opt))
         res = {}
         for v, rs in runs.items():
             rs.sort(key=lambda r: r[0])
