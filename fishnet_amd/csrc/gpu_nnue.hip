@@ -417,6 +417,21 @@ struct Dev {
     DevBuf<uint16_t> gtail; // the _pv calls: the grandchildren's tails from the leaf stage ...
     DevBuf<gn_pv> pv;       // ... and the chunk's PVs
   } l2;
+  // gn_evaluate_lines3: one chunk of roots' depth-1 expansion (l2 is in use below it: the children
+  // run through the two-ply chunk computation as parents), each child's line 1 and its PV, which
+  // never leave the device, and the chunk's lines and PVs
+  struct Lines3 {
+    DevBuf<gn_eval> po, co;
+    DevBuf<uint32_t> off;
+    DevBuf<gn_board> ch;
+    DevBuf<uint16_t> mv;
+    DevBuf<gn_line2> cln;
+    DevBuf<gn_pv> cpv;
+    DevBuf<gn_line3> ln;
+    DevBuf<gn_pv> pv;
+  } l3;
+  Event r3ev[2];     // around a chunk's rank_lines3_kernel (GN_STAT_RANK3_NS)
+  double t_rank3 = 0; // ... summed over the last three-ply call's chunks, ms
   // the leaf stage of one expansion level (value_leaves).  The selected leaves (level 0): the
   // selection and its scan, their indices, boards and values, the count of valued ones; rec: the
   // check extension's own records of them; ext: the one-ply games calls' per-chunk leaf values.
@@ -726,6 +741,7 @@ static int create(const uint8_t *big, size_t big_len, const uint8_t *small, size
       HIP_TRY(hipEventCreateWithFlags(&e->h, hipEventDisableTiming));
     for (Event &e : d.rev) HIP_TRY(hipEventCreate(&e.h));
     for (Event &e : d.pev) HIP_TRY(hipEventCreate(&e.h));
+    for (Event &e : d.r3ev) HIP_TRY(hipEventCreate(&e.h));
     HIP_TRY(d.tables.ensure(1));
     for (ExpSet *x : {&d.cur, &d.alt}) { // the planned expansion's error word and pad count
       HIP_TRY(x->perr.ensure(1));
@@ -1827,7 +1843,7 @@ static int run_shards(gn_ctx *ctx, const std::vector<size_t> &b, F &&f) {
 
 static void reset_host_stats(gn_ctx *ctx) {
   for (auto &dp : ctx->devs) {
-    dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = dp->t_keys = dp->t_pv = 0;
+    dp->t_upload = dp->t_replay = dp->t_compute = dp->t_download = dp->t_tail = dp->t_rank = dp->t_rank2 = dp->t_rank3 = dp->t_keys = dp->t_pv = 0;
     for (auto &st : dp->leaf.stats) st = {};
   }
 }
@@ -2345,6 +2361,7 @@ struct GameShard {
   std::vector<gn_eval> res;         // gathered: the evaluated positions' records ...
   std::vector<gn_line> lres;        // ... and lines ...
   std::vector<gn_line2> l2res;      // ... or two-ply lines
+  std::vector<gn_line3> l3res;      // ... or three-ply lines
   std::vector<gn_pv> pvres;         // ... and the lines' PVs (the _pv calls)
   std::vector<gn_history> hist;     // history call: each evaluated position's game so far, in rboards' indices
   std::vector<uint64_t> off;        // child offsets from pass 1 (m + 1, relative)
@@ -2371,6 +2388,7 @@ struct GamesArgs {
   int n_lines = 0;            // the lines calls: n_lines lines per position, no child reaches the host
   gn_line *lines = nullptr;   // ... one-ply (with_children 1: the children ranked on the device)
   gn_line2 *lines2 = nullptr; // ... or two-ply (with_children 0)
+  gn_line3 *lines3 = nullptr; // ... or three-ply (with_children 0; no history)
   bool history = false;       // ... with the game-history draws
   LeafRule leaf;              // ... their leaves valued by this rule (extend_stage)
   gn_pv *pvs = nullptr;       // ... and each line's whole variation (the _pv calls)
@@ -2482,7 +2500,7 @@ static int games_offsets(GamesCall &c) {
   if (c.total > c.position_cap)
     return fail(GN_E_CAPACITY, "%zu positions exceed capacity %zu", (size_t)c.total, c.position_cap);
   if (c.total && !c.position_out) return fail(GN_E_INVALID, "position_out is NULL");
-  if (c.total && c.n_lines && !c.lines && !c.lines2) return fail(GN_E_INVALID, "lines is NULL");
+  if (c.total && c.n_lines && !c.lines && !c.lines2 && !c.lines3) return fail(GN_E_INVALID, "lines is NULL");
   return GN_OK;
 }
 
@@ -2540,7 +2558,8 @@ static int games_gather(const GamesCall &c, GameShard &sh, Dev &d) {
     HIP_TRY(hipStreamSynchronize(s));
     d.t_upload += ms_since(t0);
     sh.res.resize(m);
-    if (c.lines2) sh.l2res.resize(m * (size_t)c.n_lines);
+    if (c.lines3) sh.l3res.resize(m * (size_t)c.n_lines);
+    else if (c.lines2) sh.l2res.resize(m * (size_t)c.n_lines);
     else sh.lres.resize(m * (size_t)c.n_lines);
     if (c.pvs) sh.pvres.resize(m * (size_t)c.n_lines);
   }
@@ -2639,7 +2658,8 @@ static void games_scatter(const GamesCall &c) {
   for (const GameShard &sh : c.shards)
     for (size_t e = 0; e < sh.where.size(); ++e) c.position_out[sh.where[e]] = sh.res[e];
   if (!c.n_lines) return;
-  if (c.lines2) games_scatter_lines(c, c.lines2, &GameShard::l2res, gn_line2{0, 0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE, 0});
+  if (c.lines3) games_scatter_lines(c, c.lines3, &GameShard::l3res, gn_line3{0, 0, 0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE, 0, 0});
+  else if (c.lines2) games_scatter_lines(c, c.lines2, &GameShard::l2res, gn_line2{0, 0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE, 0});
   else games_scatter_lines(c, c.lines, &GameShard::lres, gn_line{0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE});
   if (c.pvs) games_scatter_lines(c, c.pvs, &GameShard::pvres, gn_pv{});
 }
@@ -2647,6 +2667,8 @@ static void games_scatter(const GamesCall &c) {
 // phase B of gn_evaluate_games_lines2: the gather, then the two-ply lines' chunk loop (below, with
 // gn_evaluate_lines2)
 static int games_lines2(const GamesCall &c, GameShard &sh, Dev &d);
+// ... and of gn_evaluate_games_lines3: the gather, then the three-ply lines' chunk loop
+static int games_lines3(const GamesCall &c, GameShard &sh, Dev &d);
 
 static int evaluate_games(const GamesArgs &a) {
   if (!slot(a.ctx, 0)) return fail(GN_E_INVALID, "bad context");
@@ -2667,7 +2689,9 @@ static int evaluate_games(const GamesArgs &a) {
     for (GameShard &sh : c.shards) games_layout(c, sh), c.all_in_place = c.all_in_place && sh.in_place;
     auto has = [&](size_t k) { return c.shards[k].has(); };
     rc = run_devices(ctx, has, [&](size_t k, Dev &d) -> int {
-      return c.lines2 ? games_lines2(c, c.shards[k], d) : games_evaluate_or_count(c, c.shards[k], d);
+      return c.lines3   ? games_lines3(c, c.shards[k], d)
+             : c.lines2 ? games_lines2(c, c.shards[k], d)
+                        : games_evaluate_or_count(c, c.shards[k], d);
     });
     if (rc) return rc;
     if (c.with_children) {
@@ -2695,6 +2719,7 @@ static int evaluate_games_lines(gn_ctx *ctx, const gn_game *games, size_t n_game
   a.game_status = game_status, a.position_out = position_out, a.position_cap = position_cap;
   a.n_lines = n_lines, a.history = history, a.leaf = leaf;
   if constexpr (std::is_same<Line, gn_line>::value) a.with_children = 1, a.lines = lines;
+  else if constexpr (std::is_same<Line, gn_line3>::value) a.lines3 = lines;
   else a.lines2 = lines;
   return evaluate_games(a);
 }
@@ -3513,6 +3538,23 @@ int gn_rank_lines2_extended_device(gn_ctx *ctx, int device_slot, const gn_board 
                           d_gext, n_lines, d_lines, stream);
 }
 
+int gn_rank_lines3_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
+                          const uint16_t *d_moves, const gn_eval *d_child_out, size_t total, const gn_line2 *d_child_lines,
+                          const gn_pv *d_child_pvs, int n_lines, gn_line3 *d_lines, gn_pv *d_pvs, void *stream) {
+  Dev *d = slot(ctx, device_slot);
+  if (!d) return fail(GN_E_INVALID, "bad context or device slot");
+  if (int rc = check_n_lines(n_lines)) return rc;
+  if (d_pvs && !d_child_pvs) return fail(GN_E_INVALID, "d_pvs without d_child_pvs");
+  if (n && !d_lines) return fail(GN_E_INVALID, "NULL buffer");
+  if (n && total && (!d_parents || !d_offsets || !d_moves || !d_child_out || !d_child_lines))
+    return fail(GN_E_INVALID, "NULL buffer");
+  DevCall call(*d, stream);
+  if (call.rc) return call.rc;
+  HIP_TRY(launch_rank_lines3(d_parents, n, d_offsets, d_moves, d_child_out, total, d_child_lines, d_child_pvs, ctx->P,
+                             d->tables.p, n_lines, d_lines, d_pvs, call.s));
+  return GN_OK;
+}
+
 int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, int mode, int iters,
                           float *ms_total, size_t *total, float *stage_ms, uint64_t *ft_rows, gn_eval *d_parent_out,
                           uint32_t *d_offsets, uint16_t *d_moves, gn_eval *d_child_out, size_t cap) {
@@ -3757,6 +3799,7 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
   case GN_STAT_HOST_DOWNLOAD_NS:
   case GN_STAT_RANK_NS:
   case GN_STAT_RANK2_NS:
+  case GN_STAT_RANK3_NS:
   case GN_STAT_KEYS_NS:
   case GN_STAT_PV_NS:
   case GN_STAT_HOST_TAIL_NS: { // the last host-buffer call, max over devices
@@ -3769,6 +3812,7 @@ int gn_get_option(const gn_ctx *ctx, int option, int64_t *value) {
                       : option == GN_STAT_HOST_DOWNLOAD_NS ? d.t_download
                       : option == GN_STAT_RANK_NS          ? d.t_rank
                       : option == GN_STAT_RANK2_NS         ? d.t_rank2
+                      : option == GN_STAT_RANK3_NS         ? d.t_rank3
                       : option == GN_STAT_KEYS_NS          ? d.t_keys
                       : option == GN_STAT_PV_NS            ? d.t_pv
                                                            : d.t_tail);
@@ -3826,22 +3870,18 @@ int gn_expand_and_evaluate(gn_ctx *ctx, const char *const *parent_fens, size_t n
   });
 }
 
-// A shard's two-ply lines (gn_evaluate_lines2, gn_evaluate_games_lines2): its m device-resident
-// parents in chunks of chunk parents; per chunk the depth-2 expansion into the device's Lines2
-// buffers (expand2_on), rank_lines2_kernel -- its history variant when history names the shard's
-// keys and its parents' gn_history entries (hist NULL: the plain one) -- and one download of the chunk's parent records and
-// lines into out / lines (the shard's first parent's).  The chunks need no cut at game starts: the
-// keys are the whole shard's.
-// leaf: a rule that extends values the grandchildren after the expansion (extend_stage; the children
-// as parents, the library's own boards), and the ranking takes their values.
-// pvs (the _pv calls; NULL: none): the shard's PVs, as lines; the leaf stage leaves the grandchildren's
-// tails, the PVs are assembled after the ranking and downloaded with the chunk's lines.
-static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m, int mode, int K, gn_eval *out,
-                         gn_line2 *lines, const RankHistory &history, LeafRule leaf, gn_pv *pvs = nullptr) {
+// One chunk of the two-ply lines (gn_evaluate_lines2, gn_evaluate_games_lines2; the three-ply calls,
+// with a root chunk's children as the parents): the mp device-resident parents' depth-2 expansion into
+// the device's Lines2 buffers (expand2_on), the leaf stage where the rule extends (extend_stage; the
+// children as parents, the library's own boards), rank_lines2_kernel -- its history variant when h
+// names the keys and these parents' gn_history entries (h.hist NULL: the plain one) -- and, with d_pvs,
+// the PVs' assembly (the quiescent rule's leaf stage leaves the grandchildren's tails).  The parents'
+// records go to x.po, the lines to d_lines and the PVs to d_pvs (NULL: none), all on the device; the
+// stream is idle on return, and the chunk's times are added to the device's stage times.
+static int lines2_compute(gn_ctx *ctx, Dev &d, const gn_board *par, size_t mp, int mode, int K, const RankHistory &h,
+                          LeafRule leaf, gn_line2 *d_lines, gn_pv *d_pvs) {
   hipStream_t s = d.stream;
   Dev::Lines2 &x = d.l2;
-  // 1,024 parents are ~1 M grandchildren: a few hundred MB of records, boards and partial sums
-  const size_t chunk = ctx->chunk_parents > 0 ? (size_t)ctx->chunk_parents : 1024;
   const std::function<int(size_t, size_t, Expand2Grand &)> size_grand = [&](size_t t, size_t g, Expand2Grand &gr) -> int {
     HIP_TRY(x.goff.ensure(t + 1));
     HIP_TRY(x.gmv.ensure(std::max<size_t>(g, 1)));
@@ -3849,11 +3889,95 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
     gr = Expand2Grand{x.goff.p, x.gmv.p, x.gco.p, std::max<size_t>(g, 1)};
     return GN_OK;
   };
+  const bool tails = d_pvs && leaf.kind == LeafRule::QUIESCE; // (the check extension's replies are not reported)
+  const auto t0 = Clock::now();
+  size_t t = 0, g = 0;
+  HIP_TRY(count_children(d, par, mp, s, &t));
+  const size_t cap = std::max<size_t>(t, 1);
+  HIP_TRY(x.po.ensure(mp));
+  HIP_TRY(x.off.ensure(mp + 1));
+  HIP_TRY(x.ch.ensure(cap));
+  HIP_TRY(x.mv.ensure(cap));
+  HIP_TRY(x.co.ensure(cap));
+  int rc = expand2_on(ctx, &d, par, mp, mode, x.po.p, x.off.p, x.ch.p, x.mv.p, x.co.p, cap, Expand2Grand{}, &t, &g, s,
+                      &size_grand);
+  if (rc) return rc;
+  if (leaf.extends()) { // (t == 0 or g == 0: nothing is read)
+    HIP_TRY(x.gext.ensure(std::max<size_t>(g, 1)));
+    if (tails) HIP_TRY(x.gtail.ensure(std::max<size_t>(g, 1) * GN_MAX_QUIESCE_DEPTH));
+    rc = extend_stage(ctx, d, PackedLeaves{x.ch.p, t, x.goff.p, x.gmv.p, x.gco.p, g}, mode, leaf, x.gext.p,
+                      tails ? x.gtail.p : nullptr, s);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipEventRecord(d.rev[0], s));
+  HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables.p, K,
+                             d_lines, h.hist ? &h : nullptr, leaf.extends() ? x.gext.p : nullptr, s));
+  HIP_TRY(hipEventRecord(d.rev[1], s));
+  if (d_pvs) { // (g == 0: no line is searched, and the tails are not read)
+    HIP_TRY(hipEventRecord(d.pev[2], s));
+    HIP_TRY(launch_line2_pvs(mp, x.off.p, x.mv.p, x.goff.p, x.gmv.p, tails ? x.gtail.p : nullptr, d_lines, K, d_pvs, s));
+    HIP_TRY(hipEventRecord(d.pev[3], s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, d.rev[0], d.rev[1]));
+  d.t_rank2 += ms;
+  if (d_pvs) {
+    HIP_TRY(hipEventElapsedTime(&ms, d.pev[2], d.pev[3]));
+    d.t_pv += ms;
+  }
+  d.t_compute += ms_since(t0);
+  return GN_OK;
+}
+
+// the ranked-lines calls' parents per chunk (GN_OPT_CHUNK_PARENTS; 0: 1,024 parents, ~1 M
+// grandchildren: a few hundred MB of records, boards and partial sums)
+static size_t lines_chunk(const gn_ctx *ctx) { return ctx->chunk_parents > 0 ? (size_t)ctx->chunk_parents : 1024; }
+
+// A shard's two-ply lines (gn_evaluate_lines2, gn_evaluate_games_lines2): its m device-resident
+// parents in chunks of chunk parents; per chunk lines2_compute into the device's Lines2 buffers and
+// one download of the chunk's parent records and lines (and, with pvs, the _pv calls, its PVs) into
+// out / lines / pvs (the shard's first parent's).  history: the shard's keys and its parents'
+// gn_history entries (hist NULL: none); the chunks need no cut at game starts: the keys are the whole
+// shard's.
+static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m, int mode, int K, gn_eval *out,
+                         gn_line2 *lines, const RankHistory &history, LeafRule leaf, gn_pv *pvs = nullptr) {
+  hipStream_t s = d.stream;
+  Dev::Lines2 &x = d.l2;
+  const size_t chunk = lines_chunk(ctx);
   for (size_t a = 0; a < m; a += chunk) {
     const size_t mp = std::min(chunk, m - a);
-    const gn_board *par = parents + a;
+    HIP_TRY(x.ln.ensure(mp * (size_t)K));
+    if (pvs) HIP_TRY(x.pv.ensure(mp * (size_t)K));
+    const RankHistory h = {history.keys, history.n_keys, history.hist ? history.hist + a : nullptr};
+    if (int rc = lines2_compute(ctx, d, parents + a, mp, mode, K, h, leaf, x.ln.p, pvs ? x.pv.p : nullptr)) return rc;
+    const auto t0 = Clock::now();
+    HIP_TRY(hipMemcpyAsync(out + a, x.po.p, mp * sizeof(gn_eval), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(lines + a * (size_t)K, x.ln.p, mp * (size_t)K * sizeof(gn_line2), hipMemcpyDeviceToHost, s));
+    if (pvs) HIP_TRY(hipMemcpyAsync(pvs + a * (size_t)K, x.pv.p, mp * (size_t)K * sizeof(gn_pv), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    d.t_download += ms_since(t0);
+  }
+  return GN_OK;
+}
+
+// A shard's three-ply lines (gn_evaluate_lines3, gn_evaluate_games_lines3; the rule at gn_line3): its
+// m device-resident roots in chunks of chunk roots.  Per chunk: the depth-1 expansion into the
+// device's Lines3 buffers (expand_level: the root records, the child boards, moves and records); the
+// children as parents through lines2_compute with K = 1, the call's leaf rule and no history, in
+// chunks of the same number of children, cut wherever they fall, each child's line 1 (and, with pvs,
+// its PV) written beside its record and never downloaded; rank_lines3_kernel; one download of the
+// chunk's root records, lines and (with pvs) PVs.
+static int lines3_chunks(gn_ctx *ctx, Dev &d, const gn_board *roots, size_t m, int mode, int K, gn_eval *out,
+                         gn_line3 *lines, LeafRule leaf, gn_pv *pvs) {
+  hipStream_t s = d.stream;
+  Dev::Lines3 &x = d.l3;
+  const size_t chunk = lines_chunk(ctx);
+  for (size_t a = 0; a < m; a += chunk) {
+    const size_t mp = std::min(chunk, m - a);
+    const gn_board *par = roots + a;
     auto t0 = Clock::now();
-    size_t t = 0, g = 0;
+    size_t t = 0;
     HIP_TRY(count_children(d, par, mp, s, &t));
     const size_t cap = std::max<size_t>(t, 1);
     HIP_TRY(x.po.ensure(mp));
@@ -3861,40 +3985,30 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
     HIP_TRY(x.ch.ensure(cap));
     HIP_TRY(x.mv.ensure(cap));
     HIP_TRY(x.co.ensure(cap));
+    HIP_TRY(x.cln.ensure(cap));
+    if (pvs) HIP_TRY(x.cpv.ensure(cap));
     HIP_TRY(x.ln.ensure(mp * (size_t)K));
-    int rc = expand2_on(ctx, &d, par, mp, mode, x.po.p, x.off.p, x.ch.p, x.mv.p, x.co.p, cap, Expand2Grand{}, &t, &g, s,
-                        &size_grand);
-    if (rc) return rc;
-    const RankHistory h = {history.keys, history.n_keys, history.hist ? history.hist + a : nullptr};
-    if (leaf.extends()) { // (t == 0 or g == 0: nothing is read)
-      HIP_TRY(x.gext.ensure(std::max<size_t>(g, 1)));
-      if (pvs) HIP_TRY(x.gtail.ensure(std::max<size_t>(g, 1) * GN_MAX_QUIESCE_DEPTH));
-      rc = extend_stage(ctx, d, PackedLeaves{x.ch.p, t, x.goff.p, x.gmv.p, x.gco.p, g}, mode, leaf, x.gext.p,
-                        pvs ? x.gtail.p : nullptr, s);
-      if (rc) return rc;
-    }
     if (pvs) HIP_TRY(x.pv.ensure(mp * (size_t)K));
-    HIP_TRY(hipEventRecord(d.rev[0], s));
-    HIP_TRY(launch_rank_lines2(par, mp, x.off.p, x.ch.p, x.co.p, x.mv.p, x.goff.p, x.gmv.p, x.gco.p, ctx->P, d.tables.p, K,
-                               x.ln.p, h.hist ? &h : nullptr, leaf.extends() ? x.gext.p : nullptr, s));
-    HIP_TRY(hipEventRecord(d.rev[1], s));
-    if (pvs) { // (g == 0: no line is searched, and the tails are not read)
-      HIP_TRY(hipEventRecord(d.pev[2], s));
-      HIP_TRY(launch_line2_pvs(mp, x.off.p, x.mv.p, x.goff.p, x.gmv.p, leaf.extends() ? x.gtail.p : nullptr, x.ln.p, K,
-                               x.pv.p, s));
-      HIP_TRY(hipEventRecord(d.pev[3], s));
-    }
+    LevelOpts root;
+    root.children = x.ch.p;
+    if (int rc = expand_level(ctx, d, par, mp, mode, x.po.p, x.off.p, x.mv.p, x.co.p, cap, &t, s, root)) return rc;
+    d.t_compute += ms_since(t0);
+    for (size_t b = 0; b < t; b += chunk) // (lines2_compute adds its own time)
+      if (int rc = lines2_compute(ctx, d, x.ch.p + b, std::min(chunk, t - b), mode, 1, NO_HISTORY, leaf, x.cln.p + b,
+                                  pvs ? x.cpv.p + b : nullptr))
+        return rc;
+    t0 = Clock::now();
+    HIP_TRY(hipEventRecord(d.r3ev[0], s));
+    HIP_TRY(launch_rank_lines3(par, mp, x.off.p, x.mv.p, x.co.p, t, x.cln.p, pvs ? x.cpv.p : nullptr, ctx->P, d.tables.p, K,
+                               x.ln.p, pvs ? x.pv.p : nullptr, s));
+    HIP_TRY(hipEventRecord(d.r3ev[1], s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, d.rev[0], d.rev[1]));
-    d.t_rank2 += ms;
-    if (pvs) {
-      HIP_TRY(hipEventElapsedTime(&ms, d.pev[2], d.pev[3]));
-      d.t_pv += ms;
-    }
+    HIP_TRY(hipEventElapsedTime(&ms, d.r3ev[0], d.r3ev[1]));
+    d.t_rank3 += ms;
     d.t_compute += ms_since(t0), t0 = Clock::now();
     HIP_TRY(hipMemcpyAsync(out + a, x.po.p, mp * sizeof(gn_eval), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(lines + a * (size_t)K, x.ln.p, mp * (size_t)K * sizeof(gn_line2), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(lines + a * (size_t)K, x.ln.p, mp * (size_t)K * sizeof(gn_line3), hipMemcpyDeviceToHost, s));
     if (pvs) HIP_TRY(hipMemcpyAsync(pvs + a * (size_t)K, x.pv.p, mp * (size_t)K * sizeof(gn_pv), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     d.t_download += ms_since(t0);
@@ -3932,6 +4046,42 @@ static int games_lines2(const GamesCall &c, GameShard &sh, Dev &d) {
                        !c.pvs ? nullptr : sh.in_place ? c.pvs + sh.p0 * (size_t)c.n_lines : sh.pvres.data());
 }
 
+// ... and the same two for the three-ply lines
+static int lines3_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int mode, int K, gn_eval *out,
+                              gn_line3 *lines, LeafRule leaf, gn_pv *pvs) {
+  const size_t nd = ctx->devs.size();
+  std::vector<size_t> b(nd + 1);
+  partition(nullptr, n, (int)nd, b.data());
+  const auto locks = lock_devices(ctx);
+  return run_shards(ctx, b, [&](size_t, Dev &d, size_t lo, size_t hi) -> int {
+    const auto t0 = Clock::now();
+    HIP_TRY(d.par.ensure(hi - lo));
+    HIP_TRY(hipMemcpyAsync(d.par.p, boards + lo, (hi - lo) * sizeof(gn_board), hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    d.t_upload += ms_since(t0);
+    return lines3_chunks(ctx, d, d.par.p, hi - lo, mode, K, out + lo, lines + lo * (size_t)K, leaf,
+                         pvs ? pvs + lo * (size_t)K : nullptr);
+  });
+}
+static int games_lines3(const GamesCall &c, GameShard &sh, Dev &d) {
+  const int rc = games_gather(c, sh, d);
+  if (rc) return rc;
+  gn_line3 *const ln = sh.in_place ? c.lines3 + sh.p0 * (size_t)c.n_lines : sh.l3res.data();
+  return lines3_chunks(c.ctx, d, sh.parents_of(d), sh.m, c.mode, c.n_lines, sh.records_of(c.position_out), ln, c.leaf,
+                       !c.pvs ? nullptr : sh.in_place ? c.pvs + sh.p0 * (size_t)c.n_lines : sh.pvres.data());
+}
+
+// The three-ply calls' leaf and depth (include/gpu_nnue.h at gn_line3) as a LeafRule; the quiescent
+// rule's depth is 1..GN_MAX_QUIESCE_DEPTH3 here: three moves and the tail fit a gn_pv
+static int leaf_rule3(const gn_ctx *ctx, int leaf, int depth, LeafRule &rule) {
+  if (leaf < GN_LEAF_STATIC || leaf > GN_LEAF_QUIESCE) return fail(GN_E_INVALID, "leaf rule %d outside 0..2", leaf);
+  if (leaf == GN_LEAF_QUIESCE && (depth < 1 || depth > GN_MAX_QUIESCE_DEPTH3))
+    return fail(GN_E_INVALID, "quiescence depth %d outside 1..%d", depth, GN_MAX_QUIESCE_DEPTH3);
+  if (leaf != GN_LEAF_QUIESCE && depth != 0) return fail(GN_E_INVALID, "depth %d with a leaf rule that takes none", depth);
+  rule = leaf == GN_LEAF_QUIESCE ? LeafRule::quiesce(ctx, depth) : leaf == GN_LEAF_CHECKS ? LeafRule::checks() : LeafRule{};
+  return GN_OK;
+}
+
 // The FEN lines2 calls
 static int evaluate_lines2(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, LeafRule leaf,
                            gn_eval *out, gn_line2 *lines, gn_pv *pvs = nullptr) {
@@ -3964,6 +4114,31 @@ int gn_evaluate_lines2_quiescent_pv(gn_ctx *ctx, const char *const *fens, size_t
                                     gn_eval *out, gn_line2 *lines, gn_pv *pvs) {
   if (n && !pvs) return fail(GN_E_INVALID, "pvs is NULL");
   return evaluate_lines2(ctx, fens, n, mode, n_lines, LeafRule::quiesce(ctx, depth), out, lines, pvs);
+}
+
+int gn_evaluate_lines3(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, int leaf, int depth,
+                       gn_eval *out, gn_line3 *lines, gn_pv *pvs) {
+  if (!slot(ctx, 0)) return fail(GN_E_INVALID, "bad context");
+  if (int rc = check_n_lines(n_lines)) return rc;
+  LeafRule rule;
+  if (int rc = leaf_rule3(ctx, leaf, depth, rule)) return rc;
+  if (n && (!fens || !out || !lines)) return fail(GN_E_INVALID, "NULL argument");
+  if (!n) return GN_OK;
+  return on_packed_fens(ctx, fens, n, [&](const gn_board *boards) -> int {
+    return lines3_boards_host(ctx, boards, n, mode, n_lines, out, lines, rule, pvs);
+  });
+}
+
+int gn_evaluate_games_lines3(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines, int leaf,
+                             int depth, uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
+                             size_t position_cap, gn_line3 *lines, gn_pv *pvs) {
+  if (!slot(ctx, 0)) return fail(GN_E_INVALID, "bad context");
+  if (int rc = check_n_lines(n_lines)) return rc;
+  LeafRule rule;
+  if (int rc = leaf_rule3(ctx, leaf, depth, rule)) return rc;
+  if (n_games && !lines) return fail(GN_E_INVALID, "lines is NULL");
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, false, rule, position_offsets, game_status,
+                              position_out, position_cap, lines, pvs);
 }
 
 int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {

@@ -325,6 +325,16 @@ hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t 
                               const uint16_t *gmoves, const gn_eval *grec, const gn_eval_params &P,
                               const Tables *tables, int K, gn_line2 *lines, const RankHistory *history,
                               const int32_t *gext, hipStream_t s);
+// Three-ply ranked lines, the root step (include/gpu_nnue.h gn_line3): lines[i * K + k] = line k + 1 of
+// root i, from the root expansion (offsets, moves, the child records rec for GN_FLAG_IN_CHECK) and
+// clines[c] = line 1 of the two-ply ranking with child c as the parent (empty: c has no legal move);
+// with pvs (NULL: none) pvs[i * K + k] = [move] + cpvs[the line's child].  One launch, no move
+// generation, no scratch memory; every child range is clamped to total, and with total == 0 no input
+// but n is read.
+hipError_t launch_rank_lines3(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
+                              const gn_eval *rec, size_t total, const gn_line2 *clines, const gn_pv *cpvs,
+                              const gn_eval_params &P, const Tables *tables, int K, gn_line3 *lines, gn_pv *pvs,
+                              hipStream_t s);
 // Check extension of one expansion level (gpu_nnue.hip extend_checks): select (sel[total + 1] from
 // the leaf records' GN_FLAG_IN_CHECK, ext[total] = GN_NOT_EXTENDED), boards (pos = exclusive scan of
 // sel: the selected leaves' boards sb, leaf indices idx and sv = GN_NOT_EXTENDED, compacted; the

@@ -1504,6 +1504,94 @@ hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t 
   return hipGetLastError();
 }
 
+// ---- three-ply ranked lines: the root step (include/gpu_nnue.h gn_line3) -----------------
+// A three-ply line of a root is a two-ply line of one of its children, negated: clines[c] is line 1
+// of the two-ply ranking with child c as the parent, an empty one (GN_FLAG_NO_SCORE) where c has no
+// legal move -- the kernel generates no move and asks no any_legal; it unpacks the root alone, for
+// wdl_material.  Shaped like rank_children_kernel: a group of GN_RANK_WIDTH lanes per root, a lane
+// per child, the group looping over a longer segment, top_k_rounds over the lanes' keys.  The key
+// (Root3Key) is (value + 32768) << 25 | (0xFFFF - move) << 9 | index << 1 | in-check: larger value
+// first, then the smaller move; the child's index within its segment (< 256: a position has at most
+// 218 legal moves, and a longer segment is cut there) rides below the move, where it cannot change the
+// order, and leads lanes 0..K-1 back to the winning child's line for reply, reply2, plies and flags
+// and, with pvs, to its gn_pv: the line's PV is [move] + the child's, written by the same lane.
+// Every child range is clamped to total; with total == 0 not even the offsets are read.
+using Root3Key = SortKey<24, 1>;
+constexpr uint32_t ROOT3_MAX_SEGMENT = 256;
+__global__ void __launch_bounds__(RANK_WG)
+    rank_lines3_kernel(const gn_board *__restrict__ parents, size_t n, const uint32_t *__restrict__ offsets,
+                       const uint16_t *__restrict__ moves, const gn_eval *__restrict__ rec, size_t total,
+                       const gn_line2 *__restrict__ clines, const gn_pv *__restrict__ cpvs, gn_eval_params P,
+                       const Tables *__restrict__ tables, int K, gn_line3 *__restrict__ lines, gn_pv *__restrict__ pvs) {
+  __shared__ Tables T;
+  load_tables(T, tables);
+  constexpr int W = GN_RANK_WIDTH;
+  const int lane = threadIdx.x & (W - 1);
+  const size_t stride = (size_t)gridDim.x * (RANK_WG / W);
+  for (size_t p = (size_t)blockIdx.x * (RANK_WG / W) + threadIdx.x / W; p < n; p += stride) {
+    uint64_t c0 = 0, c1 = 0;
+    if (total) {
+      c1 = std::min<uint64_t>(offsets[p + 1], total), c0 = std::min<uint64_t>(offsets[p], c1);
+      c1 = std::min<uint64_t>(c1, c0 + ROOT3_MAX_SEGMENT);
+    }
+    uint64_t top = 0; // lanes 0..K-1: the running top K (0: none yet)
+    Board B;
+    const bool ok = c1 > c0 && unpack(parents[p], B, T);
+    for (uint64_t c = c0; ok && c < c1; c += W) {
+      uint64_t key = 0;
+      if (c + lane < c1) {
+        const uint32_t mv = moves[c + lane];
+        const uint32_t check = (rec[c + lane].flags & GN_FLAG_IN_CHECK) ? KEY_CHECK : 0u;
+        const gn_line2 L = clines[c + lane];
+        const int32_t R = (L.flags & GN_FLAG_NO_SCORE) ? (check ? -VALUE_MATE : 0) : L.value;
+        key = Root3Key::pack(negate_ply(R), (uint64_t)(0xFFFFu - mv) << 8 | (uint32_t)(c + lane - c0), check);
+      }
+      top = top_k_rounds<W>(key, top, lane, K);
+    }
+    if (lane < K) {
+      gn_line3 l = {0, 0, 0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE, 0, 0};
+      gn_pv pv = {};
+      if (top) {
+        const uint64_t j = c0 + (Root3Key::payload(top) & 0xFFu);
+        const gn_line2 L = clines[j];
+        const bool none = L.flags & GN_FLAG_NO_SCORE;
+        uint32_t fl = (Root3Key::flags(top) ? GN_FLAG_IN_CHECK : 0u) |
+                      (none ? GN_FLAG_NO_MOVES : L.flags & (GN_FLAG_NO_MOVES | GN_FLAG_SEARCHED));
+        l.value = Root3Key::value(top);
+        l.move = (uint16_t)(0xFFFFu - (Root3Key::payload(top) >> 8));
+        l.reply = none ? 0 : L.move;
+        l.reply2 = none ? 0 : L.reply;
+        l.plies = (uint16_t)(none ? 1 : 1 + L.plies);
+        l.score = rule_score(l.value, wdl_material(B, P), P, fl);
+        l.flags = (uint16_t)fl;
+        if (pvs) {
+          gn_pv cp = {};
+          if (!none) cp = cpvs[j];
+          const uint32_t tail = cp.len < GN_MAX_PV - 1 ? cp.len : GN_MAX_PV - 1;
+          pv.len = (uint16_t)(1 + tail);
+          pv.moves[0] = l.move;
+#pragma unroll
+          for (uint32_t k = 0; k + 1 < GN_MAX_PV; ++k) pv.moves[k + 1] = k < tail ? cp.moves[k] : 0;
+        }
+      }
+      lines[p * (size_t)K + lane] = l;
+      if (pvs) pvs[p * (size_t)K + lane] = pv;
+    }
+  }
+}
+
+hipError_t launch_rank_lines3(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
+                              const gn_eval *rec, size_t total, const gn_line2 *clines, const gn_pv *cpvs,
+                              const gn_eval_params &P, const Tables *tables, int K, gn_line3 *lines, gn_pv *pvs,
+                              hipStream_t s) {
+  if (!n) return hipSuccess;
+  constexpr size_t per_wg = RANK_WG / GN_RANK_WIDTH, max_blocks = 8192;
+  const size_t blocks = std::min<size_t>((n + per_wg - 1) / per_wg, max_blocks);
+  hipLaunchKernelGGL(rank_lines3_kernel, dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets, moves, rec, total, clines,
+                     cpvs, P, tables, K, lines, pvs);
+  return hipGetLastError();
+}
+
 // ---- check extension of one expansion level (include/gpu_nnue.h gn_extend_checks_device) ----
 // The leaves in check of an expansion level are valued by the score rule's in-check part instead of
 // their static evaluation (gpu_nnue.hip extend_checks): selected here from their records, their
@@ -1847,7 +1935,9 @@ __global__ void count_children_kernel(const gn_board *__restrict__ boards, size_
 // bytes); a thread per child writes every array coalesced.
 //
 // The link, next_slot[i]: the child whose placement is boards[i + 1]'s (a game's next
-// position; no two legal moves give one placement); the chained walk then starts parent
+// position; no two legal moves give one placement) and whose side to move is the other one, as a
+// child's is: a sibling of boards[i] can have a child's placement (two king moves that meet), but it is
+// not that child, and its outputs are not the child's; the chained walk then starts parent
 // i + 1 from that child's accumulators, gathering one carry row per perspective instead
 // of its refresh.  Found per parent without making any child: S is the set of squares on
 // which the parent's and the next board's placements differ; a move can give the next
@@ -1881,6 +1971,7 @@ __global__ void child_moves_kernel(const gn_board *__restrict__ boards, size_t n
       S = (B.byColor[0] ^ N.byColor[0]) | (B.byColor[1] ^ N.byColor[1]) | (B.byType[0] ^ N.byType[0]);
 #pragma unroll
       for (int t = PAWN; t <= KING; ++t) S |= B.byType[t] ^ N.byType[t];
+      if (N.stm == B.stm) S = 0; // the same side to move: not a child of this board
     }
   }
   const int us = B.stm;

@@ -47,6 +47,13 @@ LINE2_DTYPE = np.dtype([("value", "<i4"), ("score", "<i4"), ("move", "<u2"), ("r
 EVAL_SIZE, BOARD_SIZE, CHILD_SIZE = EVAL_DTYPE.itemsize, BOARD_DTYPE.itemsize, CHILD_DTYPE.itemsize
 assert EVAL_SIZE == 24 and BOARD_SIZE == 32 and CHILD_SIZE == 12 and LINE_DTYPE.itemsize == 12
 assert LINE2_DTYPE.itemsize == 16
+# gn_line3: one ranked three-ply line (move, reply, the answer to it and the minimax value after three
+# plies; gpu_nnue.h at gn_line3), 20 bytes
+LINE3_DTYPE = np.dtype([("value", "<i4"), ("score", "<i4"), ("move", "<u2"), ("reply", "<u2"), ("reply2", "<u2"),
+                        ("flags", "<u2"), ("plies", "<u2"), ("reserved", "<u2")])
+assert LINE3_DTYPE.itemsize == 20
+# the three-ply calls' leaf rule (GN_LEAF_*): static leaves, the check extension, the capture quiescence
+LEAF_STATIC, LEAF_CHECKS, LEAF_QUIESCE = 0, 1, 2
 # gn_pv: one line's whole variation (its own moves, then the quiescence's; gpu_nnue.h at gn_pv), 16 bytes
 MAX_PV = 6  # GN_MAX_PV
 PV_DTYPE = np.dtype([("len", "<u2"), ("moves", "<u2", (MAX_PV,)), ("reserved", "<u2")])
@@ -72,7 +79,8 @@ EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_
            "gn_evaluate_games_lines_quiescent",
            "gn_quiesce_pv_device", "gn_line_pvs_device", "gn_line2_pvs_device", "gn_evaluate_lines2_quiescent_pv",
            "gn_evaluate_games_lines2_quiescent_pv", "gn_evaluate_games_lines_quiescent_pv",
-           "gn_see_moves", "gn_see_device"]
+           "gn_see_moves", "gn_see_device",
+           "gn_evaluate_lines3", "gn_evaluate_games_lines3", "gn_rank_lines3_device"]
 OPT_INCREMENTAL_CHILDREN, OPT_XCD_SWIZZLE, OPT_KING_SORT, OPT_CHAIN, OPT_KING_CACHE = 1, 2, 3, 4, 5
 OPT_CHUNK_PARENTS, OPT_COALESCE, OPT_STREAM_SLICES, OPT_FAST_BATCH, OPT_EXPAND_PIPELINE = 6, 7, 8, 9, 10
 OPT_QUIESCE_SEE = 11  # 1: the quiescent calls prune the noisy moves with see < 0 (the one option that changes results)
@@ -83,7 +91,9 @@ STAT_RANK_NS, STAT_RANK2_NS, STAT_KEYS_NS = 121, 122, 123
 STAT_EXTEND_NS, STAT_EXTENDED_LEAVES = 124, 125
 STAT_QUIESCE_NS, STAT_QUIESCE_LEAVES, STAT_QUIESCE_NODES = 126, 127, 128
 STAT_PV_NS = 129
+STAT_RANK3_NS = 130
 MAX_QUIESCE_DEPTH = 4  # GN_MAX_QUIESCE_DEPTH
+MAX_QUIESCE_DEPTH3 = MAX_PV - 3  # GN_MAX_QUIESCE_DEPTH3: the three-ply calls' depth, a three-move PV plus its tail
 NOT_EXTENDED = -(2 ** 31)  # GN_NOT_EXTENDED: a d_ext entry of a leaf the check extension does not value
 HOST_STAGES = {"parse": 110, "upload": 111, "replay": 112, "compute": 113, "download": 114, "tail": 115, "total": 116}
 EXPAND_STAGES = ["count_scan", "total_readback", "write_children", "classify", "small_net", "big_net", "finalize",
@@ -228,6 +238,9 @@ def lib():
         "gn_evaluate_games_lines_quiescent_pv": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp, vp],
         "gn_see_moves": [vp, sz, vp, vp, vp],
         "gn_see_device": [vp, i32, vp, sz, vp, vp, sz, vp, vp],
+        "gn_evaluate_lines3": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp],
+        "gn_evaluate_games_lines3": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp, vp],
+        "gn_rank_lines3_device": [vp, i32, vp, sz, vp, vp, vp, sz, vp, vp, i32, vp, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -667,6 +680,28 @@ class GpuNnue:
         _check((call or lib().gn_evaluate_lines2)(self.h, arr, n, mode, n_lines, out.ctypes.data, lines.ctypes.data))
         return out, lines
 
+    def evaluate_lines3(self, fens, n_lines, leaf=LEAF_STATIC, depth=0, mode=MODE_FULL, pvs=True):
+        """gn_evaluate_lines3: (positions[EVAL_DTYPE], lines[positions, n_lines] as LINE3_DTYPE, pvs[positions,
+        n_lines] as PV_DTYPE or None): the best n_lines three-ply lines (move, reply, the answer to it, the
+        minimax value) of every FEN, their leaves valued by the leaf rule (LEAF_*; depth 1..
+        MAX_QUIESCE_DEPTH3 with LEAF_QUIESCE, else 0).  pvs False: no PVs are made."""
+        n = len(fens)
+        arr, _keep = _fen_array(fens)
+        out = np.zeros(n, dtype=EVAL_DTYPE)
+        lines = np.zeros((n, max(n_lines, 1)), dtype=LINE3_DTYPE)
+        pv = np.zeros((n, max(n_lines, 1)), dtype=PV_DTYPE) if pvs else None
+        _check(lib().gn_evaluate_lines3(self.h, arr, n, mode, n_lines, leaf, depth, out.ctypes.data, lines.ctypes.data,
+                                        pv.ctypes.data if pvs else None))
+        return out, lines, pv
+
+    def evaluate_games_lines3(self, games, n_lines, leaf=LEAF_STATIC, depth=0, mode=MODE_FULL, cap=None, pvs=True):
+        """gn_evaluate_games_lines3: evaluate_games_lines2 with three-ply lines (LINE3_DTYPE) under the
+        leaf rule, without game history: (offsets, status, positions, lines, pvs or None)."""
+        f = lib().gn_evaluate_games_lines3
+        call = lambda h, arr, ng, mode, K, *rest: f(h, arr, ng, mode, K, leaf, depth, *rest, *(() if pvs else (None,)))
+        res = self._games_lines(call, LINE3_DTYPE, games, n_lines, mode, cap, pvs=pvs)
+        return res if pvs else res + (None,)
+
     def host_stages(self):
         """Stage times (ms) of the last gn_evaluate_games / gn_expand_and_evaluate (GN_STAT_HOST_*)."""
         return {k: self.get_option(v) / 1e6 for k, v in HOST_STAGES.items()}
@@ -824,6 +859,16 @@ class GpuNnue:
         _check(lib().gn_line2_pvs_device(self.h, slot, n, p("off"), p("mv"), p("goff"), p("gmv"),
                                          d_gtail.ptr if d_gtail is not None else None, d_lines.ptr, n_lines, d_pvs.ptr,
                                          stream))
+
+    def rank_lines3_device(self, d_parents, n, d_offsets, d_moves, d_child_out, total, d_child_lines, d_child_pvs, n_lines,
+                           d_lines, d_pvs=None, stream=None, slot=0):
+        """gn_rank_lines3_device: d_lines[n * n_lines] (LINE3_DTYPE) from a preceding expand_device's
+        offsets, moves and child records and d_child_lines[total] (LINE2_DTYPE), each child's line 1 of
+        the two-ply ranking with it as the parent; d_pvs (with d_child_pvs, PV_DTYPE): [move] + the
+        child's PV.  Asynchronous.  The input buffers may be None when total is 0."""
+        p = lambda b: b.ptr if b is not None else None
+        _check(lib().gn_rank_lines3_device(self.h, slot, p(d_parents), n, p(d_offsets), p(d_moves), p(d_child_out), total,
+                                           p(d_child_lines), p(d_child_pvs), n_lines, p(d_lines), p(d_pvs), stream))
 
     def rank_children_extended_device(self, d_parents, n, d_offsets, d_moves, d_child_out, d_ext, n_lines, d_lines,
                                       d_keys=None, n_keys=0, d_hist=None, stream=None, slot=0):

@@ -224,6 +224,12 @@ extern "C" {
                                          gn_evaluate_games_lines[2]_quiescent_pv, summed over its
                                          chunks (the slowest device; 0 after any other
                                          host-buffer call)                                 */
+#define GN_STAT_RANK3_NS 130          /* rank_lines3_kernel in the last gn_evaluate_lines3 or
+                                         gn_evaluate_games_lines3, summed over its chunks (the
+                                         slowest device); 0 after any other host-buffer call.
+                                         The two-ply stages below the root feed GN_STAT_RANK2_NS,
+                                         GN_STAT_EXTEND_*, GN_STAT_QUIESCE_*, GN_STAT_PV_NS and
+                                         GN_STAT_HOST_* as they do for the two-ply calls       */
 #define GN_STAT_BATCH_LAUNCHES 117    /* merged gn_evaluate_batch launches since load ...   */
 #define GN_STAT_BATCH_CALLS 118       /* ... and the calls they served (GN_OPT_COALESCE)    */
 #define GN_STAT_FAST_BATCHES 119      /* evaluations run by the captured small-batch graphs
@@ -560,6 +566,65 @@ typedef struct gn_line2 { /* 16 bytes */
                      calls, reaches a position drawn by rule), 0 for an empty line         */
 } gn_line2;
 
+/* One ranked three-ply line of a position: p's move, the opponent's best reply and p's side's best
+ * answer to it, with the minimax value after three plies (fishnet's scores[multipv][depth] and
+ * pvs[multipv][depth] at depth 3).  gn_evaluate_lines3, gn_evaluate_games_lines3 and
+ * gn_rank_lines3_device return n_lines of them per position, 1 <= n_lines <= GN_MAX_LINES.  A gn_line2
+ * ends with the opponent to move and nothing of p's side behind it: it cannot see a mate in two, nor
+ * a quiet move that wins material a move later.  A three-ply line of p is a two-ply line of each child
+ * of p, negated.
+ * The leaf rule (the calls' `leaf` and `depth`) says how the positions after the third ply are valued:
+ *   GN_LEAF_STATIC   as gn_rank_lines2_device values its leaves (the rule at gn_line2);  depth 0
+ *   GN_LEAF_CHECKS   the check-extended rule (at gn_line, "check-extended");             depth 0
+ *   GN_LEAF_QUIESCE  the quiescent rule at `depth` (at gn_line, "quiescent lines"), Qs instead of Q
+ *                    when GN_OPT_QUIESCE_SEE is 1, read once when the call starts;       depth 1..
+ *                    GN_MAX_QUIESCE_DEPTH3: 3 + depth <= GN_MAX_PV, the PV and its tail fit a gn_pv
+ * The rule, for a position p a call evaluates (not bad, not skipped) with at least one legal move,
+ * over every legal move m with child c, under the call's leaf rule:
+ *   c has no legal move: R3(c) = -VALUE_MATE when c is in check (m mates), else 0 (m stalemates);
+ *   reply = reply2 = 0, plies = 1, GN_FLAG_NO_MOVES;
+ *   otherwise let L be line 1 of the two-ply ranking with c as the parent, under the same leaf rule
+ *   and with no history: R3(c) = L.value, reply = L.move, reply2 = L.reply, plies = 1 + L.plies;
+ *   GN_FLAG_NO_MOVES exactly when L carries it (the reply ends the game: plies == 2, reply2 == 0);
+ *   GN_FLAG_SEARCHED exactly when L carries it;
+ *   value(m) = negate_ply(R3(c)), score = rule_score(value, p's win-rate material), which sets
+ *   GN_FLAG_MATE: the same negate_ply and rule_score as everywhere else.  GN_FLAG_IN_CHECK is set
+ *   exactly when c is in check (m gives check).
+ * Lines are ordered by value descending, ties to the smaller `move`; reply and reply2 inherit the
+ * two-ply rule's ties.  Missing lines are empty, (0, 0, 0, 0, 0, GN_FLAG_NO_SCORE, 0, 0); a bad,
+ * skipped, checkmated or stalemated position has only empty lines.  GN_FLAG_DRAW never appears: these
+ * calls know no game history.
+ * A line's PV (gn_pv): an empty line has len 0; otherwise [move, reply, reply2][:plies], followed by
+ * PVQ(great-grandchild, depth) (PVQs under GN_OPT_QUIESCE_SEE) exactly when the leaf rule is
+ * GN_LEAF_QUIESCE, plies == 3 and the line carries GN_FLAG_SEARCHED.  Equivalently: [move] + the gn_pv
+ * of L.  The check extension's replies are not reported.
+ * Consequences:
+ *   - for a child c with a legal move, (R3(c), reply, reply2) is exactly line 1's (value, move, reply)
+ *     of gn_evaluate_lines2 (or its _extended / _quiescent form, by the leaf rule) for c's FEN at
+ *     n_lines = 1;
+ *   - `mate 2` appears on a mate in two, and `mate -2` on its defender's side, at plies == 3;
+ *   - a line that gets mated by the reply has plies == 2 and GN_FLAG_NO_MOVES (`mate -1`);
+ *   - played out from p, the PV ends in a position whose own value -- -VALUE_MATE (mated), 0
+ *     (stalemated) or its static final_v in the call's mode -- carried back by negate_ply once per
+ *     move of the PV, is the line's value. */
+#define GN_LEAF_STATIC 0  /* leaves by their static records (gn_line2's plain rule)          */
+#define GN_LEAF_CHECKS 1  /* leaves in check by the check extension (gn_line "check-extended") */
+#define GN_LEAF_QUIESCE 2 /* searched leaves by Q(x, depth), or Qs under GN_OPT_QUIESCE_SEE   */
+#define GN_MAX_QUIESCE_DEPTH3 (GN_MAX_PV - 3) /* 3: a three-ply PV plus its tail fits a gn_pv */
+typedef struct gn_line3 { /* 20 bytes */
+  int32_t value;     /* minimax value after three plies, p's side-to-move POV, Stockfish units  */
+  int32_t score;     /* rule_score(value, p's win-rate material): cp, or the mate distance with
+                        GN_FLAG_MATE                                                            */
+  uint16_t move;     /* p's move (Stockfish encoding, castling = king takes rook)               */
+  uint16_t reply;    /* the opponent's best reply; 0 when plies == 1                            */
+  uint16_t reply2;   /* p's side's best answer to it; 0 when plies <= 2                         */
+  uint16_t flags;    /* GN_FLAG_MATE; GN_FLAG_IN_CHECK: the move gives check; GN_FLAG_NO_MOVES: the
+                        move or the reply ends the game; GN_FLAG_SEARCHED: the leaf was valued by
+                        the leaf rule's search; GN_FLAG_NO_SCORE: an empty line                 */
+  uint16_t plies;    /* 3; 2 or 1 when the game ends earlier; 0 for an empty line               */
+  uint16_t reserved; /* 0 */
+} gn_line3;
+
 /* Packed position, 32 bytes, the device input format.
  *   occ      occupied squares (bit s = square s, a1 = 0 .. h8 = 63)
  *   pc       piece codes (Stockfish encoding: 1..6 white P N B R Q K, 9..14 black)
@@ -866,6 +931,31 @@ GN_API int gn_evaluate_games_lines_quiescent_pv(gn_ctx *ctx, const gn_game *game
                                                 int32_t *game_status, gn_eval *position_out, size_t position_cap,
                                                 gn_line *lines, gn_pv *pvs);
 
+/* Three-ply ranked lines (the rule at gn_line3): lines[i * n_lines + k] = line k + 1 of position i,
+ * pvs[i * n_lines + k] its gn_pv (pvs NULL: no PVs are made or downloaded); out as
+ * gn_evaluate_lines2's, byte for byte.  leaf is GN_LEAF_STATIC, GN_LEAF_CHECKS or GN_LEAF_QUIESCE;
+ * depth is 1..GN_MAX_QUIESCE_DEPTH3 with GN_LEAF_QUIESCE and 0 otherwise.  The FENs are sharded
+ * equally over the devices; each device runs its roots in chunks of exactly GN_OPT_CHUNK_PARENTS (0:
+ * 1,024): the chunk's depth-1 expansion into library-owned buffers, then its children as parents
+ * through gn_evaluate_lines2's chunk computation at n_lines = 1 under the leaf rule -- in chunks of
+ * the same number of children, cut wherever they fall, also inside one root's children -- their line
+ * 1 (and its gn_pv) staying on the device, then rank_lines3_kernel, then one download of the chunk's
+ * records, 20 * n_lines bytes of lines and, with pvs, 16 * n_lines bytes of PVs per position.  Results
+ * are identical for every chunk size, GN_OPT_EXPAND_PIPELINE and device count.  GN_E_INVALID: n_lines
+ * outside 1..GN_MAX_LINES, leaf outside 0..2, a depth the leaf rule does not take, NULL lines with
+ * n > 0.  GN_E_NOMEM / GN_E_CAPACITY from the quiescence as for gn_evaluate_lines2_quiescent: the
+ * context stays usable.  GN_STAT_RANK3_NS: the root kernel's time; the stages below it feed the
+ * two-ply calls' statistics. */
+GN_API int gn_evaluate_lines3(gn_ctx *ctx, const char *const *fens, size_t n, int mode, int n_lines, int leaf,
+                              int depth, gn_eval *out, gn_line3 *lines, gn_pv *pvs);
+/* The same from games: the front (replay, position_offsets, game_status, position_out,
+ * GN_E_CAPACITY) exactly as gn_evaluate_games_lines2, byte for byte; n_lines lines per position, equal
+ * to gn_evaluate_lines3's for the position's FEN.  The call knows no game history.  A skipped position
+ * has only empty lines (and PVs of len 0), a failed game no positions. */
+GN_API int gn_evaluate_games_lines3(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                    int leaf, int depth, uint32_t *position_offsets, int32_t *game_status,
+                                    gn_eval *position_out, size_t position_cap, gn_line3 *lines, gn_pv *pvs);
+
 /* The partitioner the library uses to shard work over the devices of a context and
  * that multi-process callers use to shard over ranks: contiguous ranges of n_items
  * items, bounds[k] = first item of shard k, bounds[n_shards] = n_items; shard k
@@ -1057,6 +1147,23 @@ GN_API int gn_rank_lines2_extended_device(gn_ctx *ctx, int device_slot, const gn
                                           const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
                                           const gn_history *d_hist, const int32_t *d_gext, int n_lines,
                                           gn_line2 *d_lines, void *stream);
+/* The root step of the three-ply lines alone (the rule at gn_line3): d_lines[i * n_lines + k] = line
+ * k + 1 of parent i, from the root expansion as gn_expand_device wrote it (d_offsets, d_moves,
+ * d_child_out: only the records' GN_FLAG_IN_CHECK is read) and d_child_lines[j] = line 1 of the
+ * two-ply ranking with child j as the parent (gn_rank_lines2_device or a form of it at n_lines = 1
+ * over the `total` children); an empty child line (GN_FLAG_NO_SCORE) is what "child j has no legal
+ * move" means, and no move is generated here.  d_pvs (NULL: none) needs d_child_pvs, the gn_pv of
+ * each child line (gn_line2_pvs_device): d_pvs[i * n_lines + k] = [move] + the child's PV.  Every
+ * child range is clamped to total, and nothing at or beyond total is read; a range longer than 256
+ * children (no position has more than 218 legal moves) is cut to its first 256.  One launch
+ * (rank_lines3_kernel), asynchronous on `stream` (NULL = the context's own), no read-back.
+ * n == 0: GN_OK, nothing is read or written; total == 0: GN_OK, no input buffer is read (they may
+ * be NULL) and every line is empty.  GN_E_INVALID: n_lines outside 1..GN_MAX_LINES, a NULL buffer
+ * that would be read or written, d_pvs without d_child_pvs. */
+GN_API int gn_rank_lines3_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                 const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out,
+                                 size_t total, const gn_line2 *d_child_lines, const gn_pv *d_child_pvs, int n_lines,
+                                 gn_line3 *d_lines, gn_pv *d_pvs, void *stream);
 /* Time `iters` complete expansions of device-resident parents (child count +
  * scan + child generation with deltas + evaluation of parents and children in
  * `mode` + the parents' score rule).  Outputs go to the caller's device buffers when given (d_parent_out[n],

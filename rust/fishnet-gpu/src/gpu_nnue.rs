@@ -24,6 +24,7 @@ pub use sys::gn_eval as GpuEval;
 pub use sys::gn_line as GpuLine;
 pub use sys::gn_line2 as GpuLine2;
 pub use sys::gn_pv as GpuPv;
+pub use sys::gn_line3 as GpuLine3;
 
 pub struct GpuNnue(*mut sys::gn_ctx);
 
@@ -432,6 +433,51 @@ impl GpuNnue {
             sys::gn_evaluate_games_lines2_quiescent_pv(self.0, gs.as_ptr(), gs.len(), mode, n_lines as i32,
                                                        history as i32, depth, offsets.as_mut_ptr(), status.as_mut_ptr(),
                                                        evals.as_mut_ptr(), cap, lines.as_mut_ptr(), pvs.as_mut_ptr())
+        })?;
+        let total = offsets[games.len()] as usize;
+        evals.truncate(total);
+        lines.truncate(total * n_lines);
+        pvs.truncate(total * n_lines);
+        Ok((offsets, status, evals, lines, pvs))
+    }
+
+    /// Three-ply ranked lines (gn_evaluate_lines3; the header at gn_line3): per FEN the best n_lines
+    /// lines of move, reply and the answer to it, valued after three plies under the leaf rule
+    /// (sys::LEAF_*; depth 1..=sys::MAX_QUIESCE_DEPTH3 with LEAF_QUIESCE, else 0), and each line's
+    /// whole variation: what `scores[multipv][depth]` / `pvs[multipv][depth]` take at depth 3.
+    #[allow(clippy::type_complexity)]
+    pub fn evaluate_lines3(&self, fens: &[Fen], n_lines: usize, leaf: i32, depth: i32, mode: i32)
+                           -> Result<(Vec<GpuEval>, Vec<GpuLine3>, Vec<GpuPv>), GpuError> {
+        let owned: Vec<CString> = fens.iter().map(|f| CString::new(f.to_string()).unwrap()).collect();
+        let ptrs: Vec<*const std::os::raw::c_char> = owned.iter().map(|c| c.as_ptr()).collect();
+        let mut evals = vec![GpuEval::default(); fens.len()];
+        let mut lines = vec![GpuLine3::default(); fens.len() * n_lines];
+        let mut pvs = vec![GpuPv::default(); fens.len() * n_lines];
+        // SAFETY: as evaluate_lines2_quiescent_pv; lines and pvs have fens.len() * n_lines elements.
+        check(unsafe {
+            sys::gn_evaluate_lines3(self.0, ptrs.as_ptr(), ptrs.len(), mode, n_lines as i32, leaf, depth,
+                                    evals.as_mut_ptr(), lines.as_mut_ptr(), pvs.as_mut_ptr())
+        })?;
+        Ok((evals, lines, pvs))
+    }
+
+    /// evaluate_lines3 from whole games (gn_evaluate_games_lines3): the front of
+    /// evaluate_games_lines2, three-ply lines and their PVs per position, no game history.
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn evaluate_games_lines3(&self, games: &[(CString, CString, Vec<u32>)], n_lines: usize, leaf: i32, depth: i32,
+                                 mode: i32)
+                                 -> Result<(Vec<u32>, Vec<i32>, Vec<GpuEval>, Vec<GpuLine3>, Vec<GpuPv>), GpuError> {
+        let (gs, cap) = games_and_capacity(games);
+        let mut offsets = vec![0u32; games.len() + 1];
+        let mut status = vec![0i32; games.len()];
+        let mut evals = vec![GpuEval::default(); cap];
+        let mut lines = vec![GpuLine3::default(); cap * n_lines];
+        let mut pvs = vec![GpuPv::default(); cap * n_lines];
+        // SAFETY: as evaluate_games_lines2_quiescent_pv.
+        check(unsafe {
+            sys::gn_evaluate_games_lines3(self.0, gs.as_ptr(), gs.len(), mode, n_lines as i32, leaf, depth,
+                                          offsets.as_mut_ptr(), status.as_mut_ptr(), evals.as_mut_ptr(), cap,
+                                          lines.as_mut_ptr(), pvs.as_mut_ptr())
         })?;
         let total = offsets[games.len()] as usize;
         evals.truncate(total);

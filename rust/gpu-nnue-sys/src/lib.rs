@@ -67,6 +67,7 @@ pub const GN_STAT_QUIESCE_NS: c_int = 126;
 pub const GN_STAT_QUIESCE_LEAVES: c_int = 127;
 pub const GN_STAT_QUIESCE_NODES: c_int = 128;
 pub const GN_STAT_PV_NS: c_int = 129;
+pub const GN_STAT_RANK3_NS: c_int = 130;
 
 // per-position flags
 pub const GN_FLAG_IN_CHECK: u16 = 1;
@@ -171,6 +172,30 @@ pub struct gn_line2 {
     pub reply: u16,
     pub flags: u16,
     pub plies: u16,
+}
+
+/// The three-ply calls' leaf rule (the header's GN_LEAF_*): static leaves, the check extension, or the
+/// capture quiescence to `depth` plies, 1..=MAX_QUIESCE_DEPTH3 (GN_MAX_QUIESCE_DEPTH3).
+pub const LEAF_STATIC: c_int = 0;
+pub const LEAF_CHECKS: c_int = 1;
+pub const LEAF_QUIESCE: c_int = 2;
+pub const MAX_QUIESCE_DEPTH3: c_int = 3;
+
+/// One ranked three-ply line of a position (20 bytes): `move`, the opponent's best `reply` and the
+/// side's best answer `reply2` with the minimax value after three plies and its score; plies is 3, or
+/// 2 / 1 when the game ends earlier (reply2 / reply 0, GN_FLAG_NO_MOVES); an empty line is
+/// (0, 0, 0, 0, 0, GN_FLAG_NO_SCORE, 0, 0); see the header at gn_line3.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct gn_line3 {
+    pub value: i32,
+    pub score: i32,
+    pub r#move: u16,
+    pub reply: u16,
+    pub reply2: u16,
+    pub flags: u16,
+    pub plies: u16,
+    pub reserved: u16,
 }
 
 /// Packed position (32 bytes), the device input format.
@@ -307,6 +332,13 @@ extern "C" {
                                                 position_offsets: *mut u32, game_status: *mut i32,
                                                 position_out: *mut gn_eval, position_cap: usize, lines: *mut gn_line,
                                                 pvs: *mut gn_pv) -> c_int;
+    pub fn gn_evaluate_lines3(ctx: *mut gn_ctx, fens: *const *const c_char, n: usize, mode: c_int, n_lines: c_int,
+                              leaf: c_int, depth: c_int, out: *mut gn_eval, lines: *mut gn_line3, pvs: *mut gn_pv)
+                              -> c_int;
+    pub fn gn_evaluate_games_lines3(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
+                                    n_lines: c_int, leaf: c_int, depth: c_int, position_offsets: *mut u32,
+                                    game_status: *mut i32, position_out: *mut gn_eval, position_cap: usize,
+                                    lines: *mut gn_line3, pvs: *mut gn_pv) -> c_int;
     pub fn gn_partition(weights: *const u32, n_items: usize, n_shards: c_int, bounds: *mut usize) -> c_int;
     pub fn gn_perft(ctx: *mut gn_ctx, fen: *const c_char, depth: c_int, nodes: *mut u64) -> c_int;
     pub fn gn_pack_fens(fens: *const *const c_char, n: usize, out: *mut gn_board, ok: *mut u8) -> c_int;
@@ -368,6 +400,10 @@ extern "C" {
                                d_moves: *const u16, d_goffsets: *const u32, d_gmoves: *const u16,
                                d_gtail: *const u16, d_lines: *const gn_line2, n_lines: c_int, d_pvs: *mut gn_pv,
                                stream: *mut c_void) -> c_int;
+    pub fn gn_rank_lines3_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                                 d_offsets: *const u32, d_moves: *const u16, d_child_out: *const gn_eval, total: usize,
+                                 d_child_lines: *const gn_line2, d_child_pvs: *const gn_pv, n_lines: c_int,
+                                 d_lines: *mut gn_line3, d_pvs: *mut gn_pv, stream: *mut c_void) -> c_int;
     pub fn gn_rank_children_extended_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
                                             d_offsets: *const u32, d_moves: *const u16, d_child_out: *const gn_eval,
                                             d_keys: *const u64, n_keys: usize, d_hist: *const gn_history,
