@@ -427,6 +427,7 @@ struct Dev {
     DevBuf<uint16_t> mv;
     DevBuf<gn_line2> cln;
     DevBuf<gn_pv> cpv;
+    DevBuf<gn_history> chist; // the history calls: each child's entry, its root's (launch_spread_history)
     DevBuf<gn_line3> ln;
     DevBuf<gn_pv> pv;
   } l3;
@@ -2388,7 +2389,7 @@ struct GamesArgs {
   int n_lines = 0;            // the lines calls: n_lines lines per position, no child reaches the host
   gn_line *lines = nullptr;   // ... one-ply (with_children 1: the children ranked on the device)
   gn_line2 *lines2 = nullptr; // ... or two-ply (with_children 0)
-  gn_line3 *lines3 = nullptr; // ... or three-ply (with_children 0; no history)
+  gn_line3 *lines3 = nullptr; // ... or three-ply (with_children 0)
   bool history = false;       // ... with the game-history draws
   LeafRule leaf;              // ... their leaves valued by this rule (extend_stage)
   gn_pv *pvs = nullptr;       // ... and each line's whole variation (the _pv calls)
@@ -3538,21 +3539,54 @@ int gn_rank_lines2_extended_device(gn_ctx *ctx, int device_slot, const gn_board 
                           d_gext, n_lines, d_lines, stream);
 }
 
-int gn_rank_lines3_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
-                          const uint16_t *d_moves, const gn_eval *d_child_out, size_t total, const gn_line2 *d_child_lines,
-                          const gn_pv *d_child_pvs, int n_lines, gn_line3 *d_lines, gn_pv *d_pvs, void *stream) {
+int gn_rank_lines2_ahead_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                const uint32_t *d_offsets, const gn_board *d_children, const gn_eval *d_child_out,
+                                const uint16_t *d_moves, const uint32_t *d_goffsets, const uint16_t *d_gmoves,
+                                const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
+                                const gn_history *d_hist, const int32_t *d_gext, int ahead, int n_lines,
+                                gn_line2 *d_lines, void *stream) {
+  if (ahead < 0 || ahead > 1) return fail(GN_E_INVALID, "ahead %d outside 0..1", ahead);
+  return rank_lines2_call(ctx, device_slot, d_parents, n, d_offsets, d_children, d_child_out, d_moves, d_goffsets,
+                          d_gmoves, d_grand_out,
+                          d_hist ? std::optional<RankHistory>({d_keys, n_keys, d_hist, (uint32_t)ahead}) : std::nullopt,
+                          d_gext, n_lines, d_lines, stream);
+}
+
+// gn_rank_lines3_device and its history form (h NULL: the plain kernel, d_children unread)
+static int rank_lines3_call(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
+                            const uint16_t *d_moves, const gn_eval *d_child_out, size_t total,
+                            const gn_line2 *d_child_lines, const gn_pv *d_child_pvs, const gn_board *d_children,
+                            const RankHistory *h, int n_lines, gn_line3 *d_lines, gn_pv *d_pvs, void *stream) {
   Dev *d = slot(ctx, device_slot);
   if (!d) return fail(GN_E_INVALID, "bad context or device slot");
   if (int rc = check_n_lines(n_lines)) return rc;
   if (d_pvs && !d_child_pvs) return fail(GN_E_INVALID, "d_pvs without d_child_pvs");
   if (n && !d_lines) return fail(GN_E_INVALID, "NULL buffer");
-  if (n && total && (!d_parents || !d_offsets || !d_moves || !d_child_out || !d_child_lines))
+  if (n && total && (!d_parents || !d_offsets || !d_moves || !d_child_out || !d_child_lines || (h && !d_children)))
     return fail(GN_E_INVALID, "NULL buffer");
+  if (n && total && h && h->n_keys && !h->keys) return fail(GN_E_INVALID, "d_keys is NULL");
   DevCall call(*d, stream);
   if (call.rc) return call.rc;
   HIP_TRY(launch_rank_lines3(d_parents, n, d_offsets, d_moves, d_child_out, total, d_child_lines, d_child_pvs, ctx->P,
-                             d->tables.p, n_lines, d_lines, d_pvs, call.s));
+                             d->tables.p, n_lines, d_lines, d_pvs, call.s, d_children, h));
   return GN_OK;
+}
+
+int gn_rank_lines3_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, const uint32_t *d_offsets,
+                          const uint16_t *d_moves, const gn_eval *d_child_out, size_t total, const gn_line2 *d_child_lines,
+                          const gn_pv *d_child_pvs, int n_lines, gn_line3 *d_lines, gn_pv *d_pvs, void *stream) {
+  return rank_lines3_call(ctx, device_slot, d_parents, n, d_offsets, d_moves, d_child_out, total, d_child_lines,
+                          d_child_pvs, nullptr, nullptr, n_lines, d_lines, d_pvs, stream);
+}
+
+int gn_rank_lines3_history_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                  const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out,
+                                  size_t total, const gn_line2 *d_child_lines, const gn_pv *d_child_pvs,
+                                  const gn_board *d_children, const uint64_t *d_keys, size_t n_keys,
+                                  const gn_history *d_hist, int n_lines, gn_line3 *d_lines, gn_pv *d_pvs, void *stream) {
+  const RankHistory h = {d_keys, n_keys, d_hist};
+  return rank_lines3_call(ctx, device_slot, d_parents, n, d_offsets, d_moves, d_child_out, total, d_child_lines,
+                          d_child_pvs, d_children, d_hist ? &h : nullptr, n_lines, d_lines, d_pvs, stream);
 }
 
 int gn_time_expand_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n, int mode, int iters,
@@ -3964,12 +3998,18 @@ static int lines2_chunks(gn_ctx *ctx, Dev &d, const gn_board *parents, size_t m,
 // A shard's three-ply lines (gn_evaluate_lines3, gn_evaluate_games_lines3; the rule at gn_line3): its
 // m device-resident roots in chunks of chunk roots.  Per chunk: the depth-1 expansion into the
 // device's Lines3 buffers (expand_level: the root records, the child boards, moves and records); the
-// children as parents through lines2_compute with K = 1, the call's leaf rule and no history, in
-// chunks of the same number of children, cut wherever they fall, each child's line 1 (and, with pvs,
-// its PV) written beside its record and never downloaded; rank_lines3_kernel; one download of the
-// chunk's root records, lines and (with pvs) PVs.
+// children as parents through lines2_compute with K = 1, the call's leaf rule and, without a history,
+// none, in chunks of the same number of children, cut wherever they fall, each child's line 1 (and,
+// with pvs, its PV) written beside its record and never downloaded; rank_lines3_kernel; one download
+// of the chunk's root records, lines and (with pvs) PVs.
+// history (gn_evaluate_games_lines3_history; hist NULL: none): the shard's keys and its roots'
+// gn_history entries.  A chunk's entries are spread to its children (launch_spread_history; its
+// device time is in no stage statistic, only in the host total), whose chunks index them as they
+// index the child boards and run the two-ply history ranking one ply ahead of the game
+// (RankHistory::ahead = 1); the root step is the history variant.  A drawn child's two-ply line is
+// computed all the same and dropped by the root step.
 static int lines3_chunks(gn_ctx *ctx, Dev &d, const gn_board *roots, size_t m, int mode, int K, gn_eval *out,
-                         gn_line3 *lines, LeafRule leaf, gn_pv *pvs) {
+                         gn_line3 *lines, const RankHistory &history, LeafRule leaf, gn_pv *pvs) {
   hipStream_t s = d.stream;
   Dev::Lines3 &x = d.l3;
   const size_t chunk = lines_chunk(ctx);
@@ -3992,15 +4032,22 @@ static int lines3_chunks(gn_ctx *ctx, Dev &d, const gn_board *roots, size_t m, i
     LevelOpts root;
     root.children = x.ch.p;
     if (int rc = expand_level(ctx, d, par, mp, mode, x.po.p, x.off.p, x.mv.p, x.co.p, cap, &t, s, root)) return rc;
+    const RankHistory h = {history.keys, history.n_keys, history.hist ? history.hist + a : nullptr};
+    if (h.hist) {
+      HIP_TRY(x.chist.ensure(cap));
+      HIP_TRY(launch_spread_history(h.hist, mp, x.off.p, t, x.chist.p, s));
+    }
     d.t_compute += ms_since(t0);
-    for (size_t b = 0; b < t; b += chunk) // (lines2_compute adds its own time)
-      if (int rc = lines2_compute(ctx, d, x.ch.p + b, std::min(chunk, t - b), mode, 1, NO_HISTORY, leaf, x.cln.p + b,
+    for (size_t b = 0; b < t; b += chunk) { // (lines2_compute adds its own time)
+      const RankHistory hc = {h.keys, h.n_keys, h.hist ? x.chist.p + b : nullptr, 1};
+      if (int rc = lines2_compute(ctx, d, x.ch.p + b, std::min(chunk, t - b), mode, 1, hc, leaf, x.cln.p + b,
                                   pvs ? x.cpv.p + b : nullptr))
         return rc;
+    }
     t0 = Clock::now();
     HIP_TRY(hipEventRecord(d.r3ev[0], s));
     HIP_TRY(launch_rank_lines3(par, mp, x.off.p, x.mv.p, x.co.p, t, x.cln.p, pvs ? x.cpv.p : nullptr, ctx->P, d.tables.p, K,
-                               x.ln.p, pvs ? x.pv.p : nullptr, s));
+                               x.ln.p, pvs ? x.pv.p : nullptr, s, x.ch.p, h.hist ? &h : nullptr));
     HIP_TRY(hipEventRecord(d.r3ev[1], s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0;
@@ -4059,7 +4106,7 @@ static int lines3_boards_host(gn_ctx *ctx, const gn_board *boards, size_t n, int
     HIP_TRY(hipMemcpyAsync(d.par.p, boards + lo, (hi - lo) * sizeof(gn_board), hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipStreamSynchronize(d.stream));
     d.t_upload += ms_since(t0);
-    return lines3_chunks(ctx, d, d.par.p, hi - lo, mode, K, out + lo, lines + lo * (size_t)K, leaf,
+    return lines3_chunks(ctx, d, d.par.p, hi - lo, mode, K, out + lo, lines + lo * (size_t)K, NO_HISTORY, leaf,
                          pvs ? pvs + lo * (size_t)K : nullptr);
   });
 }
@@ -4067,7 +4114,8 @@ static int games_lines3(const GamesCall &c, GameShard &sh, Dev &d) {
   const int rc = games_gather(c, sh, d);
   if (rc) return rc;
   gn_line3 *const ln = sh.in_place ? c.lines3 + sh.p0 * (size_t)c.n_lines : sh.l3res.data();
-  return lines3_chunks(c.ctx, d, sh.parents_of(d), sh.m, c.mode, c.n_lines, sh.records_of(c.position_out), ln, c.leaf,
+  return lines3_chunks(c.ctx, d, sh.parents_of(d), sh.m, c.mode, c.n_lines, sh.records_of(c.position_out), ln,
+                       c.history ? RankHistory{d.rkeys.p, d.n_rkeys, d.hist.p} : NO_HISTORY, c.leaf,
                        !c.pvs ? nullptr : sh.in_place ? c.pvs + sh.p0 * (size_t)c.n_lines : sh.pvres.data());
 }
 
@@ -4129,16 +4177,30 @@ int gn_evaluate_lines3(gn_ctx *ctx, const char *const *fens, size_t n, int mode,
   });
 }
 
-int gn_evaluate_games_lines3(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines, int leaf,
-                             int depth, uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
-                             size_t position_cap, gn_line3 *lines, gn_pv *pvs) {
+static int evaluate_games_lines3(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines, int leaf,
+                                 int depth, bool history, uint32_t *position_offsets, int32_t *game_status,
+                                 gn_eval *position_out, size_t position_cap, gn_line3 *lines, gn_pv *pvs) {
   if (!slot(ctx, 0)) return fail(GN_E_INVALID, "bad context");
   if (int rc = check_n_lines(n_lines)) return rc;
   LeafRule rule;
   if (int rc = leaf_rule3(ctx, leaf, depth, rule)) return rc;
   if (n_games && !lines) return fail(GN_E_INVALID, "lines is NULL");
-  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, false, rule, position_offsets, game_status,
+  return evaluate_games_lines(ctx, games, n_games, mode, n_lines, history, rule, position_offsets, game_status,
                               position_out, position_cap, lines, pvs);
+}
+
+int gn_evaluate_games_lines3(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines, int leaf,
+                             int depth, uint32_t *position_offsets, int32_t *game_status, gn_eval *position_out,
+                             size_t position_cap, gn_line3 *lines, gn_pv *pvs) {
+  return evaluate_games_lines3(ctx, games, n_games, mode, n_lines, leaf, depth, false, position_offsets, game_status,
+                               position_out, position_cap, lines, pvs);
+}
+
+int gn_evaluate_games_lines3_history(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines, int leaf,
+                                     int depth, uint32_t *position_offsets, int32_t *game_status,
+                                     gn_eval *position_out, size_t position_cap, gn_line3 *lines, gn_pv *pvs) {
+  return evaluate_games_lines3(ctx, games, n_games, mode, n_lines, leaf, depth, true, position_offsets, game_status,
+                               position_out, position_cap, lines, pvs);
 }
 
 int gn_perft(gn_ctx *ctx, const char *fen, int depth, uint64_t *nodes) {

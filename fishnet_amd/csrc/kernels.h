@@ -295,10 +295,14 @@ hipError_t launch_pack_children(const gn_eval *in, size_t n, gn_child *out, hipS
 // parent i's game so far in keys[0, n_keys) (position_key of each position).  NULL: the plain ranking.
 // With ext (include/gpu_nnue.h, the check-extended calls): ext[c] is child c's check extension, or
 // GN_NOT_EXTENDED where it keeps its static value.  NULL: no extension, today's kernels.
+// ahead (rank_lines2_kernel alone; 0 or 1): the plies parent i lies after keys[hist[i].self].  1 is the
+// three-ply chain, whose parents are the children of a game's position (include/gpu_nnue.h at
+// gn_line3, "game history"); every other ranking kernel ignores it.
 struct RankHistory {
   const uint64_t *keys;
   size_t n_keys;
   const gn_history *hist;
+  uint32_t ahead = 0;
 };
 hipError_t launch_rank_children(const Board *unpacked, size_t n, const uint64_t *offsets, const uint16_t *moves,
                                 const gn_eval *rec, const gn_eval_params &P, const Tables *tables, int K,
@@ -331,10 +335,19 @@ hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t 
 // with pvs (NULL: none) pvs[i * K + k] = [move] + cpvs[the line's child].  One launch, no move
 // generation, no scratch memory; every child range is clamped to total, and with total == 0 no input
 // but n is read.
+// history (NULL: the plain kernel, which takes no child board): hist[i] names root i's game so far; a
+// child (children[c], the library's own boards) whose line is not empty and that is drawn by rule
+// against that window overrides its line (value 0, GN_FLAG_DRAW, plies 1), and a child line's
+// GN_FLAG_DRAW passes into the root's.
 hipError_t launch_rank_lines3(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
                               const gn_eval *rec, size_t total, const gn_line2 *clines, const gn_pv *cpvs,
                               const gn_eval_params &P, const Tables *tables, int K, gn_line3 *lines, gn_pv *pvs,
-                              hipStream_t s);
+                              hipStream_t s, const gn_board *children = nullptr, const RankHistory *history = nullptr);
+// chist[j] = hist[i] for every child j in [offsets[i], offsets[i + 1]) of the n roots, the ranges
+// clamped to total as rank_lines3_kernel clamps them (total == 0: nothing is read): the children's
+// gn_history entries for the two-ply stage of the three-ply history calls (RankHistory::ahead = 1)
+hipError_t launch_spread_history(const gn_history *hist, size_t n, const uint32_t *offsets, size_t total,
+                                 gn_history *chist, hipStream_t s);
 // Check extension of one expansion level (gpu_nnue.hip extend_checks): select (sel[total + 1] from
 // the leaf records' GN_FLAG_IN_CHECK, ext[total] = GN_NOT_EXTENDED), boards (pos = exclusive scan of
 // sel: the selected leaves' boards sb, leaf indices idx and sv = GN_NOT_EXTENDED, compacted; the

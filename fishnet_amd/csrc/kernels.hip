@@ -1354,6 +1354,17 @@ hipError_t launch_position_keys(const gn_board *boards, size_t n, bool gate, con
 // bits, the other fields one bit higher: (value + 32768) << 35 | (0xFFFF - move) << 19 |
 // reply << 3 | draw << 2 | no-moves << 1 | in-check.  A child without a reply to show (none, or
 // drawn) has reply 0, a legal reply's encoding is never 0: plies is reply ? 2 : 1.
+// Ahead of the game (RankHistory::ahead, 0 or 1, uniform; the three-ply chain's children as parents):
+// the parent lies `ahead` plies after keys[self], and is itself no key of the array.  The window moves
+// with it: a parent with a history (len > 0) takes self + ahead for self and len + ahead for len, so a
+// child is tested below keys + self + 1 + ahead over len + ahead keys and a grandchild below
+// keys + self + 2 + ahead over len + ahead + 1; no history stays none at both levels.  The parity holds
+// (the child is d plies after (keys + self + 1 + ahead)[-d] as before), and the parent, which the
+// window skips, has the other side to move than its child and is two plies from its grandchild:
+// neither test could have counted it.  Indices: a reader forms newest_plus_1 - d with
+// 4 <= d <= length only, that is [self + 1 - len, self + ahead - 3] for a child and
+// [self + 1 - len, self + ahead - 2] for a grandchild: never below first = self + 1 - len, and with
+// ahead <= 1 never above self - 1 < n_keys.  ahead == 0 leaves every address and every byte as they were.
 //
 // Extended variant (EXT; include/gpu_nnue.h at gn_line2, "check-extended"): a second optional
 // trailing RankExtension over the grandchildren.  A grandchild that has a legal move, is not drawn by
@@ -1385,7 +1396,11 @@ __global__ void __launch_bounds__(RANK_WG)
     }
     uint64_t top = 0; // lane k: this group's k-th best child key so far (0: none)
     HistWindow hw = {0, 0}; // HIST: the parent's game so far (len 0: no history)
-    if constexpr (HIST) hw = hist_window(arg_of<RankHistory>(extra...), p);
+    if constexpr (HIST) {
+      hw = hist_window(arg_of<RankHistory>(extra...), p);
+      const uint32_t ahead = arg_of<RankHistory>(extra...).ahead; // (uniform) the window `ahead` plies further on
+      if (hw.len) hw.self += ahead, hw.len += ahead;
+    }
     const uint32_t glen = hw.len ? hw.len + 1 : 0u; // the window as a grandchild counts it, a ply further on
     for (uint64_t cb = c0; cb < c1; cb += GROUPS) {
       const uint64_t c = cb + q;
@@ -1516,13 +1531,33 @@ hipError_t launch_rank_lines2(const gn_board *parents, size_t n, const uint32_t 
 // order, and leads lanes 0..K-1 back to the winning child's line for reply, reply2, plies and flags
 // and, with pvs, to its gn_pv: the line's PV is [move] + the child's, written by the same lane.
 // Every child range is clamped to total; with total == 0 not even the offsets are read.
-using Root3Key = SortKey<24, 1>;
+//
+// History variant (HIST; include/gpu_nnue.h at gn_line3, "game history"), chosen like the other ranking
+// kernels' by an optional trailing RankHistory, followed here by the child boards (Root3Children), so
+// the plain instantiation keeps its arguments and its bytes.  The root's window (hist_window) is read
+// once per root.  A lane whose child's line is not empty -- the child has a legal move -- unpacks the
+// child (the library's own board: unpack_fields) and tests it with drawn_by_rule against the root's
+// window, the child being one ply after keys[self]; the test sits where the lane makes its key, before
+// top_k_rounds and outside every shuffle.  A drawn child's line is dropped: R3 = 0, and a draw bit rides
+// in the key above the check bit, (value + 32768) << 26 | (0xFFFF - move) << 10 | index << 2 |
+// draw << 1 | in-check; the winning lane then writes reply = reply2 = 0, plies = 1, GN_FLAG_DRAW and
+// the PV [move].  A child that is not drawn passes its line's GN_FLAG_DRAW on.
+template <bool HIST> using Root3Key = SortKey<24, HIST ? 2 : 1>;
+constexpr uint32_t ROOT3_DRAW = 2; // (above KEY_CHECK)
 constexpr uint32_t ROOT3_MAX_SEGMENT = 256;
+struct Root3Children {
+  const gn_board *boards;
+};
+template <class... Extra>
 __global__ void __launch_bounds__(RANK_WG)
     rank_lines3_kernel(const gn_board *__restrict__ parents, size_t n, const uint32_t *__restrict__ offsets,
                        const uint16_t *__restrict__ moves, const gn_eval *__restrict__ rec, size_t total,
                        const gn_line2 *__restrict__ clines, const gn_pv *__restrict__ cpvs, gn_eval_params P,
-                       const Tables *__restrict__ tables, int K, gn_line3 *__restrict__ lines, gn_pv *__restrict__ pvs) {
+                       const Tables *__restrict__ tables, int K, gn_line3 *__restrict__ lines, gn_pv *__restrict__ pvs,
+                       Extra... extra) {
+  constexpr bool HIST = has_arg<RankHistory, Extra...>;
+  static_assert(sizeof...(Extra) == (HIST ? 2 : 0), "nothing, or a RankHistory and the child boards");
+  using Key = Root3Key<HIST>;
   __shared__ Tables T;
   load_tables(T, tables);
   constexpr int W = GN_RANK_WIDTH;
@@ -1537,14 +1572,26 @@ __global__ void __launch_bounds__(RANK_WG)
     uint64_t top = 0; // lanes 0..K-1: the running top K (0: none yet)
     Board B;
     const bool ok = c1 > c0 && unpack(parents[p], B, T);
+    HistWindow hw = {0, 0}; // HIST: the root's game so far (len 0: no history)
+    if constexpr (HIST) {
+      if (ok) hw = hist_window(arg_of<RankHistory>(extra...), p);
+    }
     for (uint64_t c = c0; ok && c < c1; c += W) {
       uint64_t key = 0;
       if (c + lane < c1) {
         const uint32_t mv = moves[c + lane];
         const uint32_t check = (rec[c + lane].flags & GN_FLAG_IN_CHECK) ? KEY_CHECK : 0u;
         const gn_line2 L = clines[c + lane];
-        const int32_t R = (L.flags & GN_FLAG_NO_SCORE) ? (check ? -VALUE_MATE : 0) : L.value;
-        key = Root3Key::pack(negate_ply(R), (uint64_t)(0xFFFFu - mv) << 8 | (uint32_t)(c + lane - c0), check);
+        const bool none = L.flags & GN_FLAG_NO_SCORE;
+        uint32_t draw = 0;
+        if constexpr (HIST) {
+          Board C;
+          if (!none && unpack_fields(arg_of<Root3Children>(extra...).boards[c + lane], C) &&
+              drawn_by_rule(C, arg_of<RankHistory>(extra...).keys + ((size_t)hw.self + 1), hw.len))
+            draw = ROOT3_DRAW;
+        }
+        const int32_t R = none ? (check ? -VALUE_MATE : 0) : draw ? 0 : L.value;
+        key = Key::pack(negate_ply(R), (uint64_t)(0xFFFFu - mv) << 8 | (uint32_t)(c + lane - c0), draw | check);
       }
       top = top_k_rounds<W>(key, top, lane, K);
     }
@@ -1552,13 +1599,16 @@ __global__ void __launch_bounds__(RANK_WG)
       gn_line3 l = {0, 0, 0, 0, 0, (uint16_t)GN_FLAG_NO_SCORE, 0, 0};
       gn_pv pv = {};
       if (top) {
-        const uint64_t j = c0 + (Root3Key::payload(top) & 0xFFu);
+        const uint64_t j = c0 + (Key::payload(top) & 0xFFu);
         const gn_line2 L = clines[j];
-        const bool none = L.flags & GN_FLAG_NO_SCORE;
-        uint32_t fl = (Root3Key::flags(top) ? GN_FLAG_IN_CHECK : 0u) |
-                      (none ? GN_FLAG_NO_MOVES : L.flags & (GN_FLAG_NO_MOVES | GN_FLAG_SEARCHED));
-        l.value = Root3Key::value(top);
-        l.move = (uint16_t)(0xFFFFu - (Root3Key::payload(top) >> 8));
+        const bool drawn = HIST && (Key::flags(top) & ROOT3_DRAW); // the child is the draw: its line is dropped
+        const bool none = drawn || (L.flags & GN_FLAG_NO_SCORE);   // the line ends at the child
+        uint32_t fl = ((Key::flags(top) & KEY_CHECK) ? GN_FLAG_IN_CHECK : 0u) |
+                      (drawn  ? GN_FLAG_DRAW
+                       : none ? GN_FLAG_NO_MOVES
+                              : L.flags & (GN_FLAG_NO_MOVES | GN_FLAG_SEARCHED | (HIST ? GN_FLAG_DRAW : 0u)));
+        l.value = Key::value(top);
+        l.move = (uint16_t)(0xFFFFu - (Key::payload(top) >> 8));
         l.reply = none ? 0 : L.move;
         l.reply2 = none ? 0 : L.reply;
         l.plies = (uint16_t)(none ? 1 : 1 + L.plies);
@@ -1583,12 +1633,44 @@ __global__ void __launch_bounds__(RANK_WG)
 hipError_t launch_rank_lines3(const gn_board *parents, size_t n, const uint32_t *offsets, const uint16_t *moves,
                               const gn_eval *rec, size_t total, const gn_line2 *clines, const gn_pv *cpvs,
                               const gn_eval_params &P, const Tables *tables, int K, gn_line3 *lines, gn_pv *pvs,
-                              hipStream_t s) {
+                              hipStream_t s, const gn_board *children, const RankHistory *history) {
   if (!n) return hipSuccess;
   constexpr size_t per_wg = RANK_WG / GN_RANK_WIDTH, max_blocks = 8192;
   const size_t blocks = std::min<size_t>((n + per_wg - 1) / per_wg, max_blocks);
-  hipLaunchKernelGGL(rank_lines3_kernel, dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets, moves, rec, total, clines,
-                     cpvs, P, tables, K, lines, pvs);
+  if (history)
+    hipLaunchKernelGGL((rank_lines3_kernel<RankHistory, Root3Children>), dim3(blocks), dim3(RANK_WG), 0, s, parents, n,
+                       offsets, moves, rec, total, clines, cpvs, P, tables, K, lines, pvs, *history,
+                       Root3Children{children});
+  else
+    hipLaunchKernelGGL(rank_lines3_kernel<>, dim3(blocks), dim3(RANK_WG), 0, s, parents, n, offsets, moves, rec, total,
+                       clines, cpvs, P, tables, K, lines, pvs);
+  return hipGetLastError();
+}
+
+// The children's gn_history entries for the two-ply stage below a root chunk (gpu_nnue.hip
+// lines3_chunks): chist[j] = hist[i] for each child j of root i, a group of 32 lanes per root, the
+// ranges clamped to total as above, so no entry at or beyond total is written and with total == 0
+// nothing is read.
+__global__ void __launch_bounds__(256)
+    spread_history_kernel(const gn_history *__restrict__ hist, size_t n, const uint32_t *__restrict__ offsets, size_t total,
+                          gn_history *__restrict__ chist) {
+  constexpr int W = 32;
+  if (!total) return;
+  const int lane = threadIdx.x & (W - 1);
+  const size_t stride = (size_t)gridDim.x * (256 / W);
+  for (size_t p = (size_t)blockIdx.x * (256 / W) + threadIdx.x / W; p < n; p += stride) {
+    const uint64_t c1 = std::min<uint64_t>(offsets[p + 1], total), c0 = std::min<uint64_t>(offsets[p], c1);
+    if (c0 == c1) continue;
+    const gn_history e = hist[p];
+    for (uint64_t c = c0 + lane; c < c1; c += W) chist[c] = e;
+  }
+}
+hipError_t launch_spread_history(const gn_history *hist, size_t n, const uint32_t *offsets, size_t total,
+                                 gn_history *chist, hipStream_t s) {
+  if (!n || !total) return hipSuccess;
+  constexpr size_t per_wg = 256 / 32, max_blocks = 8192;
+  const size_t blocks = std::min<size_t>((n + per_wg - 1) / per_wg, max_blocks);
+  hipLaunchKernelGGL(spread_history_kernel, dim3(blocks), dim3(256), 0, s, hist, n, offsets, total, chist);
   return hipGetLastError();
 }
 

@@ -80,7 +80,8 @@ EXPORTS = ["gn_load_net", "gn_load_net_memory", "gn_free", "gn_last_error", "gn_
            "gn_quiesce_pv_device", "gn_line_pvs_device", "gn_line2_pvs_device", "gn_evaluate_lines2_quiescent_pv",
            "gn_evaluate_games_lines2_quiescent_pv", "gn_evaluate_games_lines_quiescent_pv",
            "gn_see_moves", "gn_see_device",
-           "gn_evaluate_lines3", "gn_evaluate_games_lines3", "gn_rank_lines3_device"]
+           "gn_evaluate_lines3", "gn_evaluate_games_lines3", "gn_rank_lines3_device",
+           "gn_evaluate_games_lines3_history", "gn_rank_lines3_history_device", "gn_rank_lines2_ahead_device"]
 OPT_INCREMENTAL_CHILDREN, OPT_XCD_SWIZZLE, OPT_KING_SORT, OPT_CHAIN, OPT_KING_CACHE = 1, 2, 3, 4, 5
 OPT_CHUNK_PARENTS, OPT_COALESCE, OPT_STREAM_SLICES, OPT_FAST_BATCH, OPT_EXPAND_PIPELINE = 6, 7, 8, 9, 10
 OPT_QUIESCE_SEE = 11  # 1: the quiescent calls prune the noisy moves with see < 0 (the one option that changes results)
@@ -241,6 +242,9 @@ def lib():
         "gn_evaluate_lines3": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp],
         "gn_evaluate_games_lines3": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp, vp],
         "gn_rank_lines3_device": [vp, i32, vp, sz, vp, vp, vp, sz, vp, vp, i32, vp, vp, vp],
+        "gn_evaluate_games_lines3_history": [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp, vp],
+        "gn_rank_lines3_history_device": [vp, i32, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, i32, vp, vp, vp],
+        "gn_rank_lines2_ahead_device": [vp, i32, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, i32, i32, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -694,13 +698,21 @@ class GpuNnue:
                                         pv.ctypes.data if pvs else None))
         return out, lines, pv
 
-    def evaluate_games_lines3(self, games, n_lines, leaf=LEAF_STATIC, depth=0, mode=MODE_FULL, cap=None, pvs=True):
+    def evaluate_games_lines3(self, games, n_lines, leaf=LEAF_STATIC, depth=0, mode=MODE_FULL, cap=None, pvs=True,
+                              history=False):
         """gn_evaluate_games_lines3: evaluate_games_lines2 with three-ply lines (LINE3_DTYPE) under the
-        leaf rule, without game history: (offsets, status, positions, lines, pvs or None)."""
-        f = lib().gn_evaluate_games_lines3
+        leaf rule: (offsets, status, positions, lines, pvs or None).  history:
+        gn_evaluate_games_lines3_history (draws by repetition and the fifty-move rule at the child, the
+        reply and the answer, FLAG_DRAW; plies tells them apart); else without game history."""
+        f = lib().gn_evaluate_games_lines3_history if history else lib().gn_evaluate_games_lines3
         call = lambda h, arr, ng, mode, K, *rest: f(h, arr, ng, mode, K, leaf, depth, *rest, *(() if pvs else (None,)))
         res = self._games_lines(call, LINE3_DTYPE, games, n_lines, mode, cap, pvs=pvs)
         return res if pvs else res + (None,)
+
+    def evaluate_games_lines3_history(self, games, n_lines, leaf=LEAF_STATIC, depth=0, mode=MODE_FULL, cap=None,
+                                      pvs=True):
+        """gn_evaluate_games_lines3_history: evaluate_games_lines3 with each game's history."""
+        return self.evaluate_games_lines3(games, n_lines, leaf, depth, mode, cap, pvs, history=True)
 
     def host_stages(self):
         """Stage times (ms) of the last gn_evaluate_games / gn_expand_and_evaluate (GN_STAT_HOST_*)."""
@@ -869,6 +881,27 @@ class GpuNnue:
         p = lambda b: b.ptr if b is not None else None
         _check(lib().gn_rank_lines3_device(self.h, slot, p(d_parents), n, p(d_offsets), p(d_moves), p(d_child_out), total,
                                            p(d_child_lines), p(d_child_pvs), n_lines, p(d_lines), p(d_pvs), stream))
+
+    def rank_lines3_history_device(self, d_parents, n, d_offsets, d_moves, d_child_out, total, d_child_lines, d_child_pvs,
+                                   d_children, d_keys, n_keys, d_hist, n_lines, d_lines, d_pvs=None, stream=None, slot=0):
+        """gn_rank_lines3_history_device: rank_lines3_device with the game-history draws at the child:
+        d_children (the root expansion's child boards), d_hist[n] (HISTORY_DTYPE) naming each parent's
+        game so far in d_keys[n_keys]; d_hist None: no history at all.  Asynchronous."""
+        p = lambda b: b.ptr if b is not None else None
+        _check(lib().gn_rank_lines3_history_device(self.h, slot, p(d_parents), n, p(d_offsets), p(d_moves), p(d_child_out),
+                                                   total, p(d_child_lines), p(d_child_pvs), p(d_children), p(d_keys),
+                                                   n_keys, p(d_hist), n_lines, p(d_lines), p(d_pvs), stream))
+
+    def rank_lines2_ahead_device(self, d_parents, n, out, d_gext, ahead, n_lines, d_lines, d_keys=None, n_keys=0,
+                                 d_hist=None, stream=None, slot=0):
+        """gn_rank_lines2_ahead_device: rank_lines2_extended_device whose parents lie `ahead` (0 or 1)
+        plies after the position their d_hist entry names (1: the three-ply chain's children as
+        parents).  Asynchronous."""
+        p = lambda k: out[k].ptr if out.get(k) is not None else None
+        q = lambda b: b.ptr if b is not None else None
+        _check(lib().gn_rank_lines2_ahead_device(self.h, slot, d_parents.ptr, n, p("off"), p("ch"), p("co"), p("mv"),
+                                                 p("goff"), p("gmv"), p("gco"), q(d_keys), n_keys, q(d_hist), q(d_gext),
+                                                 ahead, n_lines, d_lines.ptr, stream))
 
     def rank_children_extended_device(self, d_parents, n, d_offsets, d_moves, d_child_out, d_ext, n_lines, d_lines,
                                       d_keys=None, n_keys=0, d_hist=None, stream=None, slot=0):

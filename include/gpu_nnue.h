@@ -195,8 +195,9 @@ extern "C" {
                                          over its chunks (0 after any other host-buffer
                                          call)                                             */
 #define GN_STAT_KEYS_NS 123           /* position_keys_kernel in the last
-                                         gn_evaluate_games_lines_history or
-                                         gn_evaluate_games_lines2_history (the slowest
+                                         gn_evaluate_games_lines_history,
+                                         gn_evaluate_games_lines2_history or
+                                         gn_evaluate_games_lines3_history (the slowest
                                          device; 0 after any other host-buffer call)       */
 #define GN_STAT_RANK2_NS 122          /* rank_lines2_kernel in the last gn_evaluate_lines2 or
                                          gn_evaluate_games_lines2, or its history variant in
@@ -225,8 +226,10 @@ extern "C" {
                                          chunks (the slowest device; 0 after any other
                                          host-buffer call)                                 */
 #define GN_STAT_RANK3_NS 130          /* rank_lines3_kernel in the last gn_evaluate_lines3 or
-                                         gn_evaluate_games_lines3, summed over its chunks (the
-                                         slowest device); 0 after any other host-buffer call.
+                                         gn_evaluate_games_lines3, or its history variant in the
+                                         last gn_evaluate_games_lines3_history, summed over its
+                                         chunks (the slowest device); 0 after any other
+                                         host-buffer call.
                                          The two-ply stages below the root feed GN_STAT_RANK2_NS,
                                          GN_STAT_EXTEND_*, GN_STAT_QUIESCE_*, GN_STAT_PV_NS and
                                          GN_STAT_HOST_* as they do for the two-ply calls       */
@@ -253,9 +256,10 @@ extern "C" {
                                  calls only: the line's leaf is valued by that rule;
                                  of the quiescent calls: by the quiescence Q(x, depth) */
 #define GN_FLAG_NO_MOVES 256u /* no legal move: checkmate (with IN_CHECK) or stalemate */
-#define GN_FLAG_DRAW 512u /* gn_line.flags and gn_line2.flags of the history calls only: the
-                             line ends in a position drawn by rule (threefold repetition or
-                             fifty-move rule; gn_history and gn_line2 below)            */
+#define GN_FLAG_DRAW 512u /* gn_line.flags, gn_line2.flags and gn_line3.flags of the history
+                             calls only: the line ends in a position drawn by rule (threefold
+                             repetition or fifty-move rule; gn_history, gn_line2 and gn_line3
+                             below)                                                     */
 
 /* One result.  psqt/positional are Network::evaluate's NetworkOutput (already
  * divided by OutputScale = 16) of the net that produced final_v; final_v is
@@ -592,8 +596,8 @@ typedef struct gn_line2 { /* 16 bytes */
  *   exactly when c is in check (m gives check).
  * Lines are ordered by value descending, ties to the smaller `move`; reply and reply2 inherit the
  * two-ply rule's ties.  Missing lines are empty, (0, 0, 0, 0, 0, GN_FLAG_NO_SCORE, 0, 0); a bad,
- * skipped, checkmated or stalemated position has only empty lines.  GN_FLAG_DRAW never appears: these
- * calls know no game history.
+ * skipped, checkmated or stalemated position has only empty lines.  GN_FLAG_DRAW never appears in
+ * these three calls: they know no game history ("game history" below is the form that does).
  * A line's PV (gn_pv): an empty line has len 0; otherwise [move, reply, reply2][:plies], followed by
  * PVQ(great-grandchild, depth) (PVQs under GN_OPT_QUIESCE_SEE) exactly when the leaf rule is
  * GN_LEAF_QUIESCE, plies == 3 and the line carries GN_FLAG_SEARCHED.  Equivalently: [move] + the gn_pv
@@ -606,7 +610,44 @@ typedef struct gn_line2 { /* 16 bytes */
  *   - a line that gets mated by the reply has plies == 2 and GN_FLAG_NO_MOVES (`mate -1`);
  *   - played out from p, the PV ends in a position whose own value -- -VALUE_MATE (mated), 0
  *     (stalemated) or its static final_v in the call's mode -- carried back by negate_ply once per
- *     move of the PV, is the line's value. */
+ *     move of the PV, is the line's value.
+ * Game history (gn_evaluate_games_lines3_history, gn_rank_lines3_history_device; GN_FLAG_DRAW is valid
+ * on gn_line3.flags for these calls only).  Position k of a game has the history of gn_history above:
+ * positions 0..=k, skipped ones included; nothing before the root FEN is known.  A position x that is
+ * the child, grandchild or great-grandchild of position k is drawn by rule when it has a legal move
+ * and x.rule50 >= 100 or x's identity equals that of at least two of positions 0..=k.  For a legal
+ * move m of position k with child c, in this order of precedence:
+ *   1. c has no legal move: nothing changes (plies = 1, GN_FLAG_NO_MOVES, no GN_FLAG_DRAW).
+ *   2. c is drawn by rule: R3(c) = 0, reply = reply2 = 0, plies = 1, GN_FLAG_DRAW, GN_FLAG_IN_CHECK if
+ *      m gives check, no GN_FLAG_NO_MOVES and no GN_FLAG_SEARCHED.  c's two-ply line is not consulted
+ *      (it is computed all the same, and dropped by the root step).
+ *   3. otherwise let L be line 1 of the two-ply history ranking (the rule at gn_line2, "with the
+ *      game-history draws") with c as the parent, under the call's leaf rule, where c's game so far is
+ *      positions 0..=k followed by c: R3(c) = L.value, reply = L.move, reply2 = L.reply,
+ *      plies = 1 + L.plies, and GN_FLAG_NO_MOVES, GN_FLAG_SEARCHED and GN_FLAG_DRAW exactly when L
+ *      carries them.
+ * A drawn line has value 0 and score 0; plies tells the three kinds apart (1: the child is the draw;
+ * 2: the reply reaches it; 3: the answer reaches it).  Value, score, order, ties and empty lines are
+ * unchanged, and so is the precedence inside the leaf (no legal move, then drawn by rule, then the leaf
+ * rule's search, then static), which is the two-ply history rule's; the check extension and the
+ * quiescence know no history inside their own trees.  PV: [move, reply, reply2][:plies]; the
+ * quiescence's tail follows only when plies == 3 and the line carries GN_FLAG_SEARCHED, which a drawn
+ * leaf never does.
+ * Why "third occurrence against 0..=k" is the whole rule at ply 3 as well (extending the paragraph at
+ * gn_line2): two positions of equal identity have the same side to move, and no pair of moves, one by
+ * each side, restores a position, so equal positions are at least 4 plies apart; at ply <= 3 the
+ * earlier occurrence therefore always lies at or before the root, Stockfish's "single repetition after
+ * the root" cannot trigger, and neither c nor the grandchild g can be one of the occurrences that
+ * count for a position below them.  For a grandchild the kernel tests positions k + 2 - d and for a
+ * great-grandchild k + 3 - d, d = 4, 6, ... up to min(rule50, k + 2) and min(rule50, k + 3).
+ * Consequences:
+ *   (a) for a child c that has a legal move and is not drawn, (R3(c), reply, reply2) and L's flags are
+ *       line 1 at position k + 1 of gn_evaluate_games_lines2_history (its _extended / _quiescent form
+ *       with history = 1 when the leaf rule is not static) for the same game with m appended;
+ *   (b) where nothing is drawn at any of the three levels, the lines are byte-equal to
+ *       gn_evaluate_games_lines3's;
+ *   (c) position_offsets, game_status and position_out are byte-equal to gn_evaluate_games_lines3's
+ *       always. */
 #define GN_LEAF_STATIC 0  /* leaves by their static records (gn_line2's plain rule)          */
 #define GN_LEAF_CHECKS 1  /* leaves in check by the check extension (gn_line "check-extended") */
 #define GN_LEAF_QUIESCE 2 /* searched leaves by Q(x, depth), or Qs under GN_OPT_QUIESCE_SEE   */
@@ -620,8 +661,10 @@ typedef struct gn_line3 { /* 20 bytes */
   uint16_t reply2;   /* p's side's best answer to it; 0 when plies <= 2                         */
   uint16_t flags;    /* GN_FLAG_MATE; GN_FLAG_IN_CHECK: the move gives check; GN_FLAG_NO_MOVES: the
                         move or the reply ends the game; GN_FLAG_SEARCHED: the leaf was valued by
-                        the leaf rule's search; GN_FLAG_NO_SCORE: an empty line                 */
-  uint16_t plies;    /* 3; 2 or 1 when the game ends earlier; 0 for an empty line               */
+                        the leaf rule's search; GN_FLAG_NO_SCORE: an empty line; GN_FLAG_DRAW: the
+                        history calls only                                                      */
+  uint16_t plies;    /* 3; 2 or 1 when the game ends earlier (or, in the history calls, reaches a
+                        position drawn by rule); 0 for an empty line                            */
   uint16_t reserved; /* 0 */
 } gn_line3;
 
@@ -955,6 +998,19 @@ GN_API int gn_evaluate_lines3(gn_ctx *ctx, const char *const *fens, size_t n, in
 GN_API int gn_evaluate_games_lines3(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
                                     int leaf, int depth, uint32_t *position_offsets, int32_t *game_status,
                                     gn_eval *position_out, size_t position_cap, gn_line3 *lines, gn_pv *pvs);
+/* gn_evaluate_games_lines3 with the game-history draws at the child, the reply and the answer (the
+ * rule at gn_line3, "game history"): the same arguments, errors and front, byte for byte.  The keys of
+ * the replayed positions are computed on the device once per shard (GN_STAT_KEYS_NS), as for
+ * gn_evaluate_games_lines2_history; per chunk the roots' gn_history entries are spread to their
+ * children, which run through the two-ply history ranking one ply ahead of the game, and the root step
+ * is rank_lines3_kernel's history variant (GN_STAT_RANK3_NS); the spreading kernel's time is counted
+ * in no stage statistic, only in GN_STAT_HOST_TOTAL_NS.  A drawn child's two-ply line is computed and
+ * then dropped.  Results are identical for every chunk size, GN_OPT_EXPAND_PIPELINE and
+ * device count. */
+GN_API int gn_evaluate_games_lines3_history(gn_ctx *ctx, const gn_game *games, size_t n_games, int mode, int n_lines,
+                                            int leaf, int depth, uint32_t *position_offsets, int32_t *game_status,
+                                            gn_eval *position_out, size_t position_cap, gn_line3 *lines,
+                                            gn_pv *pvs);
 
 /* The partitioner the library uses to shard work over the devices of a context and
  * that multi-process callers use to shard over ranks: contiguous ranges of n_items
@@ -1147,6 +1203,20 @@ GN_API int gn_rank_lines2_extended_device(gn_ctx *ctx, int device_slot, const gn
                                           const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
                                           const gn_history *d_hist, const int32_t *d_gext, int n_lines,
                                           gn_line2 *d_lines, void *stream);
+/* gn_rank_lines2_extended_device with the history window `ahead` plies ahead of the game: parent i is
+ * not the position at d_keys[d_hist[i].self] but lies `ahead` plies after it (ahead = 1: a child of
+ * it, the three-ply chain's parents; the parent itself has no key in the array).  A child is then
+ * tested against the len + ahead positions first..=self, being 1 + ahead plies after the newest, and a
+ * grandchild likewise 2 + ahead plies after it; "no history" entries stay so.  No key at or beyond
+ * n_keys or below first is read.  ahead = 0: byte-equal to gn_rank_lines2_extended_device; ahead
+ * outside 0..1: GN_E_INVALID. */
+GN_API int gn_rank_lines2_ahead_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                       const uint32_t *d_offsets, const gn_board *d_children,
+                                       const gn_eval *d_child_out, const uint16_t *d_moves,
+                                       const uint32_t *d_goffsets, const uint16_t *d_gmoves,
+                                       const gn_eval *d_grand_out, const uint64_t *d_keys, size_t n_keys,
+                                       const gn_history *d_hist, const int32_t *d_gext, int ahead, int n_lines,
+                                       gn_line2 *d_lines, void *stream);
 /* The root step of the three-ply lines alone (the rule at gn_line3): d_lines[i * n_lines + k] = line
  * k + 1 of parent i, from the root expansion as gn_expand_device wrote it (d_offsets, d_moves,
  * d_child_out: only the records' GN_FLAG_IN_CHECK is read) and d_child_lines[j] = line 1 of the
@@ -1164,6 +1234,22 @@ GN_API int gn_rank_lines3_device(gn_ctx *ctx, int device_slot, const gn_board *d
                                  const uint32_t *d_offsets, const uint16_t *d_moves, const gn_eval *d_child_out,
                                  size_t total, const gn_line2 *d_child_lines, const gn_pv *d_child_pvs, int n_lines,
                                  gn_line3 *d_lines, gn_pv *d_pvs, void *stream);
+/* gn_rank_lines3_device with the game-history draws at the child (the rule at gn_line3, "game
+ * history"): d_children are the root expansion's child boards as gn_expand_device wrote them, and
+ * d_hist[i] names parent i's game so far in d_keys[0, n_keys), as for gn_rank_lines2_history_device:
+ * an entry with first > self or self >= n_keys is "no history" (the fifty-move part still applies),
+ * d_keys is never read at or beyond n_keys and may be NULL when n_keys is 0.  A child whose line is
+ * not empty and that is drawn by rule overrides its line (rule 2); a child line's GN_FLAG_DRAW passes
+ * into the root's line, so d_child_lines are to come from gn_rank_lines2_ahead_device at ahead = 1
+ * with each child's entry its parent's.  d_hist == NULL: no history at all, byte-equal to
+ * gn_rank_lines3_device (d_children and d_keys are not read).  Otherwise as gn_rank_lines3_device;
+ * d_children is one of the buffers that may be NULL only when total is 0. */
+GN_API int gn_rank_lines3_history_device(gn_ctx *ctx, int device_slot, const gn_board *d_parents, size_t n,
+                                         const uint32_t *d_offsets, const uint16_t *d_moves,
+                                         const gn_eval *d_child_out, size_t total, const gn_line2 *d_child_lines,
+                                         const gn_pv *d_child_pvs, const gn_board *d_children,
+                                         const uint64_t *d_keys, size_t n_keys, const gn_history *d_hist,
+                                         int n_lines, gn_line3 *d_lines, gn_pv *d_pvs, void *stream);
 /* Time `iters` complete expansions of device-resident parents (child count +
  * scan + child generation with deltas + evaluation of parents and children in
  * `mode` + the parents' score rule).  Outputs go to the caller's device buffers when given (d_parent_out[n],

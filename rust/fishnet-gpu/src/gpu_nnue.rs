@@ -467,6 +467,24 @@ impl GpuNnue {
     pub fn evaluate_games_lines3(&self, games: &[(CString, CString, Vec<u32>)], n_lines: usize, leaf: i32, depth: i32,
                                  mode: i32)
                                  -> Result<(Vec<u32>, Vec<i32>, Vec<GpuEval>, Vec<GpuLine3>, Vec<GpuPv>), GpuError> {
+        self.games_lines3(games, n_lines, leaf, depth, mode, false)
+    }
+
+    /// evaluate_games_lines3 with each game's history (gn_evaluate_games_lines3_history; the header at
+    /// gn_line3, "game history"): a child, reply or answer that is a third occurrence or reaches the
+    /// fifty-move rule is the draw Stockfish sees there (GN_FLAG_DRAW, value 0; `plies` says at which
+    /// of the three it lies).  What `position fen ... moves ...` analysis takes at depth 3.
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn evaluate_games_lines3_history(&self, games: &[(CString, CString, Vec<u32>)], n_lines: usize, leaf: i32,
+                                         depth: i32, mode: i32)
+                                         -> Result<(Vec<u32>, Vec<i32>, Vec<GpuEval>, Vec<GpuLine3>, Vec<GpuPv>), GpuError> {
+        self.games_lines3(games, n_lines, leaf, depth, mode, true)
+    }
+
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    fn games_lines3(&self, games: &[(CString, CString, Vec<u32>)], n_lines: usize, leaf: i32, depth: i32, mode: i32,
+                    history: bool)
+                    -> Result<(Vec<u32>, Vec<i32>, Vec<GpuEval>, Vec<GpuLine3>, Vec<GpuPv>), GpuError> {
         let (gs, cap) = games_and_capacity(games);
         let mut offsets = vec![0u32; games.len() + 1];
         let mut status = vec![0i32; games.len()];
@@ -474,10 +492,10 @@ impl GpuNnue {
         let mut lines = vec![GpuLine3::default(); cap * n_lines];
         let mut pvs = vec![GpuPv::default(); cap * n_lines];
         // SAFETY: as evaluate_games_lines2_quiescent_pv.
+        let call = if history { sys::gn_evaluate_games_lines3_history } else { sys::gn_evaluate_games_lines3 };
         check(unsafe {
-            sys::gn_evaluate_games_lines3(self.0, gs.as_ptr(), gs.len(), mode, n_lines as i32, leaf, depth,
-                                          offsets.as_mut_ptr(), status.as_mut_ptr(), evals.as_mut_ptr(), cap,
-                                          lines.as_mut_ptr(), pvs.as_mut_ptr())
+            call(self.0, gs.as_ptr(), gs.len(), mode, n_lines as i32, leaf, depth, offsets.as_mut_ptr(),
+                 status.as_mut_ptr(), evals.as_mut_ptr(), cap, lines.as_mut_ptr(), pvs.as_mut_ptr())
         })?;
         let total = offsets[games.len()] as usize;
         evals.truncate(total);

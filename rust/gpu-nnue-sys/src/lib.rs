@@ -339,6 +339,10 @@ extern "C" {
                                     n_lines: c_int, leaf: c_int, depth: c_int, position_offsets: *mut u32,
                                     game_status: *mut i32, position_out: *mut gn_eval, position_cap: usize,
                                     lines: *mut gn_line3, pvs: *mut gn_pv) -> c_int;
+    pub fn gn_evaluate_games_lines3_history(ctx: *mut gn_ctx, games: *const gn_game, n_games: usize, mode: c_int,
+                                            n_lines: c_int, leaf: c_int, depth: c_int, position_offsets: *mut u32,
+                                            game_status: *mut i32, position_out: *mut gn_eval, position_cap: usize,
+                                            lines: *mut gn_line3, pvs: *mut gn_pv) -> c_int;
     pub fn gn_partition(weights: *const u32, n_items: usize, n_shards: c_int, bounds: *mut usize) -> c_int;
     pub fn gn_perft(ctx: *mut gn_ctx, fen: *const c_char, depth: c_int, nodes: *mut u64) -> c_int;
     pub fn gn_pack_fens(fens: *const *const c_char, n: usize, out: *mut gn_board, ok: *mut u8) -> c_int;
@@ -404,6 +408,18 @@ extern "C" {
                                  d_offsets: *const u32, d_moves: *const u16, d_child_out: *const gn_eval, total: usize,
                                  d_child_lines: *const gn_line2, d_child_pvs: *const gn_pv, n_lines: c_int,
                                  d_lines: *mut gn_line3, d_pvs: *mut gn_pv, stream: *mut c_void) -> c_int;
+    pub fn gn_rank_lines3_history_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                                         d_offsets: *const u32, d_moves: *const u16, d_child_out: *const gn_eval,
+                                         total: usize, d_child_lines: *const gn_line2, d_child_pvs: *const gn_pv,
+                                         d_children: *const gn_board, d_keys: *const u64, n_keys: usize,
+                                         d_hist: *const gn_history, n_lines: c_int, d_lines: *mut gn_line3,
+                                         d_pvs: *mut gn_pv, stream: *mut c_void) -> c_int;
+    pub fn gn_rank_lines2_ahead_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
+                                       d_offsets: *const u32, d_children: *const gn_board,
+                                       d_child_out: *const gn_eval, d_moves: *const u16, d_goffsets: *const u32,
+                                       d_gmoves: *const u16, d_grand_out: *const gn_eval, d_keys: *const u64,
+                                       n_keys: usize, d_hist: *const gn_history, d_gext: *const i32, ahead: c_int,
+                                       n_lines: c_int, d_lines: *mut gn_line2, stream: *mut c_void) -> c_int;
     pub fn gn_rank_children_extended_device(ctx: *mut gn_ctx, device_slot: c_int, d_parents: *const gn_board, n: usize,
                                             d_offsets: *const u32, d_moves: *const u16, d_child_out: *const gn_eval,
                                             d_keys: *const u64, n_keys: usize, d_hist: *const gn_history,
